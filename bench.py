@@ -11,21 +11,25 @@ segment of every frame through the classifier (inputs cut on the device by swk_s
 keep-if-argmax==1 rule (segment_classification.py:36-39) reduced to kept segments per frame -- the reference's
 __main__.py:77-85 for the whole batch.  value = ROI frames/s over all ranks.
 
-After the headline loop a second timed loop runs the image_filtering part alone (BASELINE configs[1] as worded:
-"image_filtering HIP kernels") and reports it, with the streaming kernel's roofline, under "segment_only".
+A plain run sets up, warms up, times exactly --steps steps and prints the line (contract fields + "roofline" +
+"roofline_cnn" + "kernel_ms_per_step", all from the timed steps themselves).  --dump-outputs DIR then also writes what the
+last timed step computed as DIR/<name>.npy (float32 / float64, under 64 MB; see dump_outputs).
 
-After that, on rank 0 at N = 1, the reference's own call pattern is timed from host 1080p frames (sub-results, never `value`):
-"drop_in" = FrameQueue() as the CLI constructs it, push + preprocess_queue + segment_queue per 21-frame window
-(__main__.py:73-78); "count_loop" = swift_counting_algorithm (__main__.py:56-100) with the classifier ON (the calibrated head),
-tracker and events; "pcie_inclusive" = a segment step fed from host memory.
+Everything else runs only with --full:
+a second timed loop of the image_filtering part alone (BASELINE configs[1] as worded: "image_filtering HIP kernels"),
+reported with the streaming kernel's roofline under "segment_only"; then, on rank 0 at N = 1, the reference's own call pattern
+timed from host 1080p frames (sub-results, never `value`): "drop_in" = FrameQueue() as the CLI constructs it, push +
+preprocess_queue + segment_queue per 21-frame window (__main__.py:73-78); "count_loop" = swift_counting_algorithm
+(__main__.py:56-100) with the classifier ON (the calibrated head), tracker and events; "pcie_inclusive" = a segment step fed
+from host memory; the CPU baseline with its "parity" check; and the "video_sharded" leg (BASELINE configs 4 / 5).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full        (+ segment_only, drop_in, count_loop, pcie_inclusive, cpu_baseline, ...)
     python bench.py --gpus N ...            (starts N ranks itself: one fresh process per GPU, RCCL; this process never touches a GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract fields + "roofline" + "roofline_cnn" + "segment_only" + "drop_in" + "count_loop" +
-"pcie_inclusive" + "cpu_baseline").
+Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -95,7 +99,15 @@ def parse():
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="launcher rehearsal without any GPU work: the ranks join the process group (SWK_DIST_BACKEND, gloo on CPU-only "
                          "hosts), run the barrier / max-over-ranks clock / count gather around EMPTY steps and print the line with value 0")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the headline loop: segment_only, video_sharded, pcie_inclusive, drop_in, "
+                         "count_loop, cpu_baseline and its parity check (the --no-* switches above then turn single legs off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32 / float64, < 64 MB")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args):
@@ -558,6 +570,66 @@ def video_sharded_leg(args, rank, world, local, clf):
     return out
 
 
+DUMP_SEED = 20190816
+
+
+def dump_outputs(path, labels, segs, nseg, iters, seg_cap, last):
+    """--dump-outputs: what the last timed step handed its caller, as .npy files (float32, float64 where an integer may pass 2^24).
+    Inputs are seeded, so two builds can be compared file by file.  Arrays above their byte budget are a fixed, seeded sample of
+    rows, sorted, with the rows taken in <name>_rows.npy; the budgets add up to under 64 MB.
+        iters               (windows,)          IALM iterations per window
+        nseg                (frames,)           region records per frame
+        segments            (records, 8) f64    label, r0, c0, r1, c1, area, sum_r, sum_c of every frame's valid records, frame order
+        segment_frame       (records,)          frame of each record
+        labels              (k, Hc, Wc)         label images of k frames drawn with a fixed seed (labels_rows.npy: which frames)
+        classifier_scores   (rows, 2)           the classifier's scores, one row per segment it ran on
+        classifier_frame    (rows,)             frame of each score row
+        kept_per_frame      (frames,)           segments kept by the argmax == 1 rule, per frame"""
+    import numpy as np
+    import torch
+    from swiftwatcher_amd import _lib
+    os.makedirs(path, exist_ok=True)
+    mb = 1000 * 1000          # worst case of all files together: about 60 MB
+
+    def rows_within(n, row_bytes, budget, seed):
+        """None (all rows fit) or the sorted seeded sample of rows that fits `budget` together with its index"""
+        if n * row_bytes <= budget:
+            return None
+        k = int(budget // (row_bytes + 8))
+        return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+    def save(name, arr, budget, seed, rows=None):
+        arr = np.ascontiguousarray(arr)
+        if rows is None and arr.shape:
+            rows = rows_within(arr.shape[0], arr[:1].nbytes, budget, seed)
+        if rows is not None:
+            arr = arr[rows]
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), arr)
+        return rows
+
+    F, Hc, Wc = labels.shape
+    save("iters", iters.cpu().numpy().astype(np.float32), 1 * mb, DUMP_SEED)
+    nseg_h = np.minimum(nseg.cpu().numpy().astype(np.int64), seg_cap)
+    save("nseg", nseg_h.astype(np.float32), 2 * mb, DUMP_SEED + 1)
+    rec = segs.cpu().numpy().reshape(F * seg_cap * segs.shape[2]).view(_lib.SEGMENT_DTYPE).reshape(F, seg_cap)
+    valid = np.arange(seg_cap)[None, :] < nseg_h[:, None]
+    rec = rec[valid]                                                     # frame-major, each frame's records in their order
+    fields = ("label", "r0", "c0", "r1", "c1", "area", "sum_r", "sum_c")
+    seg_arr = np.stack([rec[f].astype(np.float64) for f in fields], axis=1) if len(rec) else np.zeros((0, 8))
+    seg_rows = save("segments", seg_arr, 20 * mb, DUMP_SEED + 2)
+    save("segment_frame", np.nonzero(valid)[0].astype(np.float32), 4 * mb, DUMP_SEED + 2, rows=seg_rows)
+    k = max(1, min(16, F, (20 * mb) // (Hc * Wc * 4)))
+    pick = np.sort(np.random.default_rng(DUMP_SEED + 3).choice(F, size=k, replace=False))
+    np.save(os.path.join(path, "labels_rows.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "labels.npy"), labels[torch.from_numpy(pick).to(labels.device)].cpu().numpy().astype(np.float32))
+    if last:
+        scores = last["scores"].float().cpu().numpy()
+        sc_rows = save("classifier_scores", scores, 6 * mb, DUMP_SEED + 4)
+        save("classifier_frame", last["fidx"].cpu().numpy().astype(np.float32), 3 * mb, DUMP_SEED + 4, rows=sc_rows)
+        save("kept_per_frame", last["per_frame"].cpu().numpy().astype(np.float32), 2 * mb, DUMP_SEED + 5)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -674,6 +746,8 @@ def main():
         sd["classifier.1.bias"] = torch.tensor([big, big - float(d.median())])
         clf = SegmentClassifier.from_state_dict(sd, device=dev, batch_size=args.cls_batch, cropped=not args.full_network)
 
+    last = {}          # the classifier's products of the latest step (--dump-outputs)
+
     def step():
         segment_step()
         if clf is not None:
@@ -682,6 +756,7 @@ def main():
             per_frame = torch.bincount(fidx[keep].to(torch.int64), minlength=F)      # kept segments of every frame
             kept_total[0] = int(per_frame.sum().item())
             kept_total[1] = int(scores.shape[0])
+            last.update(scores=scores, fidx=fidx, per_frame=per_frame)
 
     own_dt = [0.0]
 
@@ -716,6 +791,8 @@ def main():
         step()
     redo0, redo_w0 = ctx.redo_batches, ctx.redo_windows
     dt_max, prof, bpe, net = timed(step)
+    if args.dump_outputs and rank == 0:          # before any other loop reuses the buffers
+        dump_outputs(args.dump_outputs, labels, segs, nseg, iters, seg_cap, last)
     overlapped = None
     if args.overlap and clf is not None:
         # Two-stage software pipeline over the SAME K steps: products of step i+1 go to a second set of buffers while
@@ -760,13 +837,13 @@ def main():
                       "kept_last_step": kept_o, "same_kept_as_serial": kept_o == kept_total[0]}
         ctx2.close()
     # second loop: the image_filtering part alone (same data, same step count)
-    seg_only = timed(segment_step) if clf is not None else None
+    seg_only = timed(segment_step) if clf is not None and args.full else None
     redo = ctx.redo_batches - redo0
 
     # ---- configs 4 / 5 as worded: videos sharded over the ranks, per-video counts gathered (every rank takes part) ----
     # (with one rank the leg runs last, below: its gigabytes of host frames would otherwise leave the Python heap in a state that
     #  costs the host-side sub-results -- drop_in, count_loop -- up to half of their throughput in this sandbox)
-    video_sharded = video_sharded_leg(args, rank, world, local, clf) if args.video_windows > 0 and world > 1 else None
+    video_sharded = video_sharded_leg(args, rank, world, local, clf) if args.full and args.video_windows > 0 and world > 1 else None
 
     # ---- per-rank counts gathered over RCCL (the only collective of the path) ----
     it_host = iters.cpu().numpy()
@@ -888,15 +965,16 @@ def main():
                 "segments_per_step": kept_total[1], "forwards_per_step": int(calls / args.steps),
                 "net_ms_per_step": round(net_ms / args.steps, 3),
                 "segments_per_s_in_network": round(rows / (net_ms * 1e-3), 1) if net_ms > 0 else 0.0}
-            so_dt, so_prof, so_bpe, _ = seg_only
             if overlapped is not None:
                 res["overlapped"] = overlapped
-            res["segment_only"] = {"metric": "frames/sec (segment) on 1080p ROI batches", "value": round(total_frames / so_dt, 2),
-                                   "ms_per_step": round(so_dt / args.steps * 1e3, 3), "roofline": pass_roofline(so_prof, so_bpe),
-                                   "kernel_ms_per_step": kernel_ms(so_prof)}
+            if seg_only is not None:
+                so_dt, so_prof, so_bpe, _ = seg_only
+                res["segment_only"] = {"metric": "frames/sec (segment) on 1080p ROI batches", "value": round(total_frames / so_dt, 2),
+                                       "ms_per_step": round(so_dt / args.steps * 1e3, 3), "roofline": pass_roofline(so_prof, so_bpe),
+                                       "kernel_ms_per_step": kernel_ms(so_prof)}
         if video_sharded is not None:
             res["video_sharded"] = video_sharded
-        if world == 1 and not args.no_drop_in:
+        if args.full and world == 1 and not args.no_drop_in:
             # the same segment step fed from host memory (ROI frames in page-locked memory, one copy per batch), 32 windows
             hw_ = min(nwin, 32)
             host = _lib.pinned_empty((hw_ * n, Hc, Wc, 3), np.uint8, device=local)
@@ -920,7 +998,7 @@ def main():
                     traceback.print_exc()
                     res["drop_in"] = res.get("drop_in", {"error": repr(exc)})
                     res["count_loop"] = {"error": repr(exc)}
-        if world == 1 and not args.no_cpu_baseline:          # the CPU baseline is a single-GPU-run companion (rank 0 at N = 1 only)
+        if args.full and world == 1 and not args.no_cpu_baseline:          # the CPU baseline is a single-GPU-run companion (rank 0 at N = 1 only)
             try:
                 sample = {}
                 res["cpu_baseline"] = cpu_baseline(n, Hc, Wc, args.cpu_windows, clf is not None, sample=sample)
@@ -929,7 +1007,7 @@ def main():
                 import traceback
                 traceback.print_exc()
                 res["cpu_baseline"] = {"error": repr(exc)}
-        if world == 1 and args.video_windows > 0:
+        if args.full and world == 1 and args.video_windows > 0:
             try:
                 res["video_sharded"] = video_sharded_leg(args, rank, world, local, clf)
             except Exception as exc:          # noqa: BLE001

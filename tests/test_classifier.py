@@ -1,12 +1,25 @@
 """segment_classification drop-in: structure checks on CPU, scores/decisions against the CPU oracle
 on the GPU (float32, tolerance 2e-4 on scores that are O(1); decisions identical away from ties)."""
+import hashlib
 import os
 
 import numpy as np
 import pytest
 import torch
 
-REF_MODEL = "/root/reference/swiftwatcher/model.pt"
+# SHA-256 over the reference's swiftwatcher/model.pt, tensor by tensor in key order (name, shape, float32 bytes): the weights
+# tests/golden/classifier_model_pt.npz must hold, checked without the checkpoint itself (see _weights_digest)
+MODEL_PT_SHA256 = "71c5518e3bd53723dd9f6b7c9596c904ba2b2c5d1c54c97ad890cc340c076d53"
+
+
+def _weights_digest(sd):
+    h = hashlib.sha256()
+    for k in sorted(sd):
+        a = np.ascontiguousarray(np.asarray(sd[k], dtype=np.float32))
+        h.update(k.encode())
+        h.update(str(a.shape).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
 
 
 def _segments(rng, n):
@@ -20,7 +33,7 @@ def _segments(rng, n):
     return out
 
 
-def test_topology_matches_reference_weights_when_present():
+def test_topology_matches_reference_weights_when_present(golden_dir):
     from swiftwatcher_amd.segment_classification import SqueezeNet10
     from oracle import classifier_ref as ref
     m = SqueezeNet10(2)
@@ -29,9 +42,8 @@ def test_topology_matches_reference_weights_when_present():
     assert keys == set(ref.random_state_dict(0).keys())
     for k, shp in ref.EXPECTED_SHAPES.items():
         assert tuple(m.state_dict()[k].shape) == shp
-    if os.path.exists(REF_MODEL):      # build container only: the reference's own weight file
-        sd = torch.load(REF_MODEL, map_location="cpu", weights_only=True)
-        m.load_state_dict(sd, strict=True)
+    sd, _, _, _ = _model_pt_fixture(golden_dir)          # the reference's own weights, as stored with the tests
+    m.load_state_dict(sd, strict=True)
 
 
 def test_classifier_requires_gpu_unless_asked(tmp_path):
@@ -259,9 +271,7 @@ def test_model_pt_weights_load_strict_and_oracle_reproduces_fixture(golden_dir):
     sd, crops, scores, keep = _model_pt_fixture(golden_dir)
     assert len(sd) == 52 and sum(v.numel() for v in sd.values()) == 736450
     SqueezeNet10(2).load_state_dict(sd, strict=True)
-    if os.path.exists(REF_MODEL):      # build container: the arrays ARE the checkpoint's tensors
-        disk = torch.load(REF_MODEL, map_location="cpu", weights_only=True)
-        assert set(disk) == set(sd) and all(torch.equal(disk[k].float(), sd[k]) for k in sd)
+    assert _weights_digest({k: v.numpy() for k, v in sd.items()}) == MODEL_PT_SHA256      # the arrays ARE the checkpoint's tensors
     got, got_keep = ref.classify(sd, crops[:32])
     np.testing.assert_allclose(got, scores[:32], atol=2e-4, rtol=1e-4)
     assert list(got_keep) == list(keep[:32])

@@ -216,7 +216,7 @@ def test_bench_video_sharded_leg_with_two_ranks_on_one_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--windows", "4",
-                          "--no-cpu-baseline", "--no-drop-in", "--video-windows", "4", "--verify-all-videos"],
+                          "--full", "--no-cpu-baseline", "--no-drop-in", "--video-windows", "4", "--verify-all-videos"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])

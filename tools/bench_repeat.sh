@@ -1,9 +1,9 @@
 #!/bin/bash
-# the driver's command several times in a row (GPU box): the threaded side measurements must neither fail nor change their counts
+# bench.py --full several times in a row (GPU box): the threaded side measurements must neither fail nor change their counts
 out=${1:-gpurun_out/repeat}; runs=${2:-4}
 mkdir -p $out
 for i in $(seq 1 $runs); do
-  timeout -k 10 240 python bench.py --no-cpu-baseline --steps 3 --warmup 1 > $out/b$i.json 2> $out/b$i.err || { echo "run $i failed"; tail -n 5 $out/b$i.err; exit 1; }
+  timeout -k 10 240 python bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $out/b$i.json 2> $out/b$i.err || { echo "run $i failed"; tail -n 5 $out/b$i.err; exit 1; }
 done
 python3 - "$out" "$runs" <<'PY'
 import json, sys

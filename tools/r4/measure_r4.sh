@@ -10,9 +10,9 @@ mkdir -p $out
 export TMPDIR=/tmp
 step() { local name=$1 tmo=$2; shift 2; timeout -k 10 $tmo "$@" > $out/$name 2> $out/$name.err || { echo "FAILED: $name"; tail -n 5 $out/$name.err; exit 1; }; }
 if [ "$part" = a ]; then
-  step default.json 600 python bench.py
+  step default.json 600 python bench.py --full
   rm -rf $out/prof
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --no-cpu-baseline --no-drop-in --video-windows 0 --steps 2 --warmup 1 > $out/prof_bench.json 2> $out/prof_bench.err || { echo "FAILED: rocprofv3 stats"; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -- python3 bench.py --full --no-cpu-baseline --no-drop-in --video-windows 0 --steps 2 --warmup 1 > $out/prof_bench.json 2> $out/prof_bench.err || { echo "FAILED: rocprofv3 stats"; exit 1; }
   cp $(ls $out/prof/*/*kernel_stats.csv | head -1) $out/r4_kernel_stats_default_bench.csv
   rm -rf $out/prof
   for c in FETCH_SIZE WRITE_SIZE; do
@@ -26,9 +26,9 @@ if [ "$part" = a ]; then
   head -4 $out/r4_kernel_stats_default_bench.csv | cut -c1-200
   cut -c1-300 $out/default.json
 else
-  step n21.json 300 python bench.py --no-cpu-baseline --no-drop-in --video-windows 0 --n 21 --windows 384 --steps 5
-  step p3_n21.json 300 python bench.py --no-cpu-baseline --no-drop-in --video-windows 0 --size P3 --n 21 --windows 96 --steps 5
-  SWK_DIST_BACKEND=gloo step launcher_2ranks_gloo_one_gpu.json 600 python bench.py --gpus 2 --steps 3 --warmup 1 --windows 32 --no-cpu-baseline --no-drop-in --video-windows 12 --verify-all-videos
-  step video_config5_one_gpu.json 300 python bench.py --steps 1 --warmup 0 --windows 8 --no-cpu-baseline --no-drop-in --video-config 5 --video-windows 24
+  step n21.json 300 python bench.py --full --no-cpu-baseline --no-drop-in --video-windows 0 --n 21 --windows 384 --steps 5
+  step p3_n21.json 300 python bench.py --full --no-cpu-baseline --no-drop-in --video-windows 0 --size P3 --n 21 --windows 96 --steps 5
+  SWK_DIST_BACKEND=gloo step launcher_2ranks_gloo_one_gpu.json 600 python bench.py --full --gpus 2 --steps 3 --warmup 1 --windows 32 --no-cpu-baseline --no-drop-in --video-windows 12 --verify-all-videos
+  step video_config5_one_gpu.json 300 python bench.py --full --steps 1 --warmup 0 --windows 8 --no-cpu-baseline --no-drop-in --video-config 5 --video-windows 24
   cut -c1-200 $out/n21.json; cut -c1-200 $out/p3_n21.json
 fi
