@@ -173,6 +173,14 @@ int32_t swk_device_read(swk_ctx *ctx, const void *src_device, void *dst_host, in
  * threshold -> 3x3 grey opening -> connected components -> region properties.
  * Windows are independent (no state is carried between them). */
 int32_t swk_batch_run(swk_ctx *ctx, const swk_input *in, const swk_params *p, swk_output *out);
+/* Several groups of windows in ONE call.  A group is what one swk_batch_run call takes: one video's windows with its own frames
+ * pointer, mem, channels, nwin, Hc, Wc, x0, y0, frame_stride and row_stride.  Every group has the same n.  outs[g] receives group
+ * g's results with exactly the layout and meaning swk_batch_run gives them.  The IALM runs over all groups at once on planes
+ * zero-padded to the largest ROI (exact: the padding leaves X^T X, ||X||_F and max|X| unchanged); a group whose ROI has fewer
+ * pixels than n runs as a sub-batch of its own.  Errors as swk_batch_run, checked per group before anything is launched, and
+ * SWK_ERR_ARG when the groups' n differ.  swk_segment_inputs_last then serves every group's segments, in group order, then
+ * frame order. */
+int32_t swk_batch_run_groups(swk_ctx *ctx, const swk_input *groups, int32_t ngroups, const swk_params *p, swk_output *outs);
 
 /* ---- stage-level entry points (host buffers; used by the parity tests and by the
  *      image_filtering.* drop-in functions) ------------------------------------- */

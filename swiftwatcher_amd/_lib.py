@@ -79,6 +79,7 @@ _SIGS = {
     "swk_last_error": (ctypes.c_char_p, [ctypes.c_void_p]),
     "swk_ctx_device_bytes": (ctypes.c_int64, [ctypes.c_void_p]),
     "swk_batch_run": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Params), ctypes.POINTER(Output)]),
+    "swk_batch_run_groups": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.c_int32, ctypes.POINTER(Params), ctypes.POINTER(Output)]),
     "swk_bgr2gray": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "swk_ialm": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_rpca_epilogue": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -466,6 +467,76 @@ class Context:
         out.segs = res["segs"].ctypes.data
         res["generation"] = self.batch_run_raw(inp, params, out)          # for swk_segment_inputs_last (segment_inputs_last)
         return res
+
+    def batch_run_groups(self, groups, params=None, stages=STAGES, want_A=False, want_E=False, seg_cap=255):
+        """swk_batch_run_groups: several groups of windows (one video's windows each, each with its own geometry) in ONE call.
+        groups: dicts with batch_run's per-batch arguments -- frames, nwin, n, and optionally crop, reverse_frames, seg_cap.
+        frames may also be a device tensor (torch, on this context's GPU, C-contiguous along rows / columns / channels): it is
+        read in place (SWK_MEM_DEVICE).  Returns one dict per group, in the shape batch_run returns; every dict carries the
+        call's 'generation' (swk_segment_inputs_last then serves all groups' segments, group order, then frame order)."""
+        params = params or default_params()
+        G = len(groups)
+        if G < 1:
+            raise ValueError("no groups")
+        ins = (Input * G)()
+        outs = (Output * G)()
+        results, keep = [], []
+        for g, grp in enumerate(groups):
+            frames, nwin, n = grp["frames"], int(grp["nwin"]), int(grp["n"])
+            cap = int(grp.get("seg_cap", seg_cap))
+            F = nwin * n
+            on_device = hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False)
+            shape = tuple(frames.shape)
+            if on_device:
+                if str(frames.dtype) != "torch.uint8":
+                    raise ValueError("frames must be uint8")
+                strides = tuple(int(x) for x in frames.stride())           # (elements = bytes for uint8)
+                base = frames.data_ptr()
+            else:
+                if frames.dtype != np.uint8:
+                    raise ValueError("frames must be uint8")
+                strides, base = frames.strides, frames.ctypes.data
+                keep.append(frames)
+            if shape[0] != F or len(shape) not in (3, 4):
+                raise ValueError("frames must be uint8 (nwin*n, H, W[, 3])")
+            ch = 1 if len(shape) == 3 else shape[3]
+            if (len(shape) == 4 and (strides[3] != 1 or strides[2] != ch)) or (len(shape) == 3 and strides[2] != 1):
+                raise ValueError("frames must be contiguous along columns/channels")
+            H, W = shape[1], shape[2]
+            x0, y0, Wc, Hc = grp.get("crop") or (0, 0, W, H)
+            if x0 < 0 or y0 < 0 or x0 + Wc > W or y0 + Hc > H:
+                raise ValueError("crop rectangle outside the frame")
+            rev = bool(grp.get("reverse_frames", False))
+            ins[g] = Input(frames=base + ((F - 1) * strides[0] if rev else 0), mem=MEM_DEVICE if on_device else MEM_HOST, channels=ch,
+                           nwin=nwin, n=n, Hc=Hc, Wc=Wc, x0=x0, y0=y0, frame_stride=-strides[0] if rev else strides[0],
+                           row_stride=strides[1])
+            res = {}
+            out = Output(mem=MEM_HOST, seg_cap=cap)
+            for name in stages:
+                res[name] = np.empty((F, Hc, Wc), np.uint8)
+                setattr(out, name, res[name].ctypes.data)
+            P = Hc * Wc
+            if want_A:
+                res["A"] = np.empty((nwin, P, n), np.float64)
+                out.A = res["A"].ctypes.data
+            if want_E:
+                res["E"] = np.empty((nwin, P, n), np.float64)
+                out.E = res["E"].ctypes.data
+            res["iters"] = np.zeros(nwin, np.int32)
+            res["nseg"] = np.zeros(F, np.int32)
+            res["segs"] = np.zeros((F, cap), SEGMENT_DTYPE)
+            out.iters = res["iters"].ctypes.data
+            out.nseg = res["nseg"].ctypes.data
+            out.segs = res["segs"].ctypes.data
+            outs[g] = out
+            results.append(res)
+        with self._lock:
+            self.generation += 1
+            generation = self.generation
+            self._check(self._lib.swk_batch_run_groups(self._h, ins, G, ctypes.byref(params), outs))
+        for res in results:
+            res["generation"] = generation
+        return results
 
     # ---- stage-level entry points ----
     def bgr2gray(self, bgr, gray_mode=GRAY_Q14):

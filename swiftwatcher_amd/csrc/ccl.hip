@@ -320,16 +320,25 @@ __device__ __forceinline__ int next_fg(const uint32_t *fgr, int b, int be)
     return -1;
 }
 
-template <int VEC, bool PROPS>
+// GEOM: frame f's H, W and plane offset come from geom[f] (swk_batch_run_groups; H = 0: the frame is not this launch's), its id
+// space and LDS layout are sized for that frame (the launch's LDS for the largest); otherwise every frame is H x W, packed densely.
+template <int VEC, bool PROPS, bool GEOM = false>
 __global__ __launch_bounds__(kFrameThreads) void k_ccl_frame(const uint8_t *__restrict__ src, int H, int W, int order, int conn8,
                                                              int *__restrict__ parent, int Pp, int words, int cap,
                                                              int32_t *__restrict__ labels32, uint8_t *__restrict__ labels8,
                                                              int32_t *__restrict__ ncomp, int seg_cap,
-                                                             swk_segment *__restrict__ segs, int32_t *__restrict__ nseg)
+                                                             swk_segment *__restrict__ segs, int32_t *__restrict__ nseg,
+                                                             const FrameGeom *__restrict__ geom)
 {
     extern __shared__ unsigned char lds_raw[];
     FrameLds *L = (FrameLds *)lds_raw;
+    if (GEOM) {
+        H = geom[blockIdx.x].H; W = geom[blockIdx.x].W;
+        if (H == 0) return;
+        words = (int)(((int64_t)((H + 1) / 2) * ((W + 1) / 2) * 4 + 31) / 32);          // ccl_words(H, W)
+    }
     const int P = H * W, Wb = (W + 1) / 2, rwords = (P + 31) >> 5, nwords = P / VEC;
+    const int64_t base = GEOM ? geom[blockIdx.x].off : (int64_t)blockIdx.x * P;
     uint32_t *fgr = (uint32_t *)(lds_raw + sizeof(FrameLds));          // [rwords] raster foreground bitmap
     uint32_t *rsbits = fgr + rwords;                                    // [words]  run starts, id order (roots in the fallback)
     int *rsprefix = (int *)(rsbits + words);                            // [words / kPfx]
@@ -340,7 +349,7 @@ __global__ __launch_bounds__(kFrameThreads) void k_ccl_frame(const uint8_t *__re
     uint32_t *rootbits = (uint32_t *)(rlab + cap);                      // [cap/32]
     int *rootprefix = (int *)(rootbits + cap / 32);                     // [cap/32]
     const int f = blockIdx.x, tid = threadIdx.x;
-    const uint8_t *img = src + (int64_t)f * P;
+    const uint8_t *img = src + base;
     int *par = parent + (int64_t)f * Pp;
 
     for (int i = tid; i < rwords; i += kFrameThreads) fgr[i] = 0u;
@@ -502,7 +511,7 @@ __global__ __launch_bounds__(kFrameThreads) void k_ccl_frame(const uint8_t *__re
     if (by_runs) {
         // sparse frame: clear the plane with full-width stores, then every run paints its own span
         if (labels8) {
-            uint8_t *o = labels8 + (int64_t)f * P;
+            uint8_t *o = labels8 + base;
             if ((P & 15) == 0 && (((uintptr_t)o) & 15) == 0) {
                 for (int i = tid; i < P / 16; i += kFrameThreads) ((uint4 *)o)[i] = make_uint4(0u, 0u, 0u, 0u);
             } else {
@@ -510,7 +519,7 @@ __global__ __launch_bounds__(kFrameThreads) void k_ccl_frame(const uint8_t *__re
             }
         }
         if (labels32) {
-            int32_t *o = labels32 + (int64_t)f * P;
+            int32_t *o = labels32 + base;
             for (int i = tid; i < P; i += kFrameThreads) o[i] = 0;
         }
         __syncthreads();
@@ -518,11 +527,11 @@ __global__ __launch_bounds__(kFrameThreads) void k_ccl_frame(const uint8_t *__re
             const int r = run_rc[run] >> 16, cs = run_rc[run] & 0xffff, ce = run_ce[run];
             const int label = rlab[run];
             if (labels8) {
-                uint8_t *o = labels8 + (int64_t)f * P + r * W;
+                uint8_t *o = labels8 + base + r * W;
                 for (int c = cs; c <= ce; ++c) o[c] = (uint8_t)label;
             }
             if (labels32) {
-                int32_t *o = labels32 + (int64_t)f * P + r * W;
+                int32_t *o = labels32 + base + r * W;
                 for (int c = cs; c <= ce; ++c) o[c] = label;
             }
         }
@@ -536,13 +545,13 @@ __global__ __launch_bounds__(kFrameThreads) void k_ccl_frame(const uint8_t *__re
             packed |= (uint32_t)(lab[k] & 0xff) << (8 * k);
         }
         if (labels8) {
-            uint8_t *o = labels8 + (int64_t)f * P;
+            uint8_t *o = labels8 + base;
             if (VEC == 4) ((uint32_t *)o)[i] = packed;
             else if (VEC == 2) ((uint16_t *)o)[i] = (uint16_t)packed;
             else o[i] = (uint8_t)packed;
         }
         if (labels32) {
-            int32_t *o = labels32 + (int64_t)f * P + VEC * i;
+            int32_t *o = labels32 + base + VEC * i;
 #pragma unroll
             for (int k = 0; k < VEC; ++k) o[k] = lab[k];
         }
@@ -595,7 +604,7 @@ static void launch_frame_t(hipStream_t s, const uint8_t *src, int F, int H, int 
         attr_bytes = lds;
     }
     hipLaunchKernelGGL((k_ccl_frame<VEC, PROPS>), dim3(F), dim3(kFrameThreads), lds, s, src, H, W, order, conn8, b.parent, b.Pp,
-                       b.words, kRunCap, labels32, labels8, b.ncomp, seg_cap, segs, nseg);
+                       b.words, kRunCap, labels32, labels8, b.ncomp, seg_cap, segs, nseg, nullptr);
 }
 
 template <int VEC>
@@ -604,6 +613,29 @@ static void launch_frame_p(hipStream_t s, const uint8_t *src, int F, int H, int 
 {
     if (props) launch_frame_t<VEC, true>(s, src, F, H, W, order, conn8, b, labels32, labels8, seg_cap, segs, nseg);
     else launch_frame_t<VEC, false>(s, src, F, H, W, order, conn8, b, labels32, labels8, seg_cap, segs, nseg);
+}
+
+template <int VEC>
+static void launch_frame_geom_t(hipStream_t s, const uint8_t *src, int F, const FrameGeom *geom, size_t lds, int order, int conn8,
+                                const CclBuffers &b, uint8_t *labels8, int seg_cap, swk_segment *segs, int32_t *nseg)
+{
+    static size_t attr_bytes = 0;
+    if (lds > attr_bytes) {
+        (void)hipFuncSetAttribute((const void *)k_ccl_frame<VEC, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_bytes = lds;
+    }
+    hipLaunchKernelGGL((k_ccl_frame<VEC, true, true>), dim3(F), dim3(kFrameThreads), lds, s, src, 0, 0, order, conn8, b.parent, b.Pp,
+                       b.words, kRunCap, nullptr, labels8, b.ncomp, seg_cap, segs, nseg, geom);
+}
+
+void launch_ccl_frame_geom(hipStream_t s, const uint8_t *src, int F, const FrameGeom *geom, size_t lds, int vec, int connectivity,
+                           int order, const CclBuffers &b, uint8_t *labels8, int seg_cap, swk_segment *segs, int32_t *nseg)
+{
+    if (connectivity == 4) order = SWK_ORDER_RASTER;
+    const int conn8 = connectivity == 8;
+    if (vec == 4) launch_frame_geom_t<4>(s, src, F, geom, lds, order, conn8, b, labels8, seg_cap, segs, nseg);
+    else if (vec == 2) launch_frame_geom_t<2>(s, src, F, geom, lds, order, conn8, b, labels8, seg_cap, segs, nseg);
+    else launch_frame_geom_t<1>(s, src, F, geom, lds, order, conn8, b, labels8, seg_cap, segs, nseg);
 }
 
 void launch_ccl_frame(hipStream_t s, const uint8_t *src, int F, int H, int W, int connectivity, int order, const CclBuffers &b,

@@ -168,6 +168,45 @@ __global__ __launch_bounds__(256) void k_segment_prefix(const int32_t *__restric
     for (int f = lo; f < hi; ++f) { offsets[f] = run; run += nseg[f] < seg_cap ? nseg[f] : seg_cap; }
 }
 
+// extract_segment_images' crop box (image_filtering.py:338-369) of one region record: the bbox grown symmetrically to at least
+// min_h x min_w (floor on the low side, ceil on the high side), moved by the ROI origin into full-frame coordinates, and -- where
+// the reference would mis-slice -- intersected with the frame.  box = {frame, r0, c0, h, w}
+__device__ __forceinline__ void segment_box(const swk_segment &sg, int min_h, int min_w, int x0, int y0, int frame_h, int frame_w,
+                                            int f, int *box)
+{
+    int r0 = sg.r0, c0 = sg.c0, r1 = sg.r1, c1 = sg.c1;
+    const int h = r1 - r0, w = c1 - c0;
+    if (h < min_h) { const int d = min_h - h; r0 -= d / 2; r1 += d - d / 2; }       // :349-358
+    if (w < min_w) { const int d = min_w - w; c0 -= d / 2; c1 += d - d / 2; }
+    r0 += y0; r1 += y0; c0 += x0; c1 += x0;                                          // :361-362
+    r0 = r0 < 0 ? 0 : r0; c0 = c0 < 0 ? 0 : c0;
+    r1 = r1 > frame_h ? frame_h : r1; c1 = c1 > frame_w ? frame_w : c1;
+    box[0] = f; box[1] = r0; box[2] = c0; box[3] = r1 - r0; box[4] = c1 - c0;
+}
+
+// network input of this workgroup's segment from its box in `frame`
+__device__ __forceinline__ void emit_segment(ResizeLds &L, const uint8_t *frame, int64_t row_stride, const int *box, float *net,
+                                             int32_t *seg_frame, int pad, int nhwc, float m0, float m1, float m2, float s0, float s1,
+                                             float s2, int32_t *oversize)
+{
+    const int f = box[0], r0 = box[1], c0 = box[2];
+    int h = box[3], w = box[4];
+    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+    const int side = kOut + 2 * pad;
+    if (seg_frame && threadIdx.x == 0) seg_frame[blockIdx.x] = f;
+    float *o = net + (int64_t)blockIdx.x * 3 * side * side;
+    if (h < 1 || w < 1 || h > kMaxIn || w > kMaxIn) {
+        // empty or oversize box: flagged; the input is the blank image
+        if (threadIdx.x == 0) atomicAdd(oversize, 1);
+        for (int i = threadIdx.x; i < 3 * side * side; i += 256) {
+            const int c = nhwc ? i % 3 : i / (side * side);
+            o[i] = (0.0f - mean[c]) / sd[c];
+        }
+        return;
+    }
+    resize_and_emit(L, frame + (int64_t)r0 * row_stride + (int64_t)c0 * 3, row_stride, h, w, nullptr, o, pad, nhwc, mean, sd);
+}
+
 __global__ __launch_bounds__(256) void k_segment_inputs(const uint8_t *__restrict__ frames, int64_t frame_stride, int64_t row_stride,
                                                         int frame_h, int frame_w, int x0, int y0,
                                                         const swk_segment *__restrict__ segs, const int32_t *__restrict__ offsets,
@@ -186,34 +225,58 @@ __global__ __launch_bounds__(256) void k_segment_inputs(const uint8_t *__restric
             const int mid = (lo + hi) >> 1;
             if (offsets[mid] <= k) lo = mid; else hi = mid;
         }
-        const swk_segment sg = segs[(int64_t)lo * seg_cap + (k - offsets[lo])];
-        int r0 = sg.r0, c0 = sg.c0, r1 = sg.r1, c1 = sg.c1;
-        const int h = r1 - r0, w = c1 - c0;
-        if (h < min_h) { const int d = min_h - h; r0 -= d / 2; r1 += d - d / 2; }       // :349-358
-        if (w < min_w) { const int d = min_w - w; c0 -= d / 2; c1 += d - d / 2; }
-        r0 += y0; r1 += y0; c0 += x0; c1 += x0;                                          // :361-362
-        r0 = r0 < 0 ? 0 : r0; c0 = c0 < 0 ? 0 : c0;
-        r1 = r1 > frame_h ? frame_h : r1; c1 = c1 > frame_w ? frame_w : c1;
-        s_box[0] = lo; s_box[1] = r0; s_box[2] = c0; s_box[3] = r1 - r0; s_box[4] = c1 - c0;
+        segment_box(segs[(int64_t)lo * seg_cap + (k - offsets[lo])], min_h, min_w, x0, y0, frame_h, frame_w, lo, s_box);
     }
     __syncthreads();
-    const int f = s_box[0], r0 = s_box[1], c0 = s_box[2];
-    int h = s_box[3], w = s_box[4];
-    const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
-    const int side = kOut + 2 * pad;
-    if (seg_frame && threadIdx.x == 0) seg_frame[blockIdx.x] = f;
-    float *o = net + (int64_t)blockIdx.x * 3 * side * side;
-    if (h < 1 || w < 1 || h > kMaxIn || w > kMaxIn) {
-        // empty or oversize box: flagged; the input is the blank image
-        if (threadIdx.x == 0) atomicAdd(oversize, 1);
-        for (int i = threadIdx.x; i < 3 * side * side; i += 256) {
-            const int c = nhwc ? i % 3 : i / (side * side);
-            o[i] = (0.0f - mean[c]) / sd[c];
+    const int f = s_box[0];
+    emit_segment(L, frames + (int64_t)f * frame_stride, row_stride, s_box, net, seg_frame, pad, nhwc, m0, m1, m2, s0, s1, s2, oversize);
+}
+
+// The same for several groups of windows (swk_batch_run_groups): frame f's frame, geometry and record cap from fr[f]
+__global__ __launch_bounds__(256) void k_segment_inputs_groups(const SegFrame *__restrict__ fr, const swk_segment *__restrict__ segs,
+                                                               int seg_stride, const int32_t *__restrict__ offsets, int F, int min_h,
+                                                               int min_w, int first, int count, float *__restrict__ net,
+                                                               int32_t *__restrict__ seg_frame, int pad, int nhwc, float m0, float m1,
+                                                               float m2, float s0, float s1, float s2, int32_t *__restrict__ oversize)
+{
+    __shared__ ResizeLds L;
+    __shared__ int s_box[5];
+    const int k = first + blockIdx.x;
+    if ((int)blockIdx.x >= count || k >= offsets[F]) return;
+    if (threadIdx.x == 0) {
+        int lo = 0, hi = F;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (offsets[mid] <= k) lo = mid; else hi = mid;
         }
-        return;
+        const SegFrame d = fr[lo];
+        segment_box(segs[(int64_t)lo * seg_stride + (k - offsets[lo])], min_h, min_w, d.x0, d.y0, d.frame_h, d.frame_w, lo, s_box);
     }
-    resize_and_emit(L, frames + (int64_t)f * frame_stride + (int64_t)r0 * row_stride + (int64_t)c0 * 3, row_stride, h, w,
-                    nullptr, o, pad, nhwc, mean, sd);
+    __syncthreads();
+    const SegFrame d = fr[s_box[0]];
+    emit_segment(L, d.frame, d.rs, s_box, net, seg_frame, pad, nhwc, m0, m1, m2, s0, s1, s2, oversize);
+}
+
+__global__ __launch_bounds__(256) void k_segment_prefix_groups(const int32_t *__restrict__ nseg, const SegFrame *__restrict__ fr, int F,
+                                                               int32_t *__restrict__ offsets)
+{
+    // k_segment_prefix with frame f's own cap
+    __shared__ int s_part[256];
+    const int tid = threadIdx.x;
+    const int per = (F + 255) / 256;
+    const int lo = tid * per, hi = lo + per < F ? lo + per : F;
+    int sum = 0;
+    for (int f = lo; f < hi; ++f) sum += nseg[f] < fr[f].cap ? nseg[f] : fr[f].cap;
+    s_part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int i = 0; i < 256; ++i) { const int v = s_part[i]; s_part[i] = run; run += v; }
+        offsets[F] = run;
+    }
+    __syncthreads();
+    int run = s_part[tid];
+    for (int f = lo; f < hi; ++f) { offsets[f] = run; run += nseg[f] < fr[f].cap ? nseg[f] : fr[f].cap; }
 }
 
 void launch_classifier_input(hipStream_t s, const uint8_t *crops, const int64_t *offsets, const int32_t *hw, int nseg,
@@ -237,6 +300,20 @@ void launch_segment_inputs(hipStream_t s, const uint8_t *frames, int64_t frame_s
     hipLaunchKernelGGL(k_segment_inputs, dim3(count), dim3(256), 0, s, frames, frame_stride, row_stride, frame_h, frame_w, x0, y0,
                        segs, offsets, F, seg_cap, min_h, min_w, first, count, net, seg_frame, pad, nhwc ? 1 : 0,
                        mean[0], mean[1], mean[2], sd[0], sd[1], sd[2], oversize);
+}
+
+void launch_segment_prefix_groups(hipStream_t s, const int32_t *nseg, const SegFrame *fr, int F, int32_t *offsets)
+{
+    hipLaunchKernelGGL(k_segment_prefix_groups, dim3(1), dim3(256), 0, s, nseg, fr, F, offsets);
+}
+
+void launch_segment_inputs_groups(hipStream_t s, const SegFrame *fr, const swk_segment *segs, int seg_stride, const int32_t *offsets,
+                                  int F, int min_h, int min_w, int first, int count, float *net, int32_t *seg_frame, int pad, bool nhwc,
+                                  const float *mean, const float *sd, int32_t *oversize)
+{
+    if (count < 1) return;
+    hipLaunchKernelGGL(k_segment_inputs_groups, dim3(count), dim3(256), 0, s, fr, segs, seg_stride, offsets, F, min_h, min_w, first, count,
+                       net, seg_frame, pad, nhwc ? 1 : 0, mean[0], mean[1], mean[2], sd[0], sd[1], sd[2], oversize);
 }
 
 }  // namespace swk

@@ -350,12 +350,15 @@ constexpr int kSX = 8;                   // column of the source window = image 
 constexpr int kBH = kTH + 4, kBW = kTW + 4;      // thresholded ring 36 x 68
 constexpr int kEH = kTH + 2, kEW = kTW + 2;      // eroded ring 34 x 66
 
+// GEOM: frame f's H, W and plane offset come from geom[f] (swk_batch_run_groups: the grid is sized by the largest frame, the
+// workgroups beyond a frame's extent leave at once); otherwise every frame is H x W, planes packed densely.
+template <bool GEOM>
 __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict__ src, int H, int W,
                                                       const float *__restrict__ color_w, const float *__restrict__ space_w,
                                                       const int8_t *__restrict__ tdr, const int8_t *__restrict__ tdc,
                                                       int maxk, int use_fma, int thresh,
                                                       uint8_t *__restrict__ bil_out, uint8_t *__restrict__ thr_out,
-                                                      uint8_t *__restrict__ open_out)
+                                                      uint8_t *__restrict__ open_out, const FrameGeom *__restrict__ geom)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_src[kSH * kSP];
     __shared__ uint32_t s_nz[kSH * 3];             // per source row: 80-bit mask of its nonzero pixels
@@ -370,7 +373,12 @@ __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict_
     __shared__ int s_count, s_er_any;
     const int f = blockIdx.z, tid = threadIdx.x;
     const int r0 = blockIdx.y * kTH, c0 = blockIdx.x * kTW;
-    const uint8_t *img = src + (int64_t)f * H * W;
+    int64_t base = (int64_t)f * H * W;
+    if (GEOM) {
+        H = geom[f].H; W = geom[f].W; base = geom[f].off;
+        if (r0 >= H || c0 >= W) return;
+    }
+    const uint8_t *img = src + base;
     if (tid == 0) { s_count = 0; s_er_any = 0; }
     if (tid < kSH * 3) s_nz[tid] = 0u;
     __syncthreads();
@@ -474,9 +482,9 @@ __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict_
         uint8_t outv = (uint8_t)__float2int_rn(sum / wsum);             // cvRound: half to even
         const int r = r0 - 2 + lr, c = c0 - 2 + lc;
         const bool inner = lr >= 2 && lr < kBH - 2 && lc >= 2 && lc < kBW - 2;
-        if (inner && bil_out && outv) bil_out[((int64_t)f * H + r) * W + c] = outv;
+        if (inner && bil_out && outv) bil_out[base + (int64_t)r * W + c] = outv;
         outv = outv > thresh ? outv : (uint8_t)0;
-        if (inner && thr_out && outv) thr_out[((int64_t)f * H + r) * W + c] = outv;
+        if (inner && thr_out && outv) thr_out[base + (int64_t)r * W + c] = outv;
         s_thr[i] = outv;
     }
     __syncthreads();
@@ -513,7 +521,7 @@ __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict_
                 const int v = s_er[(clampi(r + dr, H) - r0 + 1) * kEW + (clampi(c + dc, W) - c0 + 1)];
                 acc = v > acc ? v : acc;
             }
-        if (acc) open_out[((int64_t)f * H + r) * W + c] = (uint8_t)acc;
+        if (acc) open_out[base + (int64_t)r * W + c] = (uint8_t)acc;
     }
 }
 
@@ -530,9 +538,25 @@ void launch_filter_fused(hipStream_t s, const uint8_t *src, int F, int H, int W,
     for (int f0 = 0; f0 < F; f0 += 32768) {
         const int fc = F - f0 < 32768 ? F - f0 : 32768;
         const int64_t o = (int64_t)f0 * H * W;
-        hipLaunchKernelGGL(k_filter_fused, dim3(ntx, nty, fc), dim3(256), 0, s,
+        hipLaunchKernelGGL(k_filter_fused<false>, dim3(ntx, nty, fc), dim3(256), 0, s,
                            src + o, H, W, t.color_w, t.space_w, t.tap_dr, t.tap_dc, t.maxk, use_fma, thresh,
-                           bil_out ? bil_out + o : nullptr, thr_out ? thr_out + o : nullptr, open_out + o);
+                           bil_out ? bil_out + o : nullptr, thr_out ? thr_out + o : nullptr, open_out + o, nullptr);
+    }
+}
+
+void launch_filter_fused_geom(hipStream_t s, const uint8_t *src, int F, int Hmax, int Wmax, const FrameGeom *geom, size_t total,
+                              const BilateralTables &t, int use_fma, int thresh, uint8_t *bil_out, uint8_t *thr_out, uint8_t *open_out)
+{
+    const int ntx = (Wmax + kTW - 1) / kTW, nty = (Hmax + kTH - 1) / kTH;
+    hipError_t me = hipMemsetAsync(open_out, 0, total, s);
+    if (me == hipSuccess && bil_out) me = hipMemsetAsync(bil_out, 0, total, s);
+    if (me == hipSuccess && thr_out) me = hipMemsetAsync(thr_out, 0, total, s);
+    if (me != hipSuccess) { g_launch_error = (int)me; return; }
+    for (int f0 = 0; f0 < F; f0 += 32768) {
+        const int fc = F - f0 < 32768 ? F - f0 : 32768;
+        hipLaunchKernelGGL(k_filter_fused<true>, dim3(ntx, nty, fc), dim3(256), 0, s,
+                           src, 0, 0, t.color_w, t.space_w, t.tap_dr, t.tap_dc, t.maxk, use_fma, thresh,
+                           bil_out, thr_out, open_out, geom + f0);
     }
 }
 

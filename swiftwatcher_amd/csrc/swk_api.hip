@@ -7,6 +7,7 @@
 #include <string.h>
 #include <atomic>
 #include <string>
+#include <algorithm>
 #include <vector>
 
 using namespace swk;
@@ -21,7 +22,7 @@ enum Slot {
     SL_ROI = 0, SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8, SL_LAB32, SL_A, SL_Y, SL_E, SL_PN,
     SL_BM, SL_VPREV, SL_GPART, SL_ZZPART, SL_WIN, SL_ACTIVE, SL_PARENT, SL_ROOTBITS, SL_WORDPREFIX,
     SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_ITERS, SL_TMP_IN, SL_TMP_OUT, SL_COLORW, SL_SPACEW,
-    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_X2, SL_REDO_S2, SL_SEGOFFS, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_COUNT
+    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_X2, SL_REDO_S2, SL_SEGOFFS, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int fam; };
@@ -77,6 +78,7 @@ struct swk_ctx {
         int total = -1;          // segments of the batch (regions beyond cap not counted), when nseg was copied to the host
         const swk_segment *segs = nullptr;
         const int32_t *nseg = nullptr;
+        const SegFrame *fr = nullptr;   // swk_batch_run_groups: per-frame frames and geometry (device table), nwin * n frames
     } last;
 };
 
@@ -218,6 +220,65 @@ int ensure_ccl(swk_ctx *ctx, int F, int H, int W, CclBuffers *b)
     NEED(ctx, SL_NCOMP, (size_t)F * 4, b->ncomp);
     NEED(ctx, SL_TABLE, (size_t)F * 256 * 8 * 4, b->table);
     NEED(ctx, SL_SUMS, (size_t)F * 256 * 2 * 8, b->sums);
+    return SWK_OK;
+}
+
+// ---- host input -> device (swk_batch_run's copy strategies; swk_batch_run_groups stages its host groups the same way) ----
+struct HostStage { int kind; size_t bytes; };
+enum { ST_DENSE = 0, ST_WHOLE, ST_ROWS, ST_2D };
+
+HostStage host_stage_plan(const swk_input *in)
+{
+    const int F = in->nwin * in->n, H = in->Hc, W = in->Wc;
+    const size_t plane = (size_t)F * H * W;
+    const int64_t fs = in->frame_stride, rs = in->row_stride, afs = fs < 0 ? -fs : fs;
+    const int x0 = in->x0, y0 = in->y0;
+    const size_t rowb = (size_t)W * in->channels;
+    if (x0 == 0 && (size_t)rs == rowb && fs == (int64_t)H * rs) return {ST_DENSE, plane * in->channels};
+    if (rs >= (int64_t)(x0 + W) * in->channels && rs % in->channels == 0 && afs % rs == 0 && afs >= (int64_t)(y0 + H) * rs &&
+        (size_t)F * (size_t)afs <= 2 * plane * in->channels) {
+        const size_t whole = (size_t)F * (size_t)afs;
+        return {ST_WHOLE, whole > plane * in->channels ? whole : plane * in->channels};
+    }
+    if (x0 == 0 && (size_t)rs == rowb) return {ST_ROWS, plane * in->channels};
+    return {ST_2D, plane * in->channels};
+}
+
+// Copies `in` to roi and says where the kernels find it there: frame 0 at *dframes, strides *fs / *rs, ROI origin (*x0, *y0).
+int host_stage_copy(swk_ctx *ctx, const swk_input *in, const HostStage &st, uint8_t *roi, const uint8_t **dframes, int64_t *fs_out,
+                    int64_t *rs_out, int *x0_out, int *y0_out)
+{
+    hipStream_t s = ctx->stream;
+    const int F = in->nwin * in->n, H = in->Hc, W = in->Wc, P = H * W;
+    const size_t plane = (size_t)F * P;
+    const int64_t fs = in->frame_stride, rs = in->row_stride, afs = fs < 0 ? -fs : fs;
+    const int x0 = in->x0, y0 = in->y0;
+    const size_t rowb = (size_t)W * in->channels;
+    if (st.kind == ST_DENSE) {
+        // pre-cropped, densely packed ROI frames: one copy for the whole batch
+        HIPCHK(ctx, hipMemcpyAsync(roi, in->frames + (int64_t)y0 * rs, plane * in->channels, hipMemcpyHostToDevice, s));
+    } else if (st.kind == ST_WHOLE) {
+        // ROI frames with a margin around them (FrameQueue stages the crop plus the half minimum segment size, so that
+        // segment boxes can grow into it like they grow into the full frame, image_filtering.py:338-369): the whole
+        // buffer in one copy; the kernels read the ROI at (x0, y0) of the device copy.  A NEGATIVE frame stride (queue
+        // position 0 = the LAST frame in memory: a reader's block in file order) is copied as it lies and read backwards.
+        const uint8_t *lowest = fs < 0 ? in->frames + (int64_t)(F - 1) * fs : in->frames;
+        HIPCHK(ctx, hipMemcpyAsync(roi, lowest, (size_t)F * (size_t)afs, hipMemcpyHostToDevice, s));
+        *dframes = fs < 0 ? roi + (int64_t)(F - 1) * afs : roi;
+        *fs_out = fs; *rs_out = rs; *x0_out = x0; *y0_out = y0;
+        return SWK_OK;
+    } else if (st.kind == ST_ROWS) {
+        for (int f = 0; f < F; ++f)                    // full-width rows: one contiguous block per frame
+            HIPCHK(ctx, hipMemcpyAsync(roi + (size_t)f * P * in->channels, in->frames + (int64_t)f * fs + (int64_t)y0 * rs,
+                                       (size_t)P * in->channels, hipMemcpyHostToDevice, s));
+    } else {
+        for (int f = 0; f < F; ++f)
+            HIPCHK(ctx, hipMemcpy2DAsync(roi + (size_t)f * P * in->channels, rowb,
+                                         in->frames + (int64_t)f * fs + (int64_t)y0 * rs + (int64_t)x0 * in->channels, (size_t)rs,
+                                         rowb, H, hipMemcpyHostToDevice, s));
+    }
+    *dframes = roi;
+    *fs_out = (int64_t)P * in->channels; *rs_out = (int64_t)rowb; *x0_out = 0; *y0_out = 0;
     return SWK_OK;
 }
 
@@ -397,6 +458,8 @@ int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmb
 }
 
 // Iteration counts live in the per-window state structs.  Called once the stream has drained.
+int account_iters(swk_ctx *ctx, const std::vector<IalmWin> &hw, int32_t *h_iters, int32_t *d_iters);
+
 int gather_iters(swk_ctx *ctx, int32_t *h_iters, int32_t *d_iters)
 {
     const int nwin = ctx->last_nwin;
@@ -405,6 +468,13 @@ int gather_iters(swk_ctx *ctx, int32_t *h_iters, int32_t *d_iters)
     //  fails outright while another thread captures a HIP graph on one -- the classifier does, segment_classification.py)
     HIPCHK(ctx, hipMemcpyAsync(hw.data(), ctx->last_win, (size_t)nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return account_iters(ctx, hw, h_iters, d_iters);
+}
+
+// Books the per-window IALM state of a batch (counters, diagnostics) and hands out its iteration counts.
+int account_iters(swk_ctx *ctx, const std::vector<IalmWin> &hw, int32_t *h_iters, int32_t *d_iters)
+{
+    const int nwin = (int)hw.size();
     std::vector<int32_t> it(nwin);
     ctx->last_hw = hw;
     ctx->last_int_start = 0;
@@ -427,7 +497,7 @@ int gather_iters(swk_ctx *ctx, int32_t *h_iters, int32_t *d_iters)
 int segment_inputs_impl(swk_ctx *ctx, const uint8_t *frames, int64_t fs, int64_t rs, int F, int x0, int y0, int frame_h, int frame_w,
                         const swk_segment *segs, const int32_t *nseg, int seg_cap, int min_h, int min_w, const float *mean,
                         const float *std_, int pad, bool nhwc, int first, int net_cap, float *net, int32_t *seg_frame, int32_t *total,
-                        int32_t *skipped, int known_total = -1)
+                        int32_t *skipped, int known_total = -1, const SegFrame *fr = nullptr)
 {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -435,7 +505,8 @@ int segment_inputs_impl(swk_ctx *ctx, const uint8_t *frames, int64_t fs, int64_t
     NEED(ctx, SL_SEGOFFS, ((size_t)F + 2) * 4, doffs);           // [F+1] prefix sums, then the skipped-box counter
     int32_t *dskip = doffs + F + 1;
     HIPCHK(ctx, hipMemsetAsync(dskip, 0, 4, s));
-    launch_segment_prefix(s, nseg, F, seg_cap, doffs);
+    if (fr) launch_segment_prefix_groups(s, nseg, fr, F, doffs);          // (seg_cap = the records' stride; caps per frame in fr)
+    else launch_segment_prefix(s, nseg, F, seg_cap, doffs);
     int32_t tot = known_total;
     if (tot < 0) {          // the caller does not know how many segments the batch holds: one round trip
         HIPCHK(ctx, hipMemcpyAsync(&tot, doffs + F, 4, hipMemcpyDeviceToHost, s));
@@ -446,8 +517,11 @@ int segment_inputs_impl(swk_ctx *ctx, const uint8_t *frames, int64_t fs, int64_t
     int count = tot - first;
     if (count > net_cap) count = net_cap;
     if (count < 1) return SWK_OK;
-    launch_segment_inputs(s, frames, fs, rs, frame_h, frame_w, x0, y0, segs, doffs, F, seg_cap,
-                          min_h, min_w, first, count, net, seg_frame, pad, nhwc, mean, std_, dskip);
+    if (fr)
+        launch_segment_inputs_groups(s, fr, segs, seg_cap, doffs, F, min_h, min_w, first, count, net, seg_frame, pad, nhwc, mean, std_, dskip);
+    else
+        launch_segment_inputs(s, frames, fs, rs, frame_h, frame_w, x0, y0, segs, doffs, F, seg_cap,
+                              min_h, min_w, first, count, net, seg_frame, pad, nhwc, mean, std_, dskip);
     int32_t sk = 0;
     HIPCHK(ctx, hipMemcpyAsync(&sk, dskip, 4, hipMemcpyDeviceToHost, s));
     int rc = sync(ctx);
@@ -755,36 +829,11 @@ int32_t swk_batch_run(swk_ctx *ctx, const swk_input *in, const swk_params *p, sw
     int x0 = in->x0, y0 = in->y0;
     if (in->mem == SWK_MEM_HOST) {
         uint8_t *roi;
-        NEED(ctx, SL_ROI, plane * in->channels, roi);
+        const HostStage st = host_stage_plan(in);
+        NEED(ctx, SL_ROI, st.bytes, roi);
         Timed t(ctx, SWK_K_COPY);
-        bool whole = false;
-        const int64_t afs = fs < 0 ? -fs : fs;
-        const size_t rowb = (size_t)W * in->channels;
-        if (x0 == 0 && (size_t)rs == rowb && fs == (int64_t)H * rs) {
-            // pre-cropped, densely packed ROI frames: one copy for the whole batch
-            HIPCHK(ctx, hipMemcpyAsync(roi, in->frames + (int64_t)y0 * rs, plane * in->channels, hipMemcpyHostToDevice, s));
-        } else if (rs >= (int64_t)(x0 + W) * in->channels && rs % in->channels == 0 && afs % rs == 0 && afs >= (int64_t)(y0 + H) * rs &&
-                   (size_t)F * (size_t)afs <= 2 * plane * in->channels) {
-            // ROI frames with a margin around them (FrameQueue stages the crop plus the half minimum segment size, so that
-            // segment boxes can grow into it like they grow into the full frame, image_filtering.py:338-369): the whole
-            // buffer in one copy; the kernels read the ROI at (x0, y0) of the device copy.  A NEGATIVE frame stride (queue
-            // position 0 = the LAST frame in memory: a reader's block in file order) is copied as it lies and read backwards.
-            NEED(ctx, SL_ROI, (size_t)F * (size_t)afs, roi);
-            const uint8_t *lowest = fs < 0 ? in->frames + (int64_t)(F - 1) * fs : in->frames;
-            HIPCHK(ctx, hipMemcpyAsync(roi, lowest, (size_t)F * (size_t)afs, hipMemcpyHostToDevice, s));
-            whole = true;
-        } else if (x0 == 0 && (size_t)rs == rowb) {
-            for (int f = 0; f < F; ++f)                    // full-width rows: one contiguous block per frame
-                HIPCHK(ctx, hipMemcpyAsync(roi + (size_t)f * P * in->channels, in->frames + (int64_t)f * fs + (int64_t)y0 * rs,
-                                           (size_t)P * in->channels, hipMemcpyHostToDevice, s));
-        } else {
-            for (int f = 0; f < F; ++f)
-                HIPCHK(ctx, hipMemcpy2DAsync(roi + (size_t)f * P * in->channels, rowb,
-                                             in->frames + (int64_t)f * fs + (int64_t)y0 * rs + (int64_t)x0 * in->channels, (size_t)rs,
-                                             rowb, H, hipMemcpyHostToDevice, s));
-        }
-        dframes = (whole && fs < 0) ? roi + (int64_t)(F - 1) * afs : roi;
-        if (!whole) { fs = (int64_t)P * in->channels; rs = (int64_t)rowb; x0 = 0; y0 = 0; }
+        rc = host_stage_copy(ctx, in, st, roi, &dframes, &fs, &rs, &x0, &y0);
+        if (rc) return rc;
     }
     // ---- stage buffers (caller's device buffers are written in place) ----
     uint8_t *dX, *dS, *dBil = nullptr, *dThr = nullptr, *dOpen, *dLab;
@@ -866,6 +915,7 @@ int32_t swk_batch_run(swk_ctx *ctx, const swk_input *in, const swk_params *p, sw
         lb.nwin = in->nwin; lb.n = in->n; lb.Hc = H; lb.Wc = W; lb.x0 = x0; lb.y0 = y0;
         lb.frame_h = (int)((fs < 0 ? -fs : fs) / rs); lb.frame_w = (int)(rs / 3);
         lb.segs = dsegs; lb.nseg = dnseg; lb.cap = cap;
+        lb.fr = nullptr;
         lb.total = -1;
         if (!dev_out && out->nseg) {
             lb.total = 0;
@@ -874,6 +924,334 @@ int32_t swk_batch_run(swk_ctx *ctx, const swk_input *in, const swk_params *p, sw
         lb.valid = true;
     }
     return gather_iters(ctx, dev_out ? nullptr : out->iters, dev_out ? out->iters : nullptr);
+}
+
+// -------------------------------------------------------------------------------------
+// Several groups of windows (one video's windows each, every one with its own geometry and memory) in ONE call.
+// Stage planes: every frame's u8 planes start at a per-frame offset and hold its own H x W pixels.  The IALM runs once over all
+// groups whose ROI has at least n pixels, on X planes zero-padded to the largest of those ROIs (Pmax): zero pixel rows change
+// neither X^T X nor ||X||_F nor max|X|, and their rows of A, E, Y and S stay zero.  A group with fewer pixels than frames runs as a
+// sub-batch of its own at its true P (there svp = min(P, n), image_filtering.py:285, so padding would change the result).
+int32_t swk_batch_run_groups(swk_ctx *ctx, const swk_input *groups, int32_t ngroups, const swk_params *p, swk_output *outs)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!groups || !p || !outs || ngroups < 1) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (p->open_kh != 3 || p->open_kw != 3) return fail(ctx, SWK_ERR_ARG, "only the (3,3) opening window is implemented");
+    if (p->connectivity != 4 && p->connectivity != 8) return fail(ctx, SWK_ERR_ARG, "connectivity must be 4 or 8");
+    if (p->bil_d / 2 != 3) return fail(ctx, SWK_ERR_ARG, "the fused filter kernel implements bilateral d=7 (radius 3) only");
+    const int G = ngroups, n = groups[0].n;
+    int64_t nwin64 = 0;
+    for (int g = 0; g < G; ++g) {
+        const swk_input *in = &groups[g];
+        const swk_output *out = &outs[g];
+        if (!in->frames) return fail(ctx, SWK_ERR_ARG, "null frames in a group");
+        if (in->nwin < 1 || in->n < 1 || in->Hc < 1 || in->Wc < 1) return fail(ctx, SWK_ERR_ARG, "empty group");
+        if (in->n != n) return fail(ctx, SWK_ERR_ARG, "every group must have the same frames per window");
+        if (in->channels != 1 && in->channels != 3) return fail(ctx, SWK_ERR_ARG, "channels must be 1 or 3");
+        if (in->n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be <= 128");
+        if (out->segs && (out->seg_cap < 1 || out->seg_cap > 255)) return fail(ctx, SWK_ERR_ARG, "seg_cap must be in 1..255");
+        if (in->Hc < 4 || in->Wc < 4) return fail(ctx, SWK_ERR_ARG, "ROI must be at least 4x4");
+        nwin64 += in->nwin;
+    }
+    if (nwin64 * n > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "too many frames in one call");
+    const int nwin = (int)nwin64, F = nwin * n;
+
+    // ---- sub-batches of the IALM: [0] = every group with P >= n, padded to its largest P; then one per group with P < n ----
+    struct Sub { std::vector<int> gs; int P = 0, nwin = 0; int64_t off = 0; bool A = false, E = false; };
+    std::vector<Sub> subs(1);
+    std::vector<int> sub_of(G);
+    for (int g = 0; g < G; ++g) {
+        const int P = groups[g].Hc * groups[g].Wc;
+        Sub *sb;
+        if (P >= n) { sb = &subs[0]; sub_of[g] = 0; }
+        else { subs.emplace_back(); sb = &subs.back(); sub_of[g] = (int)subs.size() - 1; }
+        sb->gs.push_back(g);
+        sb->P = P > sb->P ? P : sb->P;
+        sb->nwin += groups[g].nwin;
+        sb->A = sb->A || outs[g].A; sb->E = sb->E || outs[g].E;
+    }
+    if (subs[0].gs.empty()) subs.erase(subs.begin());
+    for (int g = 0; g < G; ++g) sub_of[g] = 0;
+    for (size_t k = 0; k < subs.size(); ++k)
+        for (int g : subs[k].gs) sub_of[g] = (int)k;
+    int Pmax = 0, Hmax = 0, Wmax = 0;
+    for (int g = 0; g < G; ++g) {
+        Hmax = groups[g].Hc > Hmax ? groups[g].Hc : Hmax;
+        Wmax = groups[g].Wc > Wmax ? groups[g].Wc : Wmax;
+    }
+    // capacity: run_ialm's limit on the padded plane, checked here so that a refused call launches nothing
+    const int fpad_max = std::max(ialm_mstate_fpad(n), (n + 15) & ~15);
+    size_t total = 0;                     // stage-plane bytes: sub-batches one after the other, each 256-byte aligned
+    for (Sub &sb : subs) {
+        Pmax = sb.P > Pmax ? sb.P : Pmax;
+        if ((int64_t)fpad_max * (((int64_t)sb.P + 127) & ~(int64_t)127) >= (1ll << 28))
+            return fail(ctx, SWK_ERR_ARG, "window too large: frames x padded ROI pixels must stay below 2^28");
+        sb.off = (int64_t)total;
+        total += ((size_t)sb.nwin * n * sb.P + 255) & ~(size_t)255;
+    }
+    // region records: one stride for the call (the largest cap), each group's own cap where it counts
+    bool want_props = false, seg_last = true, host_total = true;
+    int capmax = 1;
+    for (int g = 0; g < G; ++g) {
+        want_props = want_props || outs[g].segs || outs[g].nseg;
+        if (outs[g].segs && outs[g].seg_cap > capmax) capmax = outs[g].seg_cap;
+        seg_last = seg_last && outs[g].segs && groups[g].channels == 3;
+        host_total = host_total && outs[g].mem == SWK_MEM_HOST && outs[g].nseg;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int rc;
+    ctx->last.valid = false;
+
+    // ---- every buffer first (a later NEED may not move one a queued kernel uses) ----
+    std::vector<HostStage> st(G);
+    std::vector<size_t> roi_off(G, 0);
+    size_t roi_bytes = 0;
+    for (int g = 0; g < G; ++g)
+        if (groups[g].mem == SWK_MEM_HOST) {
+            st[g] = host_stage_plan(&groups[g]);
+            roi_off[g] = roi_bytes;
+            roi_bytes += (st[g].bytes + 255) & ~(size_t)255;
+        }
+    bool any_bil = false, any_thr = false;
+    size_t pn_bytes = 0;
+    std::vector<size_t> pn_off(G, 0);
+    for (int g = 0; g < G; ++g) {
+        any_bil = any_bil || outs[g].bilateral;
+        any_thr = any_thr || outs[g].thresh;
+        if ((outs[g].A || outs[g].E) && outs[g].mem == SWK_MEM_HOST) {
+            pn_off[g] = pn_bytes;
+            pn_bytes += (size_t)groups[g].nwin * n * groups[g].Hc * groups[g].Wc * 8;
+        }
+    }
+    uint8_t *roi = nullptr, *dX, *dS, *dBil = nullptr, *dThr = nullptr, *dOpen, *dLab;
+    if (roi_bytes) NEED(ctx, SL_ROI, roi_bytes, roi);
+    NEED(ctx, SL_X, total + 4, dX);
+    NEED(ctx, SL_S, total, dS);
+    if (any_bil) NEED(ctx, SL_BIL, total, dBil);
+    if (any_thr) NEED(ctx, SL_THR, total, dThr);
+    NEED(ctx, SL_OPEN, total, dOpen);
+    NEED(ctx, SL_LAB8, total, dLab);
+    double *pn = nullptr;
+    if (pn_bytes) NEED(ctx, SL_PN, pn_bytes, pn);
+    swk_segment *dsegs = nullptr; int32_t *dnseg = nullptr;
+    if (want_props) {
+        NEED(ctx, SL_SEGS, (size_t)F * capmax * sizeof(swk_segment), dsegs);
+        NEED(ctx, SL_NSEG, (size_t)F * 4, dnseg);
+    }
+    // labelling: the one-workgroup-per-frame kernel for every group that fits it, the multi-kernel path (a dense copy of the
+    // group's planes) for the others
+    size_t lds = 0, Pp = 1, ccl_F = 1, ccl_Pp = 1, ccl_words_ = 1, tmp_bytes = 16;
+    std::vector<char> fused(G);
+    for (int g = 0; g < G; ++g) {
+        const int H = groups[g].Hc, W = groups[g].Wc, Fg = groups[g].nwin * n;
+        fused[g] = ccl_frame_supported(H, W);
+        Pp = std::max(Pp, ccl_padded(H, W));
+        if (fused[g]) lds = std::max(lds, ccl_frame_lds_bytes(H, W));
+        else {
+            ccl_F = std::max(ccl_F, (size_t)Fg);
+            ccl_Pp = std::max(ccl_Pp, ccl_padded(H, W));
+            ccl_words_ = std::max(ccl_words_, ccl_words(H, W));
+            tmp_bytes = std::max(tmp_bytes, (size_t)Fg * H * W);
+        }
+    }
+    CclBuffers cb{};
+    NEED(ctx, SL_PARENT, std::max((size_t)F * Pp, ccl_F * ccl_Pp) * 4, cb.parent);
+    NEED(ctx, SL_ROOTBITS, ccl_F * ccl_words_ * 4, cb.rootbits);
+    NEED(ctx, SL_WORDPREFIX, ccl_F * ccl_words_ * 4, cb.wordprefix);
+    NEED(ctx, SL_NCOMP, (size_t)F * 4, cb.ncomp);
+    NEED(ctx, SL_TABLE, ccl_F * 256 * 8 * 4, cb.table);
+    NEED(ctx, SL_SUMS, ccl_F * 256 * 2 * 8, cb.sums);
+    uint8_t *tmp_in = nullptr, *tmp_out = nullptr;
+    if (tmp_bytes > 16) { NEED(ctx, SL_TMP_IN, tmp_bytes, tmp_in); NEED(ctx, SL_TMP_OUT, tmp_bytes, tmp_out); }
+    // descriptor tables, one upload: windows (gather), frames (filter), frames (labelling), frames (classifier inputs),
+    // windows in sub-batch order (A, then E)
+    const size_t o_win = 0, o_gf = o_win + (((size_t)nwin * sizeof(GroupWin) + 15) & ~(size_t)15);
+    const size_t o_gc = o_gf + (size_t)F * sizeof(FrameGeom), o_sf = o_gc + (size_t)F * sizeof(FrameGeom);
+    const size_t o_pa = o_sf + (size_t)F * sizeof(SegFrame), o_pe = o_pa + (size_t)nwin * sizeof(PnWin);
+    const size_t tab_bytes = o_pe + (size_t)nwin * sizeof(PnWin);
+    uint8_t *dtab;
+    NEED(ctx, SL_GRP, tab_bytes, dtab);
+    rc = ensure_bilateral(ctx, p->bil_d, p->bil_sigma_color, p->bil_sigma_space);
+    if (rc) return rc;
+
+    // ---- inputs: host groups staged one after the other into the ROI buffer ----
+    struct View { const uint8_t *frames; int64_t fs, rs; int x0, y0; };
+    std::vector<View> view(G);
+    for (int g = 0; g < G; ++g) {
+        const swk_input *in = &groups[g];
+        View &v = view[g];
+        v = {in->frames, in->frame_stride, in->row_stride, in->x0, in->y0};
+        if (in->mem == SWK_MEM_HOST) {
+            Timed t(ctx, SWK_K_COPY);
+            rc = host_stage_copy(ctx, in, st[g], roi + roi_off[g], &v.frames, &v.fs, &v.rs, &v.x0, &v.y0);
+            if (rc) return rc;
+        }
+    }
+    std::vector<uint8_t> tab(tab_bytes, 0);
+    GroupWin *hwin = (GroupWin *)(tab.data() + o_win);
+    FrameGeom *hgf = (FrameGeom *)(tab.data() + o_gf), *hgc = (FrameGeom *)(tab.data() + o_gc);
+    SegFrame *hsf = (SegFrame *)(tab.data() + o_sf);
+    PnWin *hpa = (PnWin *)(tab.data() + o_pa), *hpe = (PnWin *)(tab.data() + o_pe);
+    std::vector<int> win0(G + 1, 0);           // first window of each group (call order)
+    std::vector<int64_t> goff(G);              // stage-plane offset of each group's first frame
+    std::vector<int> sbwin(G);                 // first window of each group inside its sub-batch
+    {
+        std::vector<int> fill(subs.size(), 0);
+        for (int g = 0; g < G; ++g) {
+            win0[g + 1] = win0[g] + groups[g].nwin;
+            const Sub &sb = subs[sub_of[g]];
+            sbwin[g] = fill[sub_of[g]];
+            fill[sub_of[g]] += groups[g].nwin;
+            goff[g] = sb.off + (int64_t)sbwin[g] * n * sb.P;
+        }
+    }
+    int vec = 4;
+    int sub_first = 0;
+    std::vector<int> sub_win0(subs.size());
+    for (size_t k = 0; k < subs.size(); ++k) { sub_win0[k] = sub_first; sub_first += subs[k].nwin; }
+    for (int g = 0; g < G; ++g) {
+        const swk_input *in = &groups[g];
+        const View &v = view[g];
+        const int H = in->Hc, W = in->Wc, P = H * W, pitch = subs[sub_of[g]].P;
+        if (P % 4 || pitch % 4 || goff[g] % 4) vec = std::min(vec, (P % 2 || pitch % 2 || goff[g] % 2) ? 1 : 2);
+        for (int wl = 0; wl < in->nwin; ++wl) {
+            const int w = win0[g] + wl;
+            GroupWin &d = hwin[w];
+            d.src = v.frames + (int64_t)wl * n * v.fs;
+            d.fs = v.fs; d.rs = v.rs; d.off = goff[g] + (int64_t)wl * n * pitch;
+            d.x0 = v.x0; d.y0 = v.y0; d.H = H; d.W = W; d.channels = in->channels; d.pitch = pitch;
+            const int ws = sub_win0[sub_of[g]] + sbwin[g] + wl;          // the window's place in sub-batch order
+            const bool host = outs[g].mem == SWK_MEM_HOST;
+            const size_t wb = (size_t)wl * n * P;
+            hpa[ws].P = hpe[ws].P = P;
+            if (outs[g].A) hpa[ws].dst = host ? pn + pn_off[g] / 8 + wb : outs[g].A + wb;
+            if (outs[g].E) hpe[ws].dst = host ? pn + pn_off[g] / 8 + wb : outs[g].E + wb;
+            for (int j = 0; j < n; ++j) {
+                const int f = w * n + j;
+                hgf[f] = {H, W, d.off + (int64_t)j * pitch};
+                hgc[f] = fused[g] ? hgf[f] : FrameGeom{0, 0, 0};
+                hsf[f].frame = v.frames + ((int64_t)wl * n + j) * v.fs;
+                hsf[f].rs = v.rs;
+                hsf[f].frame_h = (int)((v.fs < 0 ? -v.fs : v.fs) / v.rs);
+                hsf[f].frame_w = (int)(v.rs / 3);
+                hsf[f].x0 = v.x0; hsf[f].y0 = v.y0;
+                hsf[f].cap = outs[g].segs ? outs[g].seg_cap : 1;
+            }
+        }
+    }
+    const GroupWin *dwin = (const GroupWin *)(dtab + o_win);
+    const FrameGeom *dgf = (const FrameGeom *)(dtab + o_gf), *dgc = (const FrameGeom *)(dtab + o_gc);
+    const PnWin *dpa = (const PnWin *)(dtab + o_pa), *dpe = (const PnWin *)(dtab + o_pe);
+    HIPCHK(ctx, hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, s));
+
+    // ---- gray + ROI gather into the padded X planes ----
+    { Timed t(ctx, SWK_K_GRAY); launch_gray_groups(s, dwin, F, n, Pmax, p->gray_mode, dX); }
+
+    // ---- IALM per sub-batch; its float64 factors leave before the next sub-batch reuses the workspaces ----
+    std::vector<IalmWin> hw_sub(nwin);          // sub-batch order
+    for (size_t k = 0; k < subs.size(); ++k) {
+        const Sub &sb = subs[k];
+        rc = run_ialm(ctx, dX + sb.off, sb.nwin, n, sb.P, p->lmbda, p->tol, p->maxiter, sb.A, sb.E, dS + sb.off, nullptr, nullptr);
+        if (rc) return rc;
+        for (int which = 0; which < 2; ++which) {
+            if (!(which == 0 ? sb.A : sb.E)) continue;
+            const double *planes = (const double *)ctx->slot[which == 0 ? SL_A : SL_E];
+            { Timed t(ctx, SWK_K_COPY);
+              launch_planes_to_pn_groups(s, planes, (which == 0 ? dpa : dpe) + sub_win0[k], sb.nwin, n, sb.P, ctx->pstride, ctx->fpad); }
+            for (int g : sb.gs) {
+                double *dst = which == 0 ? outs[g].A : outs[g].E;
+                if (dst && outs[g].mem == SWK_MEM_HOST) {
+                    rc = copy_out(ctx, dst, pn + pn_off[g] / 8, (size_t)groups[g].nwin * n * groups[g].Hc * groups[g].Wc * 8, SWK_MEM_HOST);
+                    if (rc) return rc;
+                }
+            }
+        }
+        HIPCHK(ctx, hipMemcpyAsync(hw_sub.data() + sub_win0[k], ctx->last_win, (size_t)sb.nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+
+    // ---- bilateral + threshold + opening, every frame at its own geometry ----
+    { Timed t(ctx, SWK_K_FILTER);
+      launch_filter_fused_geom(s, dS, F, Hmax, Wmax, dgf, total, ctx->bil, p->bil_fma, p->thresh, dBil, dThr, dOpen); }
+
+    // ---- labels + region properties ----
+    if (want_props) HIPCHK(ctx, hipMemsetAsync(dsegs, 0, (size_t)F * capmax * sizeof(swk_segment), s));
+    if (lds) {
+        Timed t(ctx, SWK_K_CCL);
+        cb.Pp = (int)Pp;
+        launch_ccl_frame_geom(s, dOpen, F, dgc, lds, vec, p->connectivity, p->label_order, cb, dLab, want_props ? capmax : 1,
+                              want_props ? dsegs : nullptr, want_props ? dnseg : nullptr);
+    }
+    for (int g = 0; g < G; ++g) {
+        if (fused[g]) continue;
+        const int H = groups[g].Hc, W = groups[g].Wc, P = H * W, Fg = groups[g].nwin * n, pitch = subs[sub_of[g]].P;
+        const int f0 = win0[g] * n;
+        CclBuffers gb = cb;
+        gb.Pp = (int)ccl_padded(H, W);
+        gb.words = (int)ccl_words(H, W);
+        gb.ncomp = cb.ncomp + f0;
+        HIPCHK(ctx, hipMemcpy2DAsync(tmp_in, P, dOpen + goff[g], pitch, P, Fg, hipMemcpyDeviceToDevice, s));
+        { Timed t(ctx, SWK_K_CCL); launch_ccl(s, tmp_in, Fg, H, W, p->connectivity, p->label_order, gb, nullptr, tmp_out); }
+        if (want_props) {
+            Timed t(ctx, SWK_K_PROPS);
+            launch_regionprops(s, tmp_out, Fg, H, W, gb, capmax, dsegs + (size_t)f0 * capmax, dnseg + f0);
+        }
+        HIPCHK(ctx, hipMemcpy2DAsync(dLab + goff[g], pitch, tmp_out, P, P, Fg, hipMemcpyDeviceToDevice, s));
+    }
+
+    // ---- outputs, group by group, in swk_batch_run's layouts ----
+    {
+        Timed t(ctx, SWK_K_COPY);
+        for (int g = 0; g < G; ++g) {
+            const swk_output *out = &outs[g];
+            const int P = groups[g].Hc * groups[g].Wc, Fg = groups[g].nwin * n, pitch = subs[sub_of[g]].P;
+            const int f0 = win0[g] * n;
+            const bool dev_planes = out->mem == SWK_MEM_DEVICE || out->planes_on_device != 0;
+            const hipMemcpyKind pk = dev_planes ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+            const hipMemcpyKind ok = out->mem == SWK_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+            uint8_t *const dst[6] = {out->gray, out->rpca, out->bilateral, out->thresh, out->opened, out->labels};
+            const uint8_t *const src[6] = {dX, dS, dBil, dThr, dOpen, dLab};
+            for (int i = 0; i < 6; ++i)
+                if (dst[i]) HIPCHK(ctx, hipMemcpy2DAsync(dst[i], P, src[i] + goff[g], pitch, P, Fg, pk, s));
+            if (out->segs)
+                HIPCHK(ctx, hipMemcpy2DAsync(out->segs, (size_t)out->seg_cap * sizeof(swk_segment), dsegs + (size_t)f0 * capmax,
+                                             (size_t)capmax * sizeof(swk_segment), (size_t)out->seg_cap * sizeof(swk_segment), Fg, ok, s));
+            if (out->nseg) HIPCHK(ctx, hipMemcpyAsync(out->nseg, dnseg + f0, (size_t)Fg * 4, ok, s));
+        }
+    }
+    rc = sync(ctx);
+    if (rc) return rc;
+
+    // ---- iteration counts (sub-batch order -> call order) and the record segment_inputs_last reads ----
+    std::vector<IalmWin> hw(nwin);
+    for (int g = 0; g < G; ++g)
+        for (int wl = 0; wl < groups[g].nwin; ++wl) hw[win0[g] + wl] = hw_sub[sub_win0[sub_of[g]] + sbwin[g] + wl];
+    std::vector<int32_t> it(nwin);
+    rc = account_iters(ctx, hw, it.data(), nullptr);
+    if (rc) return rc;
+    for (int g = 0; g < G; ++g) {
+        if (!outs[g].iters) continue;
+        if (outs[g].mem == SWK_MEM_DEVICE)
+            HIPCHK(ctx, hipMemcpyAsync(outs[g].iters, it.data() + win0[g], (size_t)groups[g].nwin * 4, hipMemcpyHostToDevice, s));
+        else memcpy(outs[g].iters, it.data() + win0[g], (size_t)groups[g].nwin * 4);
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));          // `it` is a local
+    if (seg_last && want_props) {
+        swk_ctx::LastBatch &lb = ctx->last;
+        lb.frames = nullptr; lb.fs = lb.rs = 0;
+        lb.nwin = nwin; lb.n = n; lb.Hc = lb.Wc = lb.x0 = lb.y0 = lb.frame_h = lb.frame_w = 0;
+        lb.segs = dsegs; lb.nseg = dnseg; lb.cap = capmax;
+        lb.fr = (const SegFrame *)(dtab + o_sf);
+        lb.total = -1;
+        if (host_total) {
+            lb.total = 0;
+            for (int g = 0; g < G; ++g)
+                for (int f = 0; f < groups[g].nwin * n; ++f) lb.total += std::min(outs[g].nseg[f], outs[g].seg_cap);
+        }
+        lb.valid = true;
+    }
+    return SWK_OK;
 }
 
 // ---- stage-level entry points (host buffers) ----------------------------------------
@@ -1136,7 +1514,7 @@ int32_t swk_segment_inputs_last(swk_ctx *ctx, int32_t min_h, int32_t min_w, cons
     const int known = *total >= 0 && lb.total >= 0 ? lb.total : -1;          // the batch's own count, when its nseg went to the host
     if (known >= 0 && *total != known) return fail(ctx, SWK_ERR_ARG, "*total does not match the batch");
     return segment_inputs_impl(ctx, lb.frames, lb.fs, lb.rs, lb.nwin * lb.n, lb.x0, lb.y0, lb.frame_h, lb.frame_w, lb.segs, lb.nseg, lb.cap,
-                               min_h, min_w, mean, std_, pad, channels_last != 0, first, net_cap, net, seg_frame, total, skipped, known);
+                               min_h, min_w, mean, std_, pad, channels_last != 0, first, net_cap, net, seg_frame, total, skipped, known, lb.fr);
 }
 
 int32_t swk_classifier_input(swk_ctx *ctx, const uint8_t *crops, int64_t crops_bytes, const int64_t *offsets,

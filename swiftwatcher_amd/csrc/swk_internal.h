@@ -189,6 +189,39 @@ size_t ccl_words(int H, int W);
 size_t ccl_padded(int H, int W);
 
 
+// ---- several groups of windows in one call (swk_batch_run_groups) ---------------------------------------
+// A group's windows keep their own geometry; the image stages address every frame through a descriptor, and the IALM
+// runs over planes zero-padded to the batch's largest ROI (groups.hip, DESIGN section "Several videos in one call").
+// Gather source of one window: queue position j is the frame at src + j * fs, its ROI pixel (r, c) at
+// + (y0 + r) * rs + (x0 + c) * channels; frame j's X plane starts at off + j * pitch, pixels p >= H * W of it are zero.
+struct GroupWin {
+    const uint8_t *src;
+    int64_t fs, rs, off;
+    int x0, y0, H, W, channels, pitch;
+};
+// Geometry of one frame's u8 stage planes: H x W dense pixels starting at element `off` (H = 0: the kernel skips the frame)
+struct FrameGeom { int H, W; int64_t off; };
+// Classifier-input cut of one frame: its device BGR frame, row stride, frame size, ROI origin, and its region-record cap
+struct SegFrame { const uint8_t *frame; int64_t rs; int frame_h, frame_w, x0, y0, cap, pad_; };
+// (pixels, frames) scatter of one window: P pixels written to dst (null: not wanted)
+struct PnWin { double *dst; int P, pad_; };
+
+void launch_gray_groups(hipStream_t s, const GroupWin *wins, int F, int n, int Pmax, int gray_mode, uint8_t *X);
+void launch_planes_to_pn_groups(hipStream_t s, const double *planes, const PnWin *wins, int nwin, int n, int Pmax, int64_t pstride,
+                                int fpad);
+// fused filter with per-frame geometry; grid sized by the largest frame; outputs [total] pre-cleared here
+void launch_filter_fused_geom(hipStream_t s, const uint8_t *src, int F, int Hmax, int Wmax, const FrameGeom *geom, size_t total,
+                              const BilateralTables &t, int use_fma, int thresh, uint8_t *bil_out, uint8_t *thr_out, uint8_t *open_out);
+// one-workgroup-per-frame labelling + region properties with per-frame geometry (frames with H = 0 are skipped);
+// lds = the largest ccl_frame_lds_bytes of the frames, vec = word width every frame's size and offset allow (4, 2, 1)
+size_t ccl_frame_lds_bytes(int H, int W);
+void launch_ccl_frame_geom(hipStream_t s, const uint8_t *src, int F, const FrameGeom *geom, size_t lds, int vec, int connectivity,
+                           int order, const CclBuffers &b, uint8_t *labels8, int seg_cap, swk_segment *segs, int32_t *nseg);
+void launch_segment_prefix_groups(hipStream_t s, const int32_t *nseg, const SegFrame *fr, int F, int32_t *offsets);
+void launch_segment_inputs_groups(hipStream_t s, const SegFrame *fr, const swk_segment *segs, int seg_stride, const int32_t *offsets,
+                                  int F, int min_h, int min_w, int first, int count, float *net, int32_t *seg_frame, int pad, bool nhwc,
+                                  const float *mean, const float *sd, int32_t *oversize);
+
 // expand1x1 of the Fire shapes with float32 products formed from split bf16 operands (cnn_expand_bf16.hip); SWK_ERR_ARG for other shapes
 int launch_expand1x1_split_bf16(hipStream_t s, const float *src, int64_t rows, int sh, int sw, int cin, int crop_y, int crop_x, int h, int w,
                                 const float *wgt, const float *bias, int cout, float *dst, int dH, int dW, int dC, int off_y, int off_x, int c_off);

@@ -57,10 +57,11 @@ def _window_crops(frames, nseg, live, min_seg_size, crop_region):
     return buf, offsets.tolist(), np.maximum(boxes[:, 1] - boxes[:, 0], 0).tolist(), np.maximum(boxes[:, 3] - boxes[:, 2], 0).tolist()
 
 
-def window_segments(segs, nseg, slots, min_seg_size, crop_region, batch=None):
+def window_segments(segs, nseg, slots, min_seg_size, crop_region, batch=None, first=0):
     """Segment objects of a whole batch_run at once: slots = the Frame objects in the batch's frame order; segs / nseg = its
     region records.  The same attributes Segment.__init__ sets (label, bbox, centroid = sum / area in float64, area), made
-    from whole-batch arrays instead of one record at a time; segment images are cut when first read."""
+    from whole-batch arrays instead of one record at a time; segment images are cut when first read.  first: the batch index of
+    the first of these segments."""
     F, cap = segs.shape
     live = segs[np.arange(cap)[None, :] < nseg[:, None]]              # frame order, ascending label
     area = live["area"]
@@ -68,7 +69,7 @@ def window_segments(segs, nseg, slots, min_seg_size, crop_region, batch=None):
     rows = zip(live["label"].tolist(), live["r0"].tolist(), live["c0"].tolist(), live["r1"].tolist(), live["c1"].tolist(),
                (live["sum_r"].astype(np.float64) / fa).tolist(), (live["sum_c"].astype(np.float64) / fa).tolist(), area.tolist())
     new = Segment.__new__
-    k = 0
+    k = first                    # index of the first segment in `batch` (a groups call numbers all its groups' segments in one run)
     crops = None
     if len(slots) and hasattr(slots[0].frame, "roi"):
         buf, offs, hs, ws = _window_crops([s.frame for s in slots], nseg, live, min_seg_size, crop_region)
@@ -518,4 +519,62 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
             slots[pos[w] * n + (n - 1 - k)] = fr
         out.append(popped)
     window_segments(res["segs"], nseg, slots, tuple(min_seg_size), crop_region, batch)
+    return out
+
+
+def _group_staging(ctx, slot, shape):
+    """Page-locked staging array of group `slot` of a groups call (ctx.staging keeps one array per shape and thread: the groups of
+    one call need one each)."""
+    key = (slot, tuple(shape))
+    with ctx._lock:
+        cache = ctx.__dict__.setdefault("_group_staging", {})
+        arr = cache.get(key)
+        if arr is None:
+            for old in [k for k in cache if k[0] == slot]:
+                del cache[old]
+            arr = cache[key] = _lib.pinned_empty(shape, np.uint8, device=ctx.device)
+    return arr
+
+
+def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, classifier=None):
+    """segment_windows for several videos in ONE library call (swk_batch_run_groups).  groups: list of (windows, crop_region), windows
+    as segment_windows takes them; every window of every group has the same length n, the crop regions differ.  Returns, per group,
+    what segment_windows(windows, crop_region, ...) returns.  The classifier's scoring of all groups' segments starts once, over the
+    whole call: its head is batch-independent, so every score equals the one of a per-group batch."""
+    groups = [(list(w), cr) for w, cr in groups]
+    live = [i for i, (w, _) in enumerate(groups) if w]
+    if not live:
+        return [[] for _ in groups]
+    n = len(groups[live[0]][0][0][0])
+    ctx = _lib.default_context(device)
+    specs = []
+    for slot, i in enumerate(live):
+        windows, crop_region = groups[i]
+        for frames, _, _ in windows:
+            if len(frames) != n:
+                raise ValueError("every window of every group needs the same number of frames")
+        ordered = [fr for frames, _, _ in windows for fr in frames[::-1]]          # queue index 0 = newest (:134)
+        stack, (rx, ry), (Hc, Wc), backwards = stack_frames(ordered, crop_region, min_seg_size,
+                                                            lambda shape, s=slot: _group_staging(ctx, s, shape))
+        specs.append(dict(frames=stack, nwin=len(windows), n=n, crop=(rx, ry, Wc, Hc), reverse_frames=backwards))
+    results = ctx.batch_run_groups(specs, params=params, stages=())
+    for r in results:
+        if np.any(r["nseg"] > r["segs"].shape[1]):
+            raise _lib.SwkError("more regions in a frame than seg_cap")
+    total = sum(int(np.minimum(r["nseg"], r["segs"].shape[1]).sum()) for r in results)
+    bgr = all(spec["frames"].ndim == 4 for spec in specs)
+    batch = WindowBatch(ctx, results[0]["generation"], total, min_seg_size) if bgr else None
+    if batch is not None and classifier is not None:
+        batch.launch(classifier)
+    out = [[] for _ in groups]
+    first = 0
+    for i, res in zip(live, results):
+        windows, crop_region = groups[i]
+        slots = []
+        for frames, numbers, stamps in windows:
+            popped = [Frame(frames[k], numbers[k], stamps[k]) for k in range(n)]          # oldest first
+            slots.extend(popped[::-1])                                                   # the batch's frame order: newest first
+            out[i].append(popped)
+        window_segments(res["segs"], res["nseg"], slots, tuple(min_seg_size), crop_region, batch, first)
+        first += int(res["nseg"].sum())
     return out

@@ -4,7 +4,7 @@ classifier, tracker step -> events -> swift count.  The regions come from the ch
 (generate_regions on the first frame, __main__.py:62-63) or are handed in; the reader is anything with the
 reference FrameReader's read_frame / get_n_frames / total_frames (swiftwatcher_amd.io_frames.ArrayReader for decoded
 frames)."""
-from .data_structures import FrameQueue, segment_windows
+from .data_structures import FrameQueue, segment_window_groups, segment_windows
 from .io_frames import ArrayReader
 from .segment_tracking import SegmentTracker, apply_hungarian_algorithm
 from . import event_classification as ec
@@ -90,3 +90,103 @@ def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, **kw):
     """Decoded frames (oldest first) -> (swift count, events).  Regions either explicit or from corners=..."""
     events = swift_counting_algorithm(ArrayReader(frames, fps=fps), crop_region, roi_mask, **kw)
     return ec.count_swifts(events), events
+
+
+def plan_calls(items, n, pad_factor=2.0):
+    """Which groups of windows share one swk_batch_run_groups call.  items: (key, P, nwin) per group, P = ROI pixels.  The library
+    runs the IALM of a call over planes zero-padded to the call's largest P, so a call holding windows of very different sizes moves
+    more bytes than separate calls would: a call is closed when padding to its largest P would make the IALM's elements more than
+    pad_factor times the windows' own.  Groups with P < n run at their own P inside any call (no padding) and join the first one.
+    Returns a list of calls, each a list of keys; largest ROIs first."""
+    big = sorted((it for it in items if it[1] >= n), key=lambda it: -it[1])
+    small = [it[0] for it in items if it[1] < n]
+    calls, cur, pmax, real, wins = [], [], 0, 0, 0
+    for key, P, nwin in big:
+        if cur:
+            padded = max(pmax, P) * (wins + nwin)
+            if padded > pad_factor * (real + P * nwin):
+                calls.append(cur)
+                cur, pmax, real, wins = [], 0, 0, 0
+        cur.append(key)
+        pmax, real, wins = max(pmax, P), real + P * nwin, wins + nwin
+    if cur:
+        calls.append(cur)
+    if small:
+        if calls:
+            calls[0].extend(small)
+        else:
+            calls.append(small)
+    return calls
+
+
+def schedule_videos(readers, sizes, segment, consume, in_flight=4, windows_per_call=1, queue_size=21, pad_factor=2.0):
+    """The in-flight loop of count_swifts_videos, without the GPU: `in_flight` videos are open at a time; every round takes the next
+    windows_per_call queue-fuls (reader.get_n_frames, padded with null frames past the end) of each open video, plan_calls splits
+    them into calls, segment(groups) -> per group the popped frame lists runs each call (groups = [(video index, windows)]), and
+    consume(video index, popped lists) gets them in each video's own order.  A video whose frames are all read leaves after its round
+    and the next one takes its place.  sizes[v] = ROI pixels of video v (for the planner).  Returns the calls made, as lists of
+    (video index, windows in the group)."""
+    pending = list(range(len(readers)))[::-1]
+    open_, read, log = [], {}, []
+    while pending or open_:
+        while pending and len(open_) < in_flight:
+            v = pending.pop()
+            open_.append(v)
+            read[v] = 0
+        taken = {}
+        for v in open_:
+            r = readers[v]
+            windows = []
+            while len(windows) < windows_per_call and read[v] < r.total_frames:
+                triple = r.get_n_frames(n=queue_size)
+                windows.append(triple)
+                read[v] += sum(1 for k in triple[1] if k >= 0)          # null frames are not counted
+            if windows:
+                taken[v] = windows
+        items = [(v, sizes[v], len(w)) for v, w in taken.items()]
+        for call in plan_calls(items, queue_size, pad_factor):
+            groups = [(v, taken[v]) for v in sorted(call, key=open_.index)]
+            log.append([(v, len(w)) for v, w in groups])
+            for (v, _), popped in zip(groups, segment(groups)):
+                consume(v, popped)
+        open_ = [v for v in open_ if read[v] < readers[v].total_frames]
+    return log
+
+
+def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows_per_call=1, classifier=None, queue_size=21,
+                        min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None):
+    """count_swifts over a list of videos (the reference's loop over its video list, __main__.py:21), several videos at a time on one
+    GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
+    windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
+    frames one by one in the reference's order, so every count and event list equals count_swifts on that video alone.
+    videos: readers (read_frame / get_n_frames / total_frames) or decoded frame arrays (oldest first); regions: per video
+    (crop_region, roi_mask), or corners: per video the chimney's top edge (the regions then come from its first frame, :62-63).
+    Returns [(count, events), ...] in input order."""
+    readers = [v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
+    if regions is None:
+        if corners is None:
+            raise ValueError("either regions or corners are needed")
+        regions = []
+        for r, c in zip(readers, corners):
+            crop_region, roi_mask, _ = img.generate_regions(r.read_frame(0, increment=False), c)
+            regions.append((crop_region, roi_mask))
+    if len(regions) != len(readers):
+        raise ValueError("one region pair per video")
+    trackers = [SegmentTracker(mask) for _, mask in regions]
+    sizes = [(cr[1][0] - cr[0][0]) * (cr[1][1] - cr[0][1]) for cr, _ in regions]
+
+    def segment(groups):
+        out = segment_window_groups([(w, regions[v][0]) for v, w in groups], min_seg_size, device=device, params=params,
+                                    classifier=classifier)
+        if classifier is not None:
+            classifier.classify_frames([fr for per in out for popped in per for fr in popped])
+        return out
+
+    def consume(v, popped_lists):
+        for popped in popped_lists:
+            for frame in popped:
+                trackers[v].step(frame)
+
+    schedule_videos(readers, sizes, segment, consume, in_flight=in_flight, windows_per_call=windows_per_call, queue_size=queue_size,
+                    pad_factor=pad_factor)
+    return [(ec.count_swifts(t.detected_events), t.detected_events) for t in trackers]
