@@ -412,35 +412,29 @@ class Context:
             self._check(self._lib.swk_batch_run(self._h, ctypes.byref(inp), ctypes.byref(params), ctypes.byref(out)))
         return generation
 
-    def batch_run(self, frames, nwin, n, crop=None, params=None, stages=STAGES, want_A=False, want_E=False, seg_cap=255,
-                  device_stages=False, reverse_frames=False):
-        """Host-buffer convenience wrapper.
-
-        frames: u8 array (nwin*n, H, W, 3) or (nwin*n, H, W), C-contiguous in the last two/three axes
-        crop:   (x0, y0, Wc, Hc) inside each frame, or None for the whole frame
-        Returns dict with the requested stage stacks (nwin*n, Hc, Wc) u8, 'iters' (nwin,),
-        'nseg' (nwin*n,), 'segs' structured array (nwin*n, seg_cap), 'generation' (see batch_run_raw), optionally 'A'/'E' (nwin, P, n).
-        device_stages=True: the stage stacks stay on the GPU -- res['planes'] is a DevicePlanes whose read(stage, frame)
-        copies one image to the host when somebody asks for it (swk_output.planes_on_device).
-        reverse_frames=True: frame j of the batch is frames[F - 1 - j] (negative frame stride): a window that lies in memory in
-        the order it was read becomes a queue (position 0 = newest) without being reversed.
-        """
-        params = params or default_params()
+    def _group_io(self, frames, nwin, n, crop, reverse_frames, seg_cap, stages, want_A, want_E, device_stages=False):
+        """One group's (Input, Output, result dict): frames checked, result arrays allocated and wired into the Output.
+        frames: u8 (nwin*n, H, W[, 3]), contiguous along columns / channels; a numpy array, or a torch tensor on this context's
+        GPU (read in place, SWK_MEM_DEVICE)."""
         F = nwin * n
-        if frames.dtype != np.uint8 or frames.shape[0] != F or frames.ndim not in (3, 4):
+        on_device = hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False)
+        shape = tuple(frames.shape)
+        if str(frames.dtype) != ("torch.uint8" if on_device else "uint8") or shape[0] != F or len(shape) not in (3, 4):
             raise ValueError("frames must be uint8 (nwin*n, H, W[, 3])")
-        ch = 1 if frames.ndim == 3 else frames.shape[3]
-        if frames.ndim == 4 and (frames.strides[3] != 1 or frames.strides[2] != ch):
+        if on_device:
+            strides, base = tuple(int(x) for x in frames.stride()), frames.data_ptr()          # (elements = bytes for uint8)
+        else:
+            strides, base = frames.strides, frames.ctypes.data
+        ch = 1 if len(shape) == 3 else shape[3]
+        if (len(shape) == 4 and (strides[3] != 1 or strides[2] != ch)) or (len(shape) == 3 and strides[2] != 1):
             raise ValueError("frames must be contiguous along columns/channels")
-        if frames.ndim == 3 and frames.strides[2] != 1:
-            raise ValueError("frames must be contiguous along columns")
-        H, W = frames.shape[1], frames.shape[2]
+        H, W = shape[1], shape[2]
         x0, y0, Wc, Hc = crop if crop is not None else (0, 0, W, H)
         if x0 < 0 or y0 < 0 or x0 + Wc > W or y0 + Hc > H:
             raise ValueError("crop rectangle outside the frame")
-        inp = Input(frames=frames.ctypes.data + ((F - 1) * frames.strides[0] if reverse_frames else 0), mem=MEM_HOST, channels=ch,
-                    nwin=nwin, n=n, Hc=Hc, Wc=Wc, x0=x0, y0=y0,
-                    frame_stride=-frames.strides[0] if reverse_frames else frames.strides[0], row_stride=frames.strides[1])
+        inp = Input(frames=base + ((F - 1) * strides[0] if reverse_frames else 0), mem=MEM_DEVICE if on_device else MEM_HOST,
+                    channels=ch, nwin=nwin, n=n, Hc=Hc, Wc=Wc, x0=x0, y0=y0,
+                    frame_stride=-strides[0] if reverse_frames else strides[0], row_stride=strides[1])
         res = {}
         out = Output(mem=MEM_HOST, seg_cap=seg_cap)
         if device_stages and stages:
@@ -465,7 +459,23 @@ class Context:
         out.iters = res["iters"].ctypes.data
         out.nseg = res["nseg"].ctypes.data
         out.segs = res["segs"].ctypes.data
-        res["generation"] = self.batch_run_raw(inp, params, out)          # for swk_segment_inputs_last (segment_inputs_last)
+        return inp, out, res
+
+    def batch_run(self, frames, nwin, n, crop=None, params=None, stages=STAGES, want_A=False, want_E=False, seg_cap=255,
+                  device_stages=False, reverse_frames=False):
+        """Host-buffer convenience wrapper.
+
+        frames: u8 array (nwin*n, H, W, 3) or (nwin*n, H, W), C-contiguous in the last two/three axes
+        crop:   (x0, y0, Wc, Hc) inside each frame, or None for the whole frame
+        Returns dict with the requested stage stacks (nwin*n, Hc, Wc) u8, 'iters' (nwin,),
+        'nseg' (nwin*n,), 'segs' structured array (nwin*n, seg_cap), 'generation' (see batch_run_raw), optionally 'A'/'E' (nwin, P, n).
+        device_stages=True: the stage stacks stay on the GPU -- res['planes'] is a DevicePlanes whose read(stage, frame)
+        copies one image to the host when somebody asks for it (swk_output.planes_on_device).
+        reverse_frames=True: frame j of the batch is frames[F - 1 - j] (negative frame stride): a window that lies in memory in
+        the order it was read becomes a queue (position 0 = newest) without being reversed.
+        """
+        inp, out, res = self._group_io(frames, nwin, n, crop, reverse_frames, seg_cap, stages, want_A, want_E, device_stages)
+        res["generation"] = self.batch_run_raw(inp, params or default_params(), out)          # for swk_segment_inputs_last
         return res
 
     def batch_run_groups(self, groups, params=None, stages=STAGES, want_A=False, want_E=False, seg_cap=255):
@@ -480,55 +490,11 @@ class Context:
             raise ValueError("no groups")
         ins = (Input * G)()
         outs = (Output * G)()
-        results, keep = [], []
+        results = []
         for g, grp in enumerate(groups):
-            frames, nwin, n = grp["frames"], int(grp["nwin"]), int(grp["n"])
-            cap = int(grp.get("seg_cap", seg_cap))
-            F = nwin * n
-            on_device = hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False)
-            shape = tuple(frames.shape)
-            if on_device:
-                if str(frames.dtype) != "torch.uint8":
-                    raise ValueError("frames must be uint8")
-                strides = tuple(int(x) for x in frames.stride())           # (elements = bytes for uint8)
-                base = frames.data_ptr()
-            else:
-                if frames.dtype != np.uint8:
-                    raise ValueError("frames must be uint8")
-                strides, base = frames.strides, frames.ctypes.data
-                keep.append(frames)
-            if shape[0] != F or len(shape) not in (3, 4):
-                raise ValueError("frames must be uint8 (nwin*n, H, W[, 3])")
-            ch = 1 if len(shape) == 3 else shape[3]
-            if (len(shape) == 4 and (strides[3] != 1 or strides[2] != ch)) or (len(shape) == 3 and strides[2] != 1):
-                raise ValueError("frames must be contiguous along columns/channels")
-            H, W = shape[1], shape[2]
-            x0, y0, Wc, Hc = grp.get("crop") or (0, 0, W, H)
-            if x0 < 0 or y0 < 0 or x0 + Wc > W or y0 + Hc > H:
-                raise ValueError("crop rectangle outside the frame")
-            rev = bool(grp.get("reverse_frames", False))
-            ins[g] = Input(frames=base + ((F - 1) * strides[0] if rev else 0), mem=MEM_DEVICE if on_device else MEM_HOST, channels=ch,
-                           nwin=nwin, n=n, Hc=Hc, Wc=Wc, x0=x0, y0=y0, frame_stride=-strides[0] if rev else strides[0],
-                           row_stride=strides[1])
-            res = {}
-            out = Output(mem=MEM_HOST, seg_cap=cap)
-            for name in stages:
-                res[name] = np.empty((F, Hc, Wc), np.uint8)
-                setattr(out, name, res[name].ctypes.data)
-            P = Hc * Wc
-            if want_A:
-                res["A"] = np.empty((nwin, P, n), np.float64)
-                out.A = res["A"].ctypes.data
-            if want_E:
-                res["E"] = np.empty((nwin, P, n), np.float64)
-                out.E = res["E"].ctypes.data
-            res["iters"] = np.zeros(nwin, np.int32)
-            res["nseg"] = np.zeros(F, np.int32)
-            res["segs"] = np.zeros((F, cap), SEGMENT_DTYPE)
-            out.iters = res["iters"].ctypes.data
-            out.nseg = res["nseg"].ctypes.data
-            out.segs = res["segs"].ctypes.data
-            outs[g] = out
+            ins[g], outs[g], res = self._group_io(grp["frames"], int(grp["nwin"]), int(grp["n"]), grp.get("crop"),
+                                                  bool(grp.get("reverse_frames", False)), int(grp.get("seg_cap", seg_cap)), stages,
+                                                  want_A, want_E)
             results.append(res)
         with self._lock:
             self.generation += 1

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <string>
 #include <algorithm>
+#include <array>
 #include <vector>
 
 using namespace swk;
@@ -63,12 +64,12 @@ struct swk_ctx {
     int sparse_backoff = 0, norm_backoff = 0;   // batches for which a guess stays off after it failed (same video, same behaviour)
     int eig_method = 0;                  // 0 Newton-Schulz (MFMA), 1 Jacobi
     hipEvent_t ev_poll[2] = {nullptr, nullptr};   // the host polls convergence two iterations late (run_ialm)
-    std::vector<IalmWin> last_hw;        // host copy of the last batch's per-window IALM state (gather_iters): diagnostics
+    std::vector<IalmWin> last_hw;        // host copy of the last batch's per-window IALM state (account_iters): diagnostics
     IalmWin *last_win = nullptr;         // per-window IALM state of the last run
     int last_nwin = 0;
     int64_t pstride = 0;                 // plane pitch of the A/Y/E workspaces of the last IALM run
     int fpad = 0;                        // planes per window in them
-    // what the last swk_batch_run left on the device for swk_segment_inputs_last: its frames (SL_ROI copy of a host input,
+    // what the last batch call left on the device for swk_segment_inputs_last: its frames (SL_ROI copy of a host input,
     // or the caller's device frames) and region records; valid until a call reuses those buffers
     struct LastBatch {
         bool valid = false;
@@ -284,8 +285,7 @@ int host_stage_copy(swk_ctx *ctx, const swk_input *in, const HostStage &st, uint
 
 // ---- IALM driver ----------------------------------------------------------------------
 int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmbda, double tol, int maxiter,
-             bool want_A, bool want_E, uint8_t *dS, int32_t *h_iters /*host, optional*/, int32_t *d_iters /*device, optional*/,
-             bool speculate = true, int force_variant = 0)
+             bool want_A, bool want_E, uint8_t *dS, bool speculate = true, int force_variant = 0)
 {
     if (n < 1 || n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be in 1..128");
     const bool wide = n > kMaxN;          // 65 .. 128 frames: the plain f64 kernels (A/Y state, Jacobi in global memory)
@@ -428,7 +428,7 @@ int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmb
             NEED(ctx, kind == 0 ? SL_REDO_S : SL_REDO_S2, (size_t)cnt * wbytes, gs);
             for (int i = 0; i < cnt; ++i)
                 HIPCHK(ctx, hipMemcpyAsync(gx + (size_t)i * wbytes, dX + (size_t)list[i] * wbytes, wbytes, hipMemcpyDeviceToDevice, s));
-            const int rc1 = run_ialm(ctx, gx, cnt, n, P, lmbda, tol, maxiter, false, false, gs, nullptr, nullptr, false, kind == 0 ? variant : 2);
+            const int rc1 = run_ialm(ctx, gx, cnt, n, P, lmbda, tol, maxiter, false, false, gs, false, kind == 0 ? variant : 2);
             if (rc1) return rc1;
             std::vector<IalmWin> sub(cnt);
             HIPCHK(ctx, hipMemcpyAsync(sub.data(), ctx->last_win, (size_t)cnt * sizeof(IalmWin), hipMemcpyDeviceToHost, s));
@@ -453,45 +453,35 @@ int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmb
             ctx->last_nwin = nwin;
         }
     }
-    (void)h_iters; (void)d_iters;
     return SWK_OK;
 }
 
-// Iteration counts live in the per-window state structs.  Called once the stream has drained.
-int account_iters(swk_ctx *ctx, const std::vector<IalmWin> &hw, int32_t *h_iters, int32_t *d_iters);
-
-int gather_iters(swk_ctx *ctx, int32_t *h_iters, int32_t *d_iters)
+// Appends the per-window IALM state of the last run_ialm to hw (waits for it).
+int read_windows(swk_ctx *ctx, std::vector<IalmWin> &hw)
 {
-    const int nwin = ctx->last_nwin;
-    std::vector<IalmWin> hw(nwin);
+    const size_t w0 = hw.size();
+    hw.resize(w0 + ctx->last_nwin);
     // (on the context's own, non-blocking stream: a copy on the null stream would wait for every blocking stream of the process, and
     //  fails outright while another thread captures a HIP graph on one -- the classifier does, segment_classification.py)
-    HIPCHK(ctx, hipMemcpyAsync(hw.data(), ctx->last_win, (size_t)nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(hw.data() + w0, ctx->last_win, (size_t)ctx->last_nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return account_iters(ctx, hw, h_iters, d_iters);
+    return SWK_OK;
 }
 
-// Books the per-window IALM state of a batch (counters, diagnostics) and hands out its iteration counts.
-int account_iters(swk_ctx *ctx, const std::vector<IalmWin> &hw, int32_t *h_iters, int32_t *d_iters)
+// Books the per-window IALM state of a call (counters, diagnostics) and hands out its iteration counts (host, optional).
+void account_iters(swk_ctx *ctx, const std::vector<IalmWin> &hw, int32_t *iters)
 {
-    const int nwin = (int)hw.size();
-    std::vector<int32_t> it(nwin);
     ctx->last_hw = hw;
     ctx->last_int_start = 0;
     ctx->last_eig_sweeps = 0;
-    for (int w = 0; w < nwin; ++w) {
-        it[w] = hw[w].iter; ctx->window_iters += hw[w].iter; ctx->pass_b16 += hw[w].pass_b16;
+    for (size_t w = 0; w < hw.size(); ++w) {
+        if (iters) iters[w] = hw[w].iter;
+        ctx->window_iters += hw[w].iter; ctx->pass_b16 += hw[w].pass_b16;
         ctx->last_int_start += hw[w].int_gram ? 1 : 0;
         if (hw[w].refine == 2) ctx->refined_windows += 1;
         else if (hw[w].refine != 0) ctx->unrefined_windows += 1;
         if (hw[w].sweeps > ctx->last_eig_sweeps) ctx->last_eig_sweeps = hw[w].sweeps;
     }
-    if (h_iters) memcpy(h_iters, it.data(), (size_t)nwin * 4);
-    if (d_iters) {
-        HIPCHK(ctx, hipMemcpyAsync(d_iters, it.data(), (size_t)nwin * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // `it` is a local
-    }
-    return SWK_OK;
 }
 
 int segment_inputs_impl(swk_ctx *ctx, const uint8_t *frames, int64_t fs, int64_t rs, int F, int x0, int y0, int frame_h, int frame_w,
@@ -530,11 +520,379 @@ int segment_inputs_impl(swk_ctx *ctx, const uint8_t *frames, int64_t fs, int64_t
     return SWK_OK;
 }
 
-int copy_out(swk_ctx *ctx, void *dst, const void *src, size_t bytes, int mem)
+// rows x width bytes from src (rows spitch apart) to dst (dpitch apart): nothing when dst is src (an output written in place),
+// one plain copy when both sides are dense
+int copy_out(swk_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows, hipMemcpyKind kind)
 {
     if (!dst || dst == src) return SWK_OK;
-    HIPCHK(ctx, hipMemcpyAsync(dst, src, bytes, mem == SWK_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                               ctx->stream));
+    if (dpitch == width && spitch == width) HIPCHK(ctx, hipMemcpyAsync(dst, src, width * rows, kind, ctx->stream));
+    else HIPCHK(ctx, hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, ctx->stream));
+    return SWK_OK;
+}
+
+// ---- the batch driver of swk_batch_run (one group) and swk_batch_run_groups (G groups) ----------------
+// A group is one video's windows, with its own frames, memory, ROI and strides.  Every frame's u8 stage planes start at an offset
+// of their own and hold its H x W pixels.  The IALM runs once over all groups whose ROI has at least n pixels, on X planes zero-padded
+// to the largest of those ROIs (Pmax): zero pixel rows change neither X^T X nor ||X||_F nor max|X|, and their rows of A, E, Y and S
+// stay zero.  A group with fewer pixels than frames runs as a sub-batch of its own at its true P (there svp = min(P, n),
+// image_filtering.py:285, so padding would change the result).  One group is the plan's degenerate case -- one sub-batch, pitch = P,
+// offset 0 -- and takes the uniform kernels, working in the caller's device buffers where it may; several groups take the
+// per-frame geometry kernels, driven by descriptor tables, on library buffers.
+std::array<uint8_t *, 6> out_planes(const swk_output &o) { return {o.gray, o.rpca, o.bilateral, o.thresh, o.opened, o.labels}; }
+
+int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p, swk_output *outs)
+{
+    if (p->open_kh != 3 || p->open_kw != 3) return fail(ctx, SWK_ERR_ARG, "only the (3,3) opening window is implemented");
+    if (p->connectivity != 4 && p->connectivity != 8) return fail(ctx, SWK_ERR_ARG, "connectivity must be 4 or 8");
+    if (p->bil_d / 2 != 3) return fail(ctx, SWK_ERR_ARG, "the fused filter kernel implements bilateral d=7 (radius 3) only");
+    const int n = groups[0].n;
+    int64_t nwin64 = 0;
+    for (int g = 0; g < G; ++g) {
+        const swk_input *in = &groups[g];
+        const swk_output *out = &outs[g];
+        if (!in->frames) return fail(ctx, SWK_ERR_ARG, "null frames");
+        if (in->nwin < 1 || in->n < 1 || in->Hc < 1 || in->Wc < 1) return fail(ctx, SWK_ERR_ARG, "empty batch");
+        if (in->n != n) return fail(ctx, SWK_ERR_ARG, "every group must have the same frames per window");
+        if (in->channels != 1 && in->channels != 3) return fail(ctx, SWK_ERR_ARG, "channels must be 1 or 3");
+        if (in->n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be <= 128");
+        if (out->segs && (out->seg_cap < 1 || out->seg_cap > 255)) return fail(ctx, SWK_ERR_ARG, "seg_cap must be in 1..255");
+        if (in->Hc < 4 || in->Wc < 4) return fail(ctx, SWK_ERR_ARG, "ROI must be at least 4x4");
+        nwin64 += in->nwin;
+    }
+    if (nwin64 * n > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "too many frames in one call");
+    const int nwin = (int)nwin64, F = nwin * n;
+    const bool single = G == 1;
+
+    // ---- sub-batches of the IALM: [0] = every group with P >= n, padded to its largest P; then one per group with P < n ----
+    struct Sub { std::vector<int> gs; int P = 0, nwin = 0, w0 = 0; int64_t off = 0; bool A = false, E = false; };
+    std::vector<Sub> subs(1);
+    int Pmax = 0, Hmax = 0, Wmax = 0;
+    for (int g = 0; g < G; ++g) {
+        const int P = groups[g].Hc * groups[g].Wc;
+        Hmax = std::max(Hmax, groups[g].Hc);
+        Wmax = std::max(Wmax, groups[g].Wc);
+        Sub *sb = &subs[0];
+        if (P < n) { subs.emplace_back(); sb = &subs.back(); }
+        sb->gs.push_back(g);
+        sb->P = P > sb->P ? P : sb->P;
+        sb->nwin += groups[g].nwin;
+        sb->A = sb->A || outs[g].A; sb->E = sb->E || outs[g].E;
+    }
+    if (subs[0].gs.empty()) subs.erase(subs.begin());
+    std::vector<int> sub_of(G);
+    for (size_t k = 0; k < subs.size(); ++k)
+        for (int g : subs[k].gs) sub_of[g] = (int)k;
+    // capacity: run_ialm's limit on the padded plane (at the widest fpad, which its reruns may take), checked here so that a refused
+    // call launches nothing
+    const int fpad_max = std::max(ialm_mstate_fpad(n), (n + 15) & ~15);
+    size_t total = 0;                     // stage-plane bytes: sub-batches one after the other, each 256-byte aligned
+    int sub_first = 0;                    // windows in sub-batch order
+    for (Sub &sb : subs) {
+        Pmax = sb.P > Pmax ? sb.P : Pmax;
+        if ((int64_t)fpad_max * (((int64_t)sb.P + 127) & ~(int64_t)127) >= (1ll << 28))
+            return fail(ctx, SWK_ERR_ARG, "window too large: frames x padded ROI pixels must stay below 2^28");
+        sb.off = (int64_t)total;
+        total += ((size_t)sb.nwin * n * sb.P + 255) & ~(size_t)255;
+        sb.w0 = sub_first;
+        sub_first += sb.nwin;
+    }
+    // region records: one stride for the call (the largest cap), each group's own cap where it counts
+    bool want_props = false, seg_last = true, host_total = true;
+    int capmax = 1;
+    for (int g = 0; g < G; ++g) {
+        want_props = want_props || outs[g].segs || outs[g].nseg;
+        if (outs[g].segs && outs[g].seg_cap > capmax) capmax = outs[g].seg_cap;
+        seg_last = seg_last && outs[g].segs && groups[g].channels == 3;
+        host_total = host_total && outs[g].mem == SWK_MEM_HOST && outs[g].nseg;
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int rc;
+    ctx->last.valid = false;
+
+    // ---- every buffer first (a later NEED may not move one a queued kernel uses) ----
+    std::vector<HostStage> st(G);
+    std::vector<size_t> roi_off(G, 0);
+    size_t roi_bytes = 0;
+    for (int g = 0; g < G; ++g)
+        if (groups[g].mem == SWK_MEM_HOST) {
+            st[g] = host_stage_plan(&groups[g]);
+            roi_off[g] = roi_bytes;
+            roi_bytes += (st[g].bytes + 255) & ~(size_t)255;
+        }
+    size_t pn_bytes = 0;
+    std::vector<size_t> pn_off(G, 0);
+    for (int g = 0; g < G; ++g)
+        if ((outs[g].A || outs[g].E) && outs[g].mem == SWK_MEM_HOST) {
+            pn_off[g] = pn_bytes;
+            pn_bytes += (size_t)groups[g].nwin * n * groups[g].Hc * groups[g].Wc * 8;
+        }
+    uint8_t *roi = nullptr;
+    if (roi_bytes) NEED(ctx, SL_ROI, roi_bytes, roi);
+    // stage planes: gray (X), sparse image (S), bilateral, threshold, opened, labels.  One group works in the caller's device buffers
+    // (mem = SWK_MEM_DEVICE or planes_on_device) -- but a gray plane whose size is not a whole number of dwords stays in the library's
+    // padded buffer: k_gram_u8 reads it in dwords; the caller's copy is made at the end
+    const bool in_place = single && (outs[0].mem == SWK_MEM_DEVICE || outs[0].planes_on_device != 0);
+    const Slot plane_slot[6] = {SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8};
+    uint8_t *pl[6] = {};
+    for (int i = 0; i < 6; ++i) {
+        bool wanted = i != 2 && i != 3;          // the filter writes the bilateral and threshold images only when asked for
+        for (int g = 0; g < G; ++g) wanted = wanted || out_planes(outs[g])[i];
+        if (!wanted) continue;
+        uint8_t *mine = in_place ? out_planes(outs[0])[i] : nullptr;
+        if (i == 0 && ((size_t)F * groups[0].Hc * groups[0].Wc) % 4) mine = nullptr;
+        if (!mine) NEED(ctx, plane_slot[i], total + (i == 0 ? 4 : 0), mine);
+        pl[i] = mine;
+    }
+    uint8_t *const dX = pl[0], *const dS = pl[1], *const dBil = pl[2], *const dThr = pl[3], *const dOpen = pl[4], *const dLab = pl[5];
+    double *pn = nullptr;
+    if (pn_bytes) NEED(ctx, SL_PN, pn_bytes, pn);
+    // A or E of group g, (pixels, frames) layout: the caller's device buffer, or the group's part of the host outputs' staging buffer
+    auto ae_dst = [&](int g, int which) {
+        double *dst = which == 0 ? outs[g].A : outs[g].E;
+        return dst && outs[g].mem == SWK_MEM_HOST ? pn + pn_off[g] / 8 : dst;
+    };
+    swk_segment *dsegs = nullptr; int32_t *dnseg = nullptr;
+    if (want_props) {
+        const bool rec_in_place = single && outs[0].mem == SWK_MEM_DEVICE;          // one group's device records are written in place
+        if (rec_in_place && outs[0].segs) dsegs = outs[0].segs; else NEED(ctx, SL_SEGS, (size_t)F * capmax * sizeof(swk_segment), dsegs);
+        if (rec_in_place && outs[0].nseg) dnseg = outs[0].nseg; else NEED(ctx, SL_NSEG, (size_t)F * 4, dnseg);
+    }
+    // labelling: the one-workgroup-per-frame kernel for every group that fits it, the multi-kernel path for the others (several
+    // groups: on a dense copy of the group's planes)
+    size_t lds = 0, Pp = 1, words = 1, ccl_F = 1, ccl_Pp = 1, ccl_words_ = 1, tmp_bytes = 16;
+    std::vector<char> fused(G);
+    for (int g = 0; g < G; ++g) {
+        const int H = groups[g].Hc, W = groups[g].Wc, Fg = groups[g].nwin * n;
+        fused[g] = ccl_frame_supported(H, W);
+        Pp = std::max(Pp, ccl_padded(H, W));
+        words = std::max(words, ccl_words(H, W));
+        if (fused[g]) lds = std::max(lds, ccl_frame_lds_bytes(H, W));
+        else {
+            ccl_F = std::max(ccl_F, (size_t)Fg);
+            ccl_Pp = std::max(ccl_Pp, ccl_padded(H, W));
+            ccl_words_ = std::max(ccl_words_, ccl_words(H, W));
+            if (!single) tmp_bytes = std::max(tmp_bytes, (size_t)Fg * H * W);
+        }
+    }
+    CclBuffers cb{};
+    cb.Pp = (int)Pp;
+    cb.words = (int)words;          // (the geometry kernel takes each frame's own)
+    NEED(ctx, SL_PARENT, std::max((size_t)F * Pp, ccl_F * ccl_Pp) * 4, cb.parent);
+    NEED(ctx, SL_ROOTBITS, ccl_F * ccl_words_ * 4, cb.rootbits);
+    NEED(ctx, SL_WORDPREFIX, ccl_F * ccl_words_ * 4, cb.wordprefix);
+    NEED(ctx, SL_NCOMP, (size_t)F * 4, cb.ncomp);
+    NEED(ctx, SL_TABLE, ccl_F * 256 * 8 * 4, cb.table);
+    NEED(ctx, SL_SUMS, ccl_F * 256 * 2 * 8, cb.sums);
+    uint8_t *tmp_in = nullptr, *tmp_out = nullptr;
+    if (tmp_bytes > 16) { NEED(ctx, SL_TMP_IN, tmp_bytes, tmp_in); NEED(ctx, SL_TMP_OUT, tmp_bytes, tmp_out); }
+    // several groups: descriptor tables, one upload: windows (gather), frames (filter), frames (labelling), frames (classifier
+    // inputs), windows in sub-batch order (A, then E)
+    const size_t o_win = 0, o_gf = o_win + (((size_t)nwin * sizeof(GroupWin) + 15) & ~(size_t)15);
+    const size_t o_gc = o_gf + (size_t)F * sizeof(FrameGeom), o_sf = o_gc + (size_t)F * sizeof(FrameGeom);
+    const size_t o_pa = o_sf + (size_t)F * sizeof(SegFrame), o_pe = o_pa + (size_t)nwin * sizeof(PnWin);
+    const size_t tab_bytes = o_pe + (size_t)nwin * sizeof(PnWin);
+    uint8_t *dtab = nullptr;
+    if (!single) NEED(ctx, SL_GRP, tab_bytes, dtab);
+    rc = ensure_bilateral(ctx, p->bil_d, p->bil_sigma_color, p->bil_sigma_space);
+    if (rc) return rc;
+
+    // ---- inputs: host groups staged one after the other into the ROI buffer ----
+    struct View {
+        const uint8_t *frames; int64_t fs, rs; int x0, y0;
+        int frame_h() const { return (int)((fs < 0 ? -fs : fs) / rs); }
+        int frame_w() const { return (int)(rs / 3); }
+    };
+    std::vector<View> view(G);
+    for (int g = 0; g < G; ++g) {
+        const swk_input *in = &groups[g];
+        View &v = view[g];
+        v = {in->frames, in->frame_stride, in->row_stride, in->x0, in->y0};
+        if (in->mem == SWK_MEM_HOST) {
+            Timed t(ctx, SWK_K_COPY);
+            rc = host_stage_copy(ctx, in, st[g], roi + roi_off[g], &v.frames, &v.fs, &v.rs, &v.x0, &v.y0);
+            if (rc) return rc;
+        }
+    }
+    std::vector<int> win0(G + 1, 0);           // first window of each group, call order
+    std::vector<int> swin0(G);                 // ... and sub-batch order
+    std::vector<int64_t> goff(G);              // stage-plane offset of each group's first frame
+    std::vector<int> fill(subs.size(), 0);     // windows of each sub-batch placed so far
+    for (int g = 0; g < G; ++g) {
+        const Sub &sb = subs[sub_of[g]];
+        win0[g + 1] = win0[g] + groups[g].nwin;
+        swin0[g] = sb.w0 + fill[sub_of[g]];
+        goff[g] = sb.off + (int64_t)fill[sub_of[g]] * n * sb.P;
+        fill[sub_of[g]] += groups[g].nwin;
+    }
+    int vec = 4;
+    std::vector<uint8_t> tab(single ? 0 : tab_bytes, 0);          // (uploaded asynchronously: lives until the call's final sync)
+    if (!single) {
+        GroupWin *hwin = (GroupWin *)(tab.data() + o_win);
+        FrameGeom *hgf = (FrameGeom *)(tab.data() + o_gf), *hgc = (FrameGeom *)(tab.data() + o_gc);
+        SegFrame *hsf = (SegFrame *)(tab.data() + o_sf);
+        PnWin *hpa = (PnWin *)(tab.data() + o_pa), *hpe = (PnWin *)(tab.data() + o_pe);
+        for (int g = 0; g < G; ++g) {
+            const swk_input *in = &groups[g];
+            const View &v = view[g];
+            const int H = in->Hc, W = in->Wc, P = H * W, pitch = subs[sub_of[g]].P;
+            if (P % 4 || pitch % 4 || goff[g] % 4) vec = std::min(vec, (P % 2 || pitch % 2 || goff[g] % 2) ? 1 : 2);
+            for (int wl = 0; wl < in->nwin; ++wl) {
+                const int w = win0[g] + wl;
+                GroupWin &d = hwin[w];
+                d.src = v.frames + (int64_t)wl * n * v.fs;
+                d.fs = v.fs; d.rs = v.rs; d.off = goff[g] + (int64_t)wl * n * pitch;
+                d.x0 = v.x0; d.y0 = v.y0; d.H = H; d.W = W; d.channels = in->channels; d.pitch = pitch;
+                const int ws = swin0[g] + wl;
+                const size_t wb = (size_t)wl * n * P;
+                hpa[ws].P = hpe[ws].P = P;
+                if (outs[g].A) hpa[ws].dst = ae_dst(g, 0) + wb;
+                if (outs[g].E) hpe[ws].dst = ae_dst(g, 1) + wb;
+                for (int j = 0; j < n; ++j) {
+                    const int f = w * n + j;
+                    hgf[f] = {H, W, d.off + (int64_t)j * pitch};
+                    hgc[f] = fused[g] ? hgf[f] : FrameGeom{0, 0, 0};
+                    hsf[f].frame = v.frames + ((int64_t)wl * n + j) * v.fs;
+                    hsf[f].rs = v.rs;
+                    hsf[f].frame_h = v.frame_h();
+                    hsf[f].frame_w = v.frame_w();
+                    hsf[f].x0 = v.x0; hsf[f].y0 = v.y0;
+                    hsf[f].cap = outs[g].segs ? outs[g].seg_cap : 1;
+                }
+            }
+        }
+        HIPCHK(ctx, hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, s));
+    }
+    const int H0 = groups[0].Hc, W0 = groups[0].Wc;          // (one group's geometry)
+
+    // ---- gray + ROI gather into the (padded) X planes ----
+    {
+        Timed t(ctx, SWK_K_GRAY);
+        if (single) launch_gray(s, view[0].frames, groups[0].channels, view[0].fs, view[0].rs, view[0].x0, view[0].y0, F, H0, W0, p->gray_mode, dX);
+        else launch_gray_groups(s, (const GroupWin *)(dtab + o_win), F, n, Pmax, p->gray_mode, dX);
+    }
+
+    // ---- IALM per sub-batch; its float64 factors leave before the next sub-batch reuses the workspaces ----
+    std::vector<IalmWin> hw_sub;          // window state, sub-batch order
+    for (size_t k = 0; k < subs.size(); ++k) {
+        const Sub &sb = subs[k];
+        rc = run_ialm(ctx, dX + sb.off, sb.nwin, n, sb.P, p->lmbda, p->tol, p->maxiter, sb.A, sb.E, dS + sb.off);
+        if (rc) return rc;
+        for (int which = 0; which < 2; ++which) {
+            if (!(which == 0 ? sb.A : sb.E)) continue;
+            const double *planes = (const double *)ctx->slot[which == 0 ? SL_A : SL_E];
+            {
+                Timed t(ctx, SWK_K_COPY);
+                if (single) launch_planes_to_pn(s, planes, ae_dst(0, which), sb.nwin, n, sb.P, ctx->pstride, ctx->fpad);
+                else launch_planes_to_pn_groups(s, planes, (const PnWin *)(dtab + (which == 0 ? o_pa : o_pe)) + sb.w0, sb.nwin, n,
+                                                sb.P, ctx->pstride, ctx->fpad);
+            }
+            for (int g : sb.gs) {
+                double *dst = which == 0 ? outs[g].A : outs[g].E;
+                if (dst && outs[g].mem == SWK_MEM_HOST)
+                    HIPCHK(ctx, hipMemcpyAsync(dst, ae_dst(g, which), (size_t)groups[g].nwin * n * groups[g].Hc * groups[g].Wc * 8,
+                                               hipMemcpyDeviceToHost, s));
+            }
+        }
+        // the next sub-batch reuses the window-state slot: this one's state is read now (the last one's after the final sync)
+        if (k + 1 < subs.size()) {
+            rc = read_windows(ctx, hw_sub);
+            if (rc) return rc;
+        }
+    }
+
+    // ---- bilateral + threshold + opening ----
+    {
+        Timed t(ctx, SWK_K_FILTER);
+        if (single) launch_filter_fused(s, dS, F, H0, W0, ctx->bil, p->bil_fma, p->thresh, dBil, dThr, dOpen);
+        else launch_filter_fused_geom(s, dS, F, Hmax, Wmax, (const FrameGeom *)(dtab + o_gf), total, ctx->bil, p->bil_fma, p->thresh,
+                                      dBil, dThr, dOpen);
+    }
+
+    // ---- labels + region properties ----
+    if (want_props) HIPCHK(ctx, hipMemsetAsync(dsegs, 0, (size_t)F * capmax * sizeof(swk_segment), s));
+    if (lds) {
+        Timed t(ctx, SWK_K_CCL);
+        if (single) launch_ccl_frame(s, dOpen, F, H0, W0, p->connectivity, p->label_order, cb, nullptr, dLab, want_props, capmax, dsegs, dnseg);
+        else launch_ccl_frame_geom(s, dOpen, F, (const FrameGeom *)(dtab + o_gc), lds, vec, p->connectivity, p->label_order, cb, dLab,
+                                   capmax, dsegs, dnseg);
+    }
+    for (int g = 0; g < G; ++g) {
+        if (fused[g]) continue;
+        const int H = groups[g].Hc, W = groups[g].Wc, P = H * W, Fg = groups[g].nwin * n, pitch = subs[sub_of[g]].P;
+        const int f0 = win0[g] * n;
+        CclBuffers gb = cb;
+        gb.Pp = (int)ccl_padded(H, W);
+        gb.words = (int)ccl_words(H, W);
+        gb.ncomp = cb.ncomp + f0;
+        uint8_t *src = single ? dOpen : tmp_in, *lab = single ? dLab : tmp_out;
+        if (!single) HIPCHK(ctx, hipMemcpy2DAsync(tmp_in, P, dOpen + goff[g], pitch, P, Fg, hipMemcpyDeviceToDevice, s));
+        { Timed t(ctx, SWK_K_CCL); launch_ccl(s, src, Fg, H, W, p->connectivity, p->label_order, gb, nullptr, lab); }
+        if (want_props) {
+            Timed t(ctx, SWK_K_PROPS);
+            launch_regionprops(s, lab, Fg, H, W, gb, capmax, dsegs + (size_t)f0 * capmax, dnseg + f0);
+        }
+        if (!single) HIPCHK(ctx, hipMemcpy2DAsync(dLab + goff[g], pitch, tmp_out, P, P, Fg, hipMemcpyDeviceToDevice, s));
+    }
+
+    // ---- outputs, group by group, in swk_batch_run's layouts (what was written in place is not copied) ----
+    {
+        Timed t(ctx, SWK_K_COPY);
+        for (int g = 0; g < G; ++g) {
+            const swk_output *out = &outs[g];
+            const size_t P = (size_t)groups[g].Hc * groups[g].Wc, Fg = (size_t)groups[g].nwin * n, pitch = subs[sub_of[g]].P;
+            const size_t f0 = (size_t)win0[g] * n;
+            const bool dev_planes = out->mem == SWK_MEM_DEVICE || out->planes_on_device != 0;
+            const hipMemcpyKind pk = dev_planes ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+            const hipMemcpyKind ok = out->mem == SWK_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+            const std::array<uint8_t *, 6> dst = out_planes(*out);
+            for (int i = 0; i < 6; ++i)
+                if (dst[i] && (rc = copy_out(ctx, dst[i], P, pl[i] + goff[g], pitch, P, Fg, pk))) return rc;
+            const size_t rec = sizeof(swk_segment);
+            if (out->segs && (rc = copy_out(ctx, out->segs, out->seg_cap * rec, dsegs + f0 * capmax, capmax * rec, out->seg_cap * rec, Fg, ok)))
+                return rc;
+            if (out->nseg && (rc = copy_out(ctx, out->nseg, Fg * 4, dnseg + f0, Fg * 4, Fg * 4, 1, ok))) return rc;
+        }
+    }
+    rc = sync(ctx);
+    if (rc) return rc;
+
+    // ---- iteration counts (sub-batch order -> call order) and the record swk_segment_inputs_last reads ----
+    rc = read_windows(ctx, hw_sub);
+    if (rc) return rc;
+    std::vector<IalmWin> hw(nwin);
+    for (int g = 0; g < G; ++g)
+        for (int wl = 0; wl < groups[g].nwin; ++wl) hw[win0[g] + wl] = hw_sub[swin0[g] + wl];
+    std::vector<int32_t> it(nwin);
+    account_iters(ctx, hw, it.data());
+    bool uploaded = false;
+    for (int g = 0; g < G; ++g) {
+        if (!outs[g].iters) continue;
+        if (outs[g].mem == SWK_MEM_DEVICE) {
+            HIPCHK(ctx, hipMemcpyAsync(outs[g].iters, it.data() + win0[g], (size_t)groups[g].nwin * 4, hipMemcpyHostToDevice, s));
+            uploaded = true;
+        } else memcpy(outs[g].iters, it.data() + win0[g], (size_t)groups[g].nwin * 4);
+    }
+    if (uploaded) HIPCHK(ctx, hipStreamSynchronize(s));          // `it` is a local
+    if (seg_last) {
+        swk_ctx::LastBatch &lb = ctx->last;
+        lb = swk_ctx::LastBatch{};
+        lb.nwin = nwin; lb.n = n;
+        lb.segs = dsegs; lb.nseg = dnseg; lb.cap = capmax;
+        if (single) {          // one geometry: k_segment_inputs
+            const View &v = view[0];
+            lb.frames = v.frames; lb.fs = v.fs; lb.rs = v.rs;
+            lb.Hc = H0; lb.Wc = W0; lb.x0 = v.x0; lb.y0 = v.y0; lb.frame_h = v.frame_h(); lb.frame_w = v.frame_w();
+        } else {
+            lb.fr = (const SegFrame *)(dtab + o_sf);          // per-frame frames and geometry: k_segment_inputs_groups
+        }
+        if (host_total) {
+            lb.total = 0;
+            for (int g = 0; g < G; ++g)
+                for (int f = 0; f < groups[g].nwin * n; ++f) lb.total += std::min(outs[g].nseg[f], outs[g].seg_cap);
+        }
+        lb.valid = true;
+    }
     return SWK_OK;
 }
 
@@ -805,453 +1163,16 @@ int32_t swk_set_eig_method(swk_ctx *ctx, int32_t method)
 int32_t swk_batch_run(swk_ctx *ctx, const swk_input *in, const swk_params *p, swk_output *out)
 {
     if (!ctx) return SWK_ERR_ARG;
-    if (!in || !p || !out || !in->frames) return fail(ctx, SWK_ERR_ARG, "null argument");
-    if (in->nwin < 1 || in->n < 1 || in->Hc < 1 || in->Wc < 1) return fail(ctx, SWK_ERR_ARG, "empty batch");
-    if (in->channels != 1 && in->channels != 3) return fail(ctx, SWK_ERR_ARG, "channels must be 1 or 3");
-    if (in->n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be <= 128");
-    if (p->open_kh != 3 || p->open_kw != 3) return fail(ctx, SWK_ERR_ARG, "only the (3,3) opening window is implemented");
-    if (p->connectivity != 4 && p->connectivity != 8) return fail(ctx, SWK_ERR_ARG, "connectivity must be 4 or 8");
-    if (p->bil_d / 2 != 3) return fail(ctx, SWK_ERR_ARG, "the fused filter kernel implements bilateral d=7 (radius 3) only");
-    if (out->segs && (out->seg_cap < 1 || out->seg_cap > 255)) return fail(ctx, SWK_ERR_ARG, "seg_cap must be in 1..255");
-    if (in->Hc < 4 || in->Wc < 4) return fail(ctx, SWK_ERR_ARG, "ROI must be at least 4x4");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const int F = in->nwin * in->n, H = in->Hc, W = in->Wc, P = H * W;
-    const size_t plane = (size_t)F * P;
-    const bool dev_out = out->mem == SWK_MEM_DEVICE;
-    const bool dev_planes = dev_out || out->planes_on_device != 0;       // the six u8 stage images stay on the device
-    int rc;
-    ctx->last.valid = false;
-
-    // ---- input ----
-    const uint8_t *dframes = in->frames;
-    int64_t fs = in->frame_stride, rs = in->row_stride;
-    int x0 = in->x0, y0 = in->y0;
-    if (in->mem == SWK_MEM_HOST) {
-        uint8_t *roi;
-        const HostStage st = host_stage_plan(in);
-        NEED(ctx, SL_ROI, st.bytes, roi);
-        Timed t(ctx, SWK_K_COPY);
-        rc = host_stage_copy(ctx, in, st, roi, &dframes, &fs, &rs, &x0, &y0);
-        if (rc) return rc;
-    }
-    // ---- stage buffers (caller's device buffers are written in place) ----
-    uint8_t *dX, *dS, *dBil = nullptr, *dThr = nullptr, *dOpen, *dLab;
-    // (a gray plane whose size is not a whole number of dwords stays in the library's padded buffer: k_gram_u8 reads
-    // it in dwords; the caller's copy is made at the end)
-    const bool gray_in_place = dev_planes && out->gray && (plane & 3) == 0;
-    if (gray_in_place) dX = out->gray; else NEED(ctx, SL_X, plane + 4, dX);
-    if (dev_planes && out->rpca) dS = out->rpca; else NEED(ctx, SL_S, plane, dS);
-    if (out->bilateral) { if (dev_planes) dBil = out->bilateral; else NEED(ctx, SL_BIL, plane, dBil); }
-    if (out->thresh) { if (dev_planes) dThr = out->thresh; else NEED(ctx, SL_THR, plane, dThr); }
-    if (dev_planes && out->opened) dOpen = out->opened; else NEED(ctx, SL_OPEN, plane, dOpen);
-    if (dev_planes && out->labels) dLab = out->labels; else NEED(ctx, SL_LAB8, plane, dLab);
-
-    { Timed t(ctx, SWK_K_GRAY); launch_gray(s, dframes, in->channels, fs, rs, x0, y0, F, H, W, p->gray_mode, dX); }
-
-    rc = run_ialm(ctx, dX, in->nwin, in->n, P, p->lmbda, p->tol, p->maxiter, out->A != nullptr, out->E != nullptr, dS,
-                  (!dev_out) ? out->iters : nullptr, dev_out ? out->iters : nullptr);
-    if (rc) return rc;
-
-    rc = ensure_bilateral(ctx, p->bil_d, p->bil_sigma_color, p->bil_sigma_space);
-    if (rc) return rc;
-    { Timed t(ctx, SWK_K_FILTER); launch_filter_fused(s, dS, F, H, W, ctx->bil, p->bil_fma, p->thresh, dBil, dThr, dOpen); }
-
-    CclBuffers cb{};
-    rc = ensure_ccl(ctx, F, H, W, &cb);
-    if (rc) return rc;
-    const bool want_props = out->segs || out->nseg;
-    const int cap = out->segs ? out->seg_cap : 1;
-    swk_segment *dsegs = nullptr; int32_t *dnseg = nullptr;
-    if (want_props) {
-        if (dev_out && out->segs) dsegs = out->segs; else NEED(ctx, SL_SEGS, (size_t)F * cap * sizeof(swk_segment), dsegs);
-        if (dev_out && out->nseg) dnseg = out->nseg; else NEED(ctx, SL_NSEG, (size_t)F * 4, dnseg);
-        HIPCHK(ctx, hipMemsetAsync(dsegs, 0, (size_t)F * cap * sizeof(swk_segment), s));
-    }
-    const bool fused_ccl = ccl_frame_supported(H, W);
-    if (fused_ccl) {
-        // one workgroup per frame: labels and region properties in a single kernel
-        Timed t(ctx, SWK_K_CCL);
-        launch_ccl_frame(s, dOpen, F, H, W, p->connectivity, p->label_order, cb, nullptr, dLab, want_props, cap, dsegs, dnseg);
-    } else {
-        Timed t(ctx, SWK_K_CCL);
-        launch_ccl(s, dOpen, F, H, W, p->connectivity, p->label_order, cb, nullptr, dLab);
-    }
-    if (want_props) {
-        if (!fused_ccl) { Timed t(ctx, SWK_K_PROPS); launch_regionprops(s, dLab, F, H, W, cb, cap, dsegs, dnseg); }
-        if (!dev_out) {
-            rc = copy_out(ctx, out->segs, dsegs, (size_t)F * cap * sizeof(swk_segment), out->mem); if (rc) return rc;
-            rc = copy_out(ctx, out->nseg, dnseg, (size_t)F * 4, out->mem); if (rc) return rc;
-        }
-    }
-    // ---- float outputs in the reference's (pixels, frames) layout ----
-    if (out->A || out->E) {
-        const size_t elems = (size_t)in->nwin * in->n * P;
-        for (int which = 0; which < 2; ++which) {
-            double *dst = which == 0 ? out->A : out->E;
-            if (!dst) continue;
-            const double *planes = (const double *)ctx->slot[which == 0 ? SL_A : SL_E];
-            double *pn;
-            if (dev_out) pn = dst; else NEED(ctx, SL_PN, elems * 8, pn);
-            { Timed t(ctx, SWK_K_COPY); launch_planes_to_pn(s, planes, pn, in->nwin, in->n, P, ctx->pstride, ctx->fpad); }
-            if (!dev_out) { rc = copy_out(ctx, dst, pn, elems * 8, out->mem); if (rc) return rc; HIPCHK(ctx, hipStreamSynchronize(s)); }
-        }
-    }
-    if (dev_planes && out->gray && !gray_in_place) { rc = copy_out(ctx, out->gray, dX, plane, SWK_MEM_DEVICE); if (rc) return rc; }
-    if (!dev_planes) {
-        Timed t(ctx, SWK_K_COPY);
-        rc = copy_out(ctx, out->gray, dX, plane, out->mem); if (rc) return rc;
-        rc = copy_out(ctx, out->rpca, dS, plane, out->mem); if (rc) return rc;
-        rc = copy_out(ctx, out->bilateral, dBil, plane, out->mem); if (rc) return rc;
-        rc = copy_out(ctx, out->thresh, dThr, plane, out->mem); if (rc) return rc;
-        rc = copy_out(ctx, out->opened, dOpen, plane, out->mem); if (rc) return rc;
-        rc = copy_out(ctx, out->labels, dLab, plane, out->mem); if (rc) return rc;
-    }
-    rc = sync(ctx);
-    if (rc) return rc;
-    if (out->segs && in->channels == 3) {
-        swk_ctx::LastBatch &lb = ctx->last;
-        lb.frames = dframes; lb.fs = fs; lb.rs = rs;
-        lb.nwin = in->nwin; lb.n = in->n; lb.Hc = H; lb.Wc = W; lb.x0 = x0; lb.y0 = y0;
-        lb.frame_h = (int)((fs < 0 ? -fs : fs) / rs); lb.frame_w = (int)(rs / 3);
-        lb.segs = dsegs; lb.nseg = dnseg; lb.cap = cap;
-        lb.fr = nullptr;
-        lb.total = -1;
-        if (!dev_out && out->nseg) {
-            lb.total = 0;
-            for (int f = 0; f < F; ++f) lb.total += out->nseg[f] < cap ? out->nseg[f] : cap;
-        }
-        lb.valid = true;
-    }
-    return gather_iters(ctx, dev_out ? nullptr : out->iters, dev_out ? out->iters : nullptr);
+    if (!in || !p || !out) return fail(ctx, SWK_ERR_ARG, "null argument");
+    return run_batch(ctx, in, 1, p, out);
 }
 
-// -------------------------------------------------------------------------------------
-// Several groups of windows (one video's windows each, every one with its own geometry and memory) in ONE call.
-// Stage planes: every frame's u8 planes start at a per-frame offset and hold its own H x W pixels.  The IALM runs once over all
-// groups whose ROI has at least n pixels, on X planes zero-padded to the largest of those ROIs (Pmax): zero pixel rows change
-// neither X^T X nor ||X||_F nor max|X|, and their rows of A, E, Y and S stay zero.  A group with fewer pixels than frames runs as a
-// sub-batch of its own at its true P (there svp = min(P, n), image_filtering.py:285, so padding would change the result).
+// Several groups of windows (one video's windows each, every one with its own geometry and memory) in ONE call (run_batch).
 int32_t swk_batch_run_groups(swk_ctx *ctx, const swk_input *groups, int32_t ngroups, const swk_params *p, swk_output *outs)
 {
     if (!ctx) return SWK_ERR_ARG;
     if (!groups || !p || !outs || ngroups < 1) return fail(ctx, SWK_ERR_ARG, "null argument");
-    if (p->open_kh != 3 || p->open_kw != 3) return fail(ctx, SWK_ERR_ARG, "only the (3,3) opening window is implemented");
-    if (p->connectivity != 4 && p->connectivity != 8) return fail(ctx, SWK_ERR_ARG, "connectivity must be 4 or 8");
-    if (p->bil_d / 2 != 3) return fail(ctx, SWK_ERR_ARG, "the fused filter kernel implements bilateral d=7 (radius 3) only");
-    const int G = ngroups, n = groups[0].n;
-    int64_t nwin64 = 0;
-    for (int g = 0; g < G; ++g) {
-        const swk_input *in = &groups[g];
-        const swk_output *out = &outs[g];
-        if (!in->frames) return fail(ctx, SWK_ERR_ARG, "null frames in a group");
-        if (in->nwin < 1 || in->n < 1 || in->Hc < 1 || in->Wc < 1) return fail(ctx, SWK_ERR_ARG, "empty group");
-        if (in->n != n) return fail(ctx, SWK_ERR_ARG, "every group must have the same frames per window");
-        if (in->channels != 1 && in->channels != 3) return fail(ctx, SWK_ERR_ARG, "channels must be 1 or 3");
-        if (in->n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be <= 128");
-        if (out->segs && (out->seg_cap < 1 || out->seg_cap > 255)) return fail(ctx, SWK_ERR_ARG, "seg_cap must be in 1..255");
-        if (in->Hc < 4 || in->Wc < 4) return fail(ctx, SWK_ERR_ARG, "ROI must be at least 4x4");
-        nwin64 += in->nwin;
-    }
-    if (nwin64 * n > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "too many frames in one call");
-    const int nwin = (int)nwin64, F = nwin * n;
-
-    // ---- sub-batches of the IALM: [0] = every group with P >= n, padded to its largest P; then one per group with P < n ----
-    struct Sub { std::vector<int> gs; int P = 0, nwin = 0; int64_t off = 0; bool A = false, E = false; };
-    std::vector<Sub> subs(1);
-    std::vector<int> sub_of(G);
-    for (int g = 0; g < G; ++g) {
-        const int P = groups[g].Hc * groups[g].Wc;
-        Sub *sb;
-        if (P >= n) { sb = &subs[0]; sub_of[g] = 0; }
-        else { subs.emplace_back(); sb = &subs.back(); sub_of[g] = (int)subs.size() - 1; }
-        sb->gs.push_back(g);
-        sb->P = P > sb->P ? P : sb->P;
-        sb->nwin += groups[g].nwin;
-        sb->A = sb->A || outs[g].A; sb->E = sb->E || outs[g].E;
-    }
-    if (subs[0].gs.empty()) subs.erase(subs.begin());
-    for (int g = 0; g < G; ++g) sub_of[g] = 0;
-    for (size_t k = 0; k < subs.size(); ++k)
-        for (int g : subs[k].gs) sub_of[g] = (int)k;
-    int Pmax = 0, Hmax = 0, Wmax = 0;
-    for (int g = 0; g < G; ++g) {
-        Hmax = groups[g].Hc > Hmax ? groups[g].Hc : Hmax;
-        Wmax = groups[g].Wc > Wmax ? groups[g].Wc : Wmax;
-    }
-    // capacity: run_ialm's limit on the padded plane, checked here so that a refused call launches nothing
-    const int fpad_max = std::max(ialm_mstate_fpad(n), (n + 15) & ~15);
-    size_t total = 0;                     // stage-plane bytes: sub-batches one after the other, each 256-byte aligned
-    for (Sub &sb : subs) {
-        Pmax = sb.P > Pmax ? sb.P : Pmax;
-        if ((int64_t)fpad_max * (((int64_t)sb.P + 127) & ~(int64_t)127) >= (1ll << 28))
-            return fail(ctx, SWK_ERR_ARG, "window too large: frames x padded ROI pixels must stay below 2^28");
-        sb.off = (int64_t)total;
-        total += ((size_t)sb.nwin * n * sb.P + 255) & ~(size_t)255;
-    }
-    // region records: one stride for the call (the largest cap), each group's own cap where it counts
-    bool want_props = false, seg_last = true, host_total = true;
-    int capmax = 1;
-    for (int g = 0; g < G; ++g) {
-        want_props = want_props || outs[g].segs || outs[g].nseg;
-        if (outs[g].segs && outs[g].seg_cap > capmax) capmax = outs[g].seg_cap;
-        seg_last = seg_last && outs[g].segs && groups[g].channels == 3;
-        host_total = host_total && outs[g].mem == SWK_MEM_HOST && outs[g].nseg;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    int rc;
-    ctx->last.valid = false;
-
-    // ---- every buffer first (a later NEED may not move one a queued kernel uses) ----
-    std::vector<HostStage> st(G);
-    std::vector<size_t> roi_off(G, 0);
-    size_t roi_bytes = 0;
-    for (int g = 0; g < G; ++g)
-        if (groups[g].mem == SWK_MEM_HOST) {
-            st[g] = host_stage_plan(&groups[g]);
-            roi_off[g] = roi_bytes;
-            roi_bytes += (st[g].bytes + 255) & ~(size_t)255;
-        }
-    bool any_bil = false, any_thr = false;
-    size_t pn_bytes = 0;
-    std::vector<size_t> pn_off(G, 0);
-    for (int g = 0; g < G; ++g) {
-        any_bil = any_bil || outs[g].bilateral;
-        any_thr = any_thr || outs[g].thresh;
-        if ((outs[g].A || outs[g].E) && outs[g].mem == SWK_MEM_HOST) {
-            pn_off[g] = pn_bytes;
-            pn_bytes += (size_t)groups[g].nwin * n * groups[g].Hc * groups[g].Wc * 8;
-        }
-    }
-    uint8_t *roi = nullptr, *dX, *dS, *dBil = nullptr, *dThr = nullptr, *dOpen, *dLab;
-    if (roi_bytes) NEED(ctx, SL_ROI, roi_bytes, roi);
-    NEED(ctx, SL_X, total + 4, dX);
-    NEED(ctx, SL_S, total, dS);
-    if (any_bil) NEED(ctx, SL_BIL, total, dBil);
-    if (any_thr) NEED(ctx, SL_THR, total, dThr);
-    NEED(ctx, SL_OPEN, total, dOpen);
-    NEED(ctx, SL_LAB8, total, dLab);
-    double *pn = nullptr;
-    if (pn_bytes) NEED(ctx, SL_PN, pn_bytes, pn);
-    swk_segment *dsegs = nullptr; int32_t *dnseg = nullptr;
-    if (want_props) {
-        NEED(ctx, SL_SEGS, (size_t)F * capmax * sizeof(swk_segment), dsegs);
-        NEED(ctx, SL_NSEG, (size_t)F * 4, dnseg);
-    }
-    // labelling: the one-workgroup-per-frame kernel for every group that fits it, the multi-kernel path (a dense copy of the
-    // group's planes) for the others
-    size_t lds = 0, Pp = 1, ccl_F = 1, ccl_Pp = 1, ccl_words_ = 1, tmp_bytes = 16;
-    std::vector<char> fused(G);
-    for (int g = 0; g < G; ++g) {
-        const int H = groups[g].Hc, W = groups[g].Wc, Fg = groups[g].nwin * n;
-        fused[g] = ccl_frame_supported(H, W);
-        Pp = std::max(Pp, ccl_padded(H, W));
-        if (fused[g]) lds = std::max(lds, ccl_frame_lds_bytes(H, W));
-        else {
-            ccl_F = std::max(ccl_F, (size_t)Fg);
-            ccl_Pp = std::max(ccl_Pp, ccl_padded(H, W));
-            ccl_words_ = std::max(ccl_words_, ccl_words(H, W));
-            tmp_bytes = std::max(tmp_bytes, (size_t)Fg * H * W);
-        }
-    }
-    CclBuffers cb{};
-    NEED(ctx, SL_PARENT, std::max((size_t)F * Pp, ccl_F * ccl_Pp) * 4, cb.parent);
-    NEED(ctx, SL_ROOTBITS, ccl_F * ccl_words_ * 4, cb.rootbits);
-    NEED(ctx, SL_WORDPREFIX, ccl_F * ccl_words_ * 4, cb.wordprefix);
-    NEED(ctx, SL_NCOMP, (size_t)F * 4, cb.ncomp);
-    NEED(ctx, SL_TABLE, ccl_F * 256 * 8 * 4, cb.table);
-    NEED(ctx, SL_SUMS, ccl_F * 256 * 2 * 8, cb.sums);
-    uint8_t *tmp_in = nullptr, *tmp_out = nullptr;
-    if (tmp_bytes > 16) { NEED(ctx, SL_TMP_IN, tmp_bytes, tmp_in); NEED(ctx, SL_TMP_OUT, tmp_bytes, tmp_out); }
-    // descriptor tables, one upload: windows (gather), frames (filter), frames (labelling), frames (classifier inputs),
-    // windows in sub-batch order (A, then E)
-    const size_t o_win = 0, o_gf = o_win + (((size_t)nwin * sizeof(GroupWin) + 15) & ~(size_t)15);
-    const size_t o_gc = o_gf + (size_t)F * sizeof(FrameGeom), o_sf = o_gc + (size_t)F * sizeof(FrameGeom);
-    const size_t o_pa = o_sf + (size_t)F * sizeof(SegFrame), o_pe = o_pa + (size_t)nwin * sizeof(PnWin);
-    const size_t tab_bytes = o_pe + (size_t)nwin * sizeof(PnWin);
-    uint8_t *dtab;
-    NEED(ctx, SL_GRP, tab_bytes, dtab);
-    rc = ensure_bilateral(ctx, p->bil_d, p->bil_sigma_color, p->bil_sigma_space);
-    if (rc) return rc;
-
-    // ---- inputs: host groups staged one after the other into the ROI buffer ----
-    struct View { const uint8_t *frames; int64_t fs, rs; int x0, y0; };
-    std::vector<View> view(G);
-    for (int g = 0; g < G; ++g) {
-        const swk_input *in = &groups[g];
-        View &v = view[g];
-        v = {in->frames, in->frame_stride, in->row_stride, in->x0, in->y0};
-        if (in->mem == SWK_MEM_HOST) {
-            Timed t(ctx, SWK_K_COPY);
-            rc = host_stage_copy(ctx, in, st[g], roi + roi_off[g], &v.frames, &v.fs, &v.rs, &v.x0, &v.y0);
-            if (rc) return rc;
-        }
-    }
-    std::vector<uint8_t> tab(tab_bytes, 0);
-    GroupWin *hwin = (GroupWin *)(tab.data() + o_win);
-    FrameGeom *hgf = (FrameGeom *)(tab.data() + o_gf), *hgc = (FrameGeom *)(tab.data() + o_gc);
-    SegFrame *hsf = (SegFrame *)(tab.data() + o_sf);
-    PnWin *hpa = (PnWin *)(tab.data() + o_pa), *hpe = (PnWin *)(tab.data() + o_pe);
-    std::vector<int> win0(G + 1, 0);           // first window of each group (call order)
-    std::vector<int64_t> goff(G);              // stage-plane offset of each group's first frame
-    std::vector<int> sbwin(G);                 // first window of each group inside its sub-batch
-    {
-        std::vector<int> fill(subs.size(), 0);
-        for (int g = 0; g < G; ++g) {
-            win0[g + 1] = win0[g] + groups[g].nwin;
-            const Sub &sb = subs[sub_of[g]];
-            sbwin[g] = fill[sub_of[g]];
-            fill[sub_of[g]] += groups[g].nwin;
-            goff[g] = sb.off + (int64_t)sbwin[g] * n * sb.P;
-        }
-    }
-    int vec = 4;
-    int sub_first = 0;
-    std::vector<int> sub_win0(subs.size());
-    for (size_t k = 0; k < subs.size(); ++k) { sub_win0[k] = sub_first; sub_first += subs[k].nwin; }
-    for (int g = 0; g < G; ++g) {
-        const swk_input *in = &groups[g];
-        const View &v = view[g];
-        const int H = in->Hc, W = in->Wc, P = H * W, pitch = subs[sub_of[g]].P;
-        if (P % 4 || pitch % 4 || goff[g] % 4) vec = std::min(vec, (P % 2 || pitch % 2 || goff[g] % 2) ? 1 : 2);
-        for (int wl = 0; wl < in->nwin; ++wl) {
-            const int w = win0[g] + wl;
-            GroupWin &d = hwin[w];
-            d.src = v.frames + (int64_t)wl * n * v.fs;
-            d.fs = v.fs; d.rs = v.rs; d.off = goff[g] + (int64_t)wl * n * pitch;
-            d.x0 = v.x0; d.y0 = v.y0; d.H = H; d.W = W; d.channels = in->channels; d.pitch = pitch;
-            const int ws = sub_win0[sub_of[g]] + sbwin[g] + wl;          // the window's place in sub-batch order
-            const bool host = outs[g].mem == SWK_MEM_HOST;
-            const size_t wb = (size_t)wl * n * P;
-            hpa[ws].P = hpe[ws].P = P;
-            if (outs[g].A) hpa[ws].dst = host ? pn + pn_off[g] / 8 + wb : outs[g].A + wb;
-            if (outs[g].E) hpe[ws].dst = host ? pn + pn_off[g] / 8 + wb : outs[g].E + wb;
-            for (int j = 0; j < n; ++j) {
-                const int f = w * n + j;
-                hgf[f] = {H, W, d.off + (int64_t)j * pitch};
-                hgc[f] = fused[g] ? hgf[f] : FrameGeom{0, 0, 0};
-                hsf[f].frame = v.frames + ((int64_t)wl * n + j) * v.fs;
-                hsf[f].rs = v.rs;
-                hsf[f].frame_h = (int)((v.fs < 0 ? -v.fs : v.fs) / v.rs);
-                hsf[f].frame_w = (int)(v.rs / 3);
-                hsf[f].x0 = v.x0; hsf[f].y0 = v.y0;
-                hsf[f].cap = outs[g].segs ? outs[g].seg_cap : 1;
-            }
-        }
-    }
-    const GroupWin *dwin = (const GroupWin *)(dtab + o_win);
-    const FrameGeom *dgf = (const FrameGeom *)(dtab + o_gf), *dgc = (const FrameGeom *)(dtab + o_gc);
-    const PnWin *dpa = (const PnWin *)(dtab + o_pa), *dpe = (const PnWin *)(dtab + o_pe);
-    HIPCHK(ctx, hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, s));
-
-    // ---- gray + ROI gather into the padded X planes ----
-    { Timed t(ctx, SWK_K_GRAY); launch_gray_groups(s, dwin, F, n, Pmax, p->gray_mode, dX); }
-
-    // ---- IALM per sub-batch; its float64 factors leave before the next sub-batch reuses the workspaces ----
-    std::vector<IalmWin> hw_sub(nwin);          // sub-batch order
-    for (size_t k = 0; k < subs.size(); ++k) {
-        const Sub &sb = subs[k];
-        rc = run_ialm(ctx, dX + sb.off, sb.nwin, n, sb.P, p->lmbda, p->tol, p->maxiter, sb.A, sb.E, dS + sb.off, nullptr, nullptr);
-        if (rc) return rc;
-        for (int which = 0; which < 2; ++which) {
-            if (!(which == 0 ? sb.A : sb.E)) continue;
-            const double *planes = (const double *)ctx->slot[which == 0 ? SL_A : SL_E];
-            { Timed t(ctx, SWK_K_COPY);
-              launch_planes_to_pn_groups(s, planes, (which == 0 ? dpa : dpe) + sub_win0[k], sb.nwin, n, sb.P, ctx->pstride, ctx->fpad); }
-            for (int g : sb.gs) {
-                double *dst = which == 0 ? outs[g].A : outs[g].E;
-                if (dst && outs[g].mem == SWK_MEM_HOST) {
-                    rc = copy_out(ctx, dst, pn + pn_off[g] / 8, (size_t)groups[g].nwin * n * groups[g].Hc * groups[g].Wc * 8, SWK_MEM_HOST);
-                    if (rc) return rc;
-                }
-            }
-        }
-        HIPCHK(ctx, hipMemcpyAsync(hw_sub.data() + sub_win0[k], ctx->last_win, (size_t)sb.nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-    }
-
-    // ---- bilateral + threshold + opening, every frame at its own geometry ----
-    { Timed t(ctx, SWK_K_FILTER);
-      launch_filter_fused_geom(s, dS, F, Hmax, Wmax, dgf, total, ctx->bil, p->bil_fma, p->thresh, dBil, dThr, dOpen); }
-
-    // ---- labels + region properties ----
-    if (want_props) HIPCHK(ctx, hipMemsetAsync(dsegs, 0, (size_t)F * capmax * sizeof(swk_segment), s));
-    if (lds) {
-        Timed t(ctx, SWK_K_CCL);
-        cb.Pp = (int)Pp;
-        launch_ccl_frame_geom(s, dOpen, F, dgc, lds, vec, p->connectivity, p->label_order, cb, dLab, want_props ? capmax : 1,
-                              want_props ? dsegs : nullptr, want_props ? dnseg : nullptr);
-    }
-    for (int g = 0; g < G; ++g) {
-        if (fused[g]) continue;
-        const int H = groups[g].Hc, W = groups[g].Wc, P = H * W, Fg = groups[g].nwin * n, pitch = subs[sub_of[g]].P;
-        const int f0 = win0[g] * n;
-        CclBuffers gb = cb;
-        gb.Pp = (int)ccl_padded(H, W);
-        gb.words = (int)ccl_words(H, W);
-        gb.ncomp = cb.ncomp + f0;
-        HIPCHK(ctx, hipMemcpy2DAsync(tmp_in, P, dOpen + goff[g], pitch, P, Fg, hipMemcpyDeviceToDevice, s));
-        { Timed t(ctx, SWK_K_CCL); launch_ccl(s, tmp_in, Fg, H, W, p->connectivity, p->label_order, gb, nullptr, tmp_out); }
-        if (want_props) {
-            Timed t(ctx, SWK_K_PROPS);
-            launch_regionprops(s, tmp_out, Fg, H, W, gb, capmax, dsegs + (size_t)f0 * capmax, dnseg + f0);
-        }
-        HIPCHK(ctx, hipMemcpy2DAsync(dLab + goff[g], pitch, tmp_out, P, P, Fg, hipMemcpyDeviceToDevice, s));
-    }
-
-    // ---- outputs, group by group, in swk_batch_run's layouts ----
-    {
-        Timed t(ctx, SWK_K_COPY);
-        for (int g = 0; g < G; ++g) {
-            const swk_output *out = &outs[g];
-            const int P = groups[g].Hc * groups[g].Wc, Fg = groups[g].nwin * n, pitch = subs[sub_of[g]].P;
-            const int f0 = win0[g] * n;
-            const bool dev_planes = out->mem == SWK_MEM_DEVICE || out->planes_on_device != 0;
-            const hipMemcpyKind pk = dev_planes ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-            const hipMemcpyKind ok = out->mem == SWK_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-            uint8_t *const dst[6] = {out->gray, out->rpca, out->bilateral, out->thresh, out->opened, out->labels};
-            const uint8_t *const src[6] = {dX, dS, dBil, dThr, dOpen, dLab};
-            for (int i = 0; i < 6; ++i)
-                if (dst[i]) HIPCHK(ctx, hipMemcpy2DAsync(dst[i], P, src[i] + goff[g], pitch, P, Fg, pk, s));
-            if (out->segs)
-                HIPCHK(ctx, hipMemcpy2DAsync(out->segs, (size_t)out->seg_cap * sizeof(swk_segment), dsegs + (size_t)f0 * capmax,
-                                             (size_t)capmax * sizeof(swk_segment), (size_t)out->seg_cap * sizeof(swk_segment), Fg, ok, s));
-            if (out->nseg) HIPCHK(ctx, hipMemcpyAsync(out->nseg, dnseg + f0, (size_t)Fg * 4, ok, s));
-        }
-    }
-    rc = sync(ctx);
-    if (rc) return rc;
-
-    // ---- iteration counts (sub-batch order -> call order) and the record segment_inputs_last reads ----
-    std::vector<IalmWin> hw(nwin);
-    for (int g = 0; g < G; ++g)
-        for (int wl = 0; wl < groups[g].nwin; ++wl) hw[win0[g] + wl] = hw_sub[sub_win0[sub_of[g]] + sbwin[g] + wl];
-    std::vector<int32_t> it(nwin);
-    rc = account_iters(ctx, hw, it.data(), nullptr);
-    if (rc) return rc;
-    for (int g = 0; g < G; ++g) {
-        if (!outs[g].iters) continue;
-        if (outs[g].mem == SWK_MEM_DEVICE)
-            HIPCHK(ctx, hipMemcpyAsync(outs[g].iters, it.data() + win0[g], (size_t)groups[g].nwin * 4, hipMemcpyHostToDevice, s));
-        else memcpy(outs[g].iters, it.data() + win0[g], (size_t)groups[g].nwin * 4);
-    }
-    HIPCHK(ctx, hipStreamSynchronize(s));          // `it` is a local
-    if (seg_last && want_props) {
-        swk_ctx::LastBatch &lb = ctx->last;
-        lb.frames = nullptr; lb.fs = lb.rs = 0;
-        lb.nwin = nwin; lb.n = n; lb.Hc = lb.Wc = lb.x0 = lb.y0 = lb.frame_h = lb.frame_w = 0;
-        lb.segs = dsegs; lb.nseg = dnseg; lb.cap = capmax;
-        lb.fr = (const SegFrame *)(dtab + o_sf);
-        lb.total = -1;
-        if (host_total) {
-            lb.total = 0;
-            for (int g = 0; g < G; ++g)
-                for (int f = 0; f < groups[g].nwin * n; ++f) lb.total += std::min(outs[g].nseg[f], outs[g].seg_cap);
-        }
-        lb.valid = true;
-    }
-    return SWK_OK;
+    return run_batch(ctx, groups, ngroups, p, outs);
 }
 
 // ---- stage-level entry points (host buffers) ----------------------------------------
@@ -1279,7 +1200,7 @@ int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, doub
     NEED(ctx, SL_X, elems + 4, dX);
     NEED(ctx, SL_S, elems, dS);
     HIPCHK(ctx, hipMemcpyAsync(dX, planes, elems, hipMemcpyHostToDevice, ctx->stream));
-    int rc = run_ialm(ctx, dX, 1, n, P, lmbda, tol, maxiter, A != nullptr, E != nullptr, dS, iters, nullptr);
+    int rc = run_ialm(ctx, dX, 1, n, P, lmbda, tol, maxiter, A != nullptr, E != nullptr, dS);
     if (rc) return rc;
     for (int which = 0; which < 2; ++which) {
         double *dst = which == 0 ? A : E;
@@ -1292,7 +1213,11 @@ int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, doub
     }
     rc = sync(ctx);
     if (rc) return rc;
-    return gather_iters(ctx, iters, nullptr);
+    std::vector<IalmWin> hw;
+    rc = read_windows(ctx, hw);
+    if (rc) return rc;
+    account_iters(ctx, hw, iters);
+    return SWK_OK;
 }
 
 int32_t swk_rpca_epilogue(swk_ctx *ctx, const double *E, int64_t count, uint8_t *S)

@@ -189,9 +189,11 @@ size_t ccl_words(int H, int W);
 size_t ccl_padded(int H, int W);
 
 
-// ---- several groups of windows in one call (swk_batch_run_groups) ---------------------------------------
-// A group's windows keep their own geometry; the image stages address every frame through a descriptor, and the IALM
-// runs over planes zero-padded to the batch's largest ROI (groups.hip, DESIGN section "Several videos in one call").
+// ---- several groups of windows in one call ---------------------------------------------------------------
+// swk_batch_run and swk_batch_run_groups share one driver (run_batch, swk_api.hip).  A call of one group takes the uniform
+// launchers above; a call of several takes these: a group's windows keep their own geometry, the image stages address every
+// frame through a descriptor, and the IALM runs over planes zero-padded to the call's largest ROI (groups.hip, DESIGN
+// section "Several videos in one call").
 // Gather source of one window: queue position j is the frame at src + j * fs, its ROI pixel (r, c) at
 // + (y0 + r) * rs + (x0 + c) * channels; frame j's X plane starts at off + j * pitch, pixels p >= H * W of it are zero.
 struct GroupWin {

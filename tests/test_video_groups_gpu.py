@@ -1,6 +1,6 @@
 """swk_batch_run_groups: several videos' windows, each at its own geometry, in one library call.  Every group must come out as
-swk_batch_run gives it on that group alone (u8 stages, iterations, region records; A / E to float64 summation order), and as
-the CPU oracle segments it; segment_window_groups / count_swifts_videos must count every video as count_swifts does."""
+swk_batch_run gives it on that group alone (u8 stages, iterations, region records; A / E to float64 summation order, and bit for
+bit when the call has one group), and as the CPU oracle segments it; segment_window_groups / count_swifts_videos must count every video as count_swifts does."""
 import os
 
 import numpy as np
@@ -99,7 +99,9 @@ def _check_against_lone_and_oracle(ctx, orc, specs, rois, ae):
         assert np.array_equal(res["iters"], lone["iters"]), g
         assert np.array_equal(res["nseg"], lone["nseg"]), g
         assert np.array_equal(res["segs"], lone["segs"]), g
-        if ae:
+        if ae and len(specs) == 1:          # one group: the lone run's kernels, so the same summation order
+            assert np.array_equal(res["A"], lone["A"]) and np.array_equal(res["E"], lone["E"]), g
+        elif ae:
             assert np.abs(res["A"] - lone["A"]).max() <= ATOL_AE, g
             assert np.abs(res["E"] - lone["E"]).max() <= ATOL_AE, g
         for w in range(spec["nwin"]):
@@ -117,6 +119,8 @@ def test_mixed_geometries_match_lone_runs_and_oracle(ctx, orc, ae):
     specs, rois = _mixed_groups()
     got = _check_against_lone_and_oracle(ctx, orc, specs, rois, ae)
     assert sum(int(r["nseg"].sum()) for r in got) > 20
+    for g in (0, 2):          # one group alone: host BGR frames, device gray frames
+        _check_against_lone_and_oracle(ctx, orc, specs[g:g + 1], rois[g:g + 1], ae)
 
 
 def test_windows_smaller_than_n_pixels_run_at_their_own_size(ctx, orc):
@@ -274,6 +278,11 @@ def test_errors_leave_the_context_usable(ctx, orc):
     import ctypes
     assert lib.swk_batch_run_groups(ctx._h, ins, 2, ctypes.byref(params), outs) == -1          # SWK_ERR_ARG
     assert (opened == 7).all(), "a refused call wrote output"
+    # swk_batch_run runs the same checks, the call-level limits included, before anything is launched or written
+    big = _lib.Input.from_buffer_copy(ins[0])
+    big.nwin, big.frame_stride = (1 << 24) // N + 1, 0          # more than 2^24 frames (all the same one)
+    assert lib.swk_batch_run(ctx._h, ctypes.byref(big), ctypes.byref(params), ctypes.byref(outs[0])) == -1
+    assert (opened == 7).all(), "a refused swk_batch_run wrote output"
     ins[1].n = 20
     ins[1].Hc = 8
     assert lib.swk_batch_run_groups(ctx._h, ins, 2, ctypes.byref(params), outs) == -1          # mismatched n, raw
