@@ -118,11 +118,13 @@ __global__ __launch_bounds__(kSmallThreads) void k_ialm_refine_start(IalmBuffers
         //      from the pixels.  M_1 takes one of 256 values (the start pass's expressions, image_filtering.py:272, 282-284, on the 8-bit
         //      value); 16 NB pixels at a time are tabulated into LDS, a thread owns the pairs (i >= j) tid, tid + 1024, ... ----
         const double dual = st.dual_norm, thr = st.cur.thr;
-        const uint8_t *X = b.X + (int64_t)w * n * b.P;
+        const uint8_t *X = b.X + (int64_t)w * n * b.P;          // (frames b.P apart)
+        // the window's own pixels: in a groups call the rest of b.P is zero padding, whose M_1 is exactly 0 (no part of K)
+        const int Pw = b.wpix ? b.wpix[w].P : b.P;
         const int npairs = n * (n + 1) / 2;
         // (one workgroup does it: bounded to windows where that stays in the milliseconds -- such windows are small by construction,
         //  0.008 ||X||_F < 1.8 max(X) means about 1e5 elements for a daylight sky; larger ones keep the standard route, counted)
-        if ((int64_t)b.P * ((npairs + kSmallThreads - 1) / kSmallThreads) > 400000) { if (tid == 0) st.refine = 4; return; }
+        if ((int64_t)Pw * ((npairs + kSmallThreads - 1) / kSmallThreads) > 400000) { if (tid == 0) st.refine = 4; return; }
         constexpr int MAXP = (NPAD * (NPAD + 1) / 2 + kSmallThreads - 1) / kSmallThreads;
         dd acc[MAXP];
         int pi[MAXP], pj[MAXP];
@@ -139,12 +141,12 @@ __global__ __launch_bounds__(kSmallThreads) void k_ialm_refine_start(IalmBuffers
         }
         // (CH pixels at a time: a row of the staging tile holds PITCH = 16 NB + 2 values)
         constexpr int CH = NPAD;
-        for (int p0 = 0; p0 < b.P; p0 += CH) {
+        for (int p0 = 0; p0 < Pw; p0 += CH) {
             __syncthreads();
             for (int idx = tid; idx < n * CH; idx += nthreads) {
                 const int f = idx / CH, p = p0 + (idx - f * CH);
                 double m = 0.0;
-                if (p < b.P) {
+                if (p < Pw) {
                     const double x = (double)X[(int64_t)f * b.P + p];
                     const double y = x / dual;                              // :272
                     const double raw = (x - 0.0) + inv_mu * y;              // :282 (A_0 = 0)

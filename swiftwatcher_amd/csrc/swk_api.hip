@@ -23,7 +23,7 @@ enum Slot {
     SL_ROI = 0, SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8, SL_LAB32, SL_A, SL_Y, SL_E, SL_PN,
     SL_BM, SL_VPREV, SL_GPART, SL_ZZPART, SL_WIN, SL_ACTIVE, SL_PARENT, SL_ROOTBITS, SL_WORDPREFIX,
     SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_ITERS, SL_TMP_IN, SL_TMP_OUT, SL_COLORW, SL_SPACEW,
-    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_X2, SL_REDO_S2, SL_SEGOFFS, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_COUNT
+    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_X2, SL_REDO_S2, SL_REDO_P, SL_REDO_P2, SL_SEGOFFS, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int fam; };
@@ -285,12 +285,12 @@ int host_stage_copy(swk_ctx *ctx, const swk_input *in, const HostStage &st, uint
 
 // ---- IALM driver ----------------------------------------------------------------------
 int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmbda, double tol, int maxiter,
-             bool want_A, bool want_E, uint8_t *dS, bool speculate = true, int force_variant = 0)
+             bool want_A, bool want_E, uint8_t *dS, bool speculate = true, int force_variant = 0, const PnWin *wpix = nullptr)
 {
     if (n < 1 || n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be in 1..128");
     const bool wide = n > kMaxN;          // 65 .. 128 frames: the plain f64 kernels (A/Y state, Jacobi in global memory)
     IalmBuffers b{};
-    b.X = dX; b.S = dS; b.nwin = nwin; b.n = n; b.P = P;
+    b.X = dX; b.S = dS; b.nwin = nwin; b.n = n; b.P = P; b.wpix = wpix;
     // auto: the M-state pass (k-step-templated, 21 B/element) unless the caller wants the f64 low-rank / sparse matrices,
     // which only the A/Y-state pass (v2, 34 B/element) materialises
     int variant = force_variant ? force_variant : ctx->ialm_variant;
@@ -428,7 +428,13 @@ int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmb
             NEED(ctx, kind == 0 ? SL_REDO_S : SL_REDO_S2, (size_t)cnt * wbytes, gs);
             for (int i = 0; i < cnt; ++i)
                 HIPCHK(ctx, hipMemcpyAsync(gx + (size_t)i * wbytes, dX + (size_t)list[i] * wbytes, wbytes, hipMemcpyDeviceToDevice, s));
-            const int rc1 = run_ialm(ctx, gx, cnt, n, P, lmbda, tol, maxiter, false, false, gs, false, kind == 0 ? variant : 2);
+            PnWin *gp = nullptr;          // ... and their true pixel counts
+            if (wpix) {
+                NEED(ctx, kind == 0 ? SL_REDO_P : SL_REDO_P2, (size_t)cnt * sizeof(PnWin), gp);
+                for (int i = 0; i < cnt; ++i)
+                    HIPCHK(ctx, hipMemcpyAsync(gp + i, wpix + list[i], sizeof(PnWin), hipMemcpyDeviceToDevice, s));
+            }
+            const int rc1 = run_ialm(ctx, gx, cnt, n, P, lmbda, tol, maxiter, false, false, gs, false, kind == 0 ? variant : 2, gp);
             if (rc1) return rc1;
             std::vector<IalmWin> sub(cnt);
             HIPCHK(ctx, hipMemcpyAsync(sub.data(), ctx->last_win, (size_t)cnt * sizeof(IalmWin), hipMemcpyDeviceToHost, s));
@@ -776,7 +782,9 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
     std::vector<IalmWin> hw_sub;          // window state, sub-batch order
     for (size_t k = 0; k < subs.size(); ++k) {
         const Sub &sb = subs[k];
-        rc = run_ialm(ctx, dX + sb.off, sb.nwin, n, sb.P, p->lmbda, p->tol, p->maxiter, sb.A, sb.E, dS + sb.off);
+        // (several groups: each window's own pixel count, from the scatter table, bounds the accurate first iteration's work)
+        rc = run_ialm(ctx, dX + sb.off, sb.nwin, n, sb.P, p->lmbda, p->tol, p->maxiter, sb.A, sb.E, dS + sb.off, true, 0,
+                      single ? nullptr : (const PnWin *)(dtab + o_pa) + sb.w0);
         if (rc) return rc;
         for (int which = 0; which < 2; ++which) {
             if (!(which == 0 ? sb.A : sb.E)) continue;

@@ -83,6 +83,8 @@ struct IalmWin {
                                    // double-double Gram matrix)
 };
 
+struct PnWin;
+
 struct IalmBuffers {
     const uint8_t *X;              // [nwin][n][P]
     double *A, *Y;                 // [nwin][n][P]
@@ -107,6 +109,8 @@ struct IalmBuffers {
     int nred;                      // Gram slabs the small-matrix kernel still has to sum (1 after k_gram_reduce)
     int fpad;                      // planes allocated per window in A, Y, E: n rounded up to 16
     int64_t pstride;               // plane pitch (elements) of A, Y, E: P rounded up to 16 -> 128-B aligned rows
+    const PnWin *wpix;             // optional [nwin]: window w holds wpix[w].P real pixels, the rest of its P is zero padding
+                                   // (swk_batch_run_groups); null: every window holds P
 };
 
 // ialm.hip

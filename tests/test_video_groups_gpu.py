@@ -6,11 +6,12 @@ import os
 import numpy as np
 import pytest
 
+from helpers import STAGES, roi_stack
+from helpers import gray_u8 as _gray, lone_run as _lone, check_against_lone_and_oracle as _check_against_lone_and_oracle
+
 pytestmark = pytest.mark.gpu
 
 N = 21
-ATOL_AE = 1e-5
-STAGES = ("gray", "rpca", "bilateral", "thresh", "opened", "labels")
 
 
 @pytest.fixture(scope="module")
@@ -27,24 +28,8 @@ def ctx():
     c.close()
 
 
-def _gray(bgr):
-    b, g, r = (bgr[..., k].astype(np.int32) for k in range(3))
-    return ((b * 1868 + g * 9617 + r * 4899 + (1 << 13)) >> 14).astype(np.uint8)
-
-
 def _rois(seed, nwin, Hc, Wc, null_tail=()):
-    """(nwin * n, Hc, Wc, 3) ROI frames, queue order per window; null_tail[w] = how many of window w's newest frames are null"""
-    from swiftwatcher_amd import synthetic
-    out = []
-    for w in range(nwin):
-        if Hc * Wc < 64:
-            roi = np.random.default_rng(seed + w).integers(0, 256, size=(N, Hc, Wc, 3), dtype=np.uint8)
-        else:
-            roi = synthetic.roi_window(seed + w, N, Hc, Wc, birds=3, bird_len=(6, 10), bird_wid=(3, 5))
-        k = null_tail[w] if w < len(null_tail) else 0
-        roi[:k] = 0
-        out.append(roi)
-    return np.ascontiguousarray(np.concatenate(out))
+    return roi_stack(seed, nwin, Hc, Wc, n=N, null_tail=null_tail)
 
 
 def _mixed_groups(small=False, null_tails=False):
@@ -74,44 +59,6 @@ def _mixed_groups(small=False, null_tails=False):
         specs.insert(1, dict(frames=r4, nwin=1, n=N))
         rois.insert(1, r4)
     return specs, rois
-
-
-def _lone(ctx, spec, **kw):
-    frames = spec["frames"]
-    if hasattr(frames, "cpu"):
-        frames = frames.cpu().numpy()
-    return ctx.batch_run(frames, spec["nwin"], spec["n"], crop=spec.get("crop"), reverse_frames=spec.get("reverse_frames", False), **kw)
-
-
-def _seg_tuples(res, f):
-    return [(int(s["label"]), int(s["r0"]), int(s["c0"]), int(s["r1"]), int(s["c1"]), int(s["area"]), int(s["sum_r"]), int(s["sum_c"]))
-            for s in res["segs"][f, :res["nseg"][f]]]
-
-
-def _check_against_lone_and_oracle(ctx, orc, specs, rois, ae):
-    kw = dict(want_A=True, want_E=True) if ae else {}
-    got = ctx.batch_run_groups(specs, **kw)
-    assert len(got) == len(specs)
-    for g, (spec, roi, res) in enumerate(zip(specs, rois, got)):
-        lone = _lone(ctx, spec, **kw)
-        for key in STAGES:
-            assert np.array_equal(res[key], lone[key]), "group %d: stage %s differs from a lone run" % (g, key)
-        assert np.array_equal(res["iters"], lone["iters"]), g
-        assert np.array_equal(res["nseg"], lone["nseg"]), g
-        assert np.array_equal(res["segs"], lone["segs"]), g
-        if ae and len(specs) == 1:          # one group: the lone run's kernels, so the same summation order
-            assert np.array_equal(res["A"], lone["A"]) and np.array_equal(res["E"], lone["E"]), g
-        elif ae:
-            assert np.abs(res["A"] - lone["A"]).max() <= ATOL_AE, g
-            assert np.abs(res["E"] - lone["E"]).max() <= ATOL_AE, g
-        for w in range(spec["nwin"]):
-            ref = orc.window(np.ascontiguousarray(roi[w * N:(w + 1) * N]))
-            for key in ("gray", "rpca", "opened", "labels"):
-                assert np.array_equal(res[key][w * N:(w + 1) * N], ref[key]), "group %d window %d: %s vs oracle" % (g, w, key)
-            for i in range(N):
-                exp = [(s["label"],) + s["bbox"] + (s["area"], s["sum_r"], s["sum_c"]) for s in ref["segments"][i]]
-                assert _seg_tuples(res, w * N + i) == exp, "group %d window %d frame %d" % (g, w, i)
-    return got
 
 
 @pytest.mark.parametrize("ae", [False, True], ids=["mstate", "with_A_E"])
