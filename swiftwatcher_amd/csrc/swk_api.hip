@@ -22,8 +22,8 @@ std::string g_create_error;
 enum Slot {
     SL_ROI = 0, SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8, SL_LAB32, SL_A, SL_Y, SL_E, SL_PN,
     SL_BM, SL_VPREV, SL_GPART, SL_ZZPART, SL_WIN, SL_ACTIVE, SL_PARENT, SL_ROOTBITS, SL_WORDPREFIX,
-    SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_ITERS, SL_TMP_IN, SL_TMP_OUT, SL_COLORW, SL_SPACEW,
-    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_X2, SL_REDO_S2, SL_REDO_P, SL_REDO_P2, SL_SEGOFFS, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_COUNT
+    SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_TMP_IN, SL_TMP_OUT, SL_TMP_AUX, SL_COLORW, SL_SPACEW,
+    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int fam; };
@@ -63,12 +63,8 @@ struct swk_ctx {
     double norm_spec = 256.0;      // M-state pass: ||Z|| every other iteration while above 256 x tol (<= 0: every iteration)
     int sparse_backoff = 0, norm_backoff = 0;   // batches for which a guess stays off after it failed (same video, same behaviour)
     int eig_method = 0;                  // 0 Newton-Schulz (MFMA), 1 Jacobi
-    hipEvent_t ev_poll[2] = {nullptr, nullptr};   // the host polls convergence two iterations late (run_ialm)
+    hipEvent_t ev_poll[2] = {nullptr, nullptr};   // the host polls convergence two iterations late (ialm_chain)
     std::vector<IalmWin> last_hw;        // host copy of the last batch's per-window IALM state (account_iters): diagnostics
-    IalmWin *last_win = nullptr;         // per-window IALM state of the last run
-    int last_nwin = 0;
-    int64_t pstride = 0;                 // plane pitch of the A/Y/E workspaces of the last IALM run
-    int fpad = 0;                        // planes per window in them
     // what the last batch call left on the device for swk_segment_inputs_last: its frames (SL_ROI copy of a host input,
     // or the caller's device frames) and region records; valid until a call reuses those buffers
     struct LastBatch {
@@ -284,32 +280,92 @@ int host_stage_copy(swk_ctx *ctx, const swk_input *in, const HostStage &st, uint
 }
 
 // ---- IALM driver ----------------------------------------------------------------------
-int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmbda, double tol, int maxiter,
-             bool want_A, bool want_E, uint8_t *dS, bool speculate = true, int force_variant = 0, const PnWin *wpix = nullptr)
+// Planes per window in the A / Y / E workspaces (the M-state pass pads n to its k-step, the others to 16) and their pitch: P rounded
+// up to whole groups of 8 tiles.  A window's planes must stay below 2^28 elements.
+int ialm_fpad(bool mstate, int n) { return mstate ? ialm_mstate_fpad(n) : (n + 15) & ~15; }
+int64_t ialm_pstride(int64_t P) { return (P + 127) & ~(int64_t)127; }
+
+// What one IALM chain runs, decided once from the call and the context's switches.
+struct IalmPlan {
+    int variant;           // pass kernel (launch_ialm_pass): 1, 2, 4, 5 or 6
+    bool mstate;           // the M-state pass (variants 4 / 5): no A / E; guesses and the guard band, so windows may run again
+    int fpad;              // planes per window in A, Y, E
+    int64_t pstride;       // plane pitch (elements) of A, Y, E
+    int nblk;              // blocks per window of every pass
+    bool gram8;            // the integer start may run (where gram_u8_supported allows it for the buffers)
+    double refine;         // threshold of the accurate first iteration (ialm_refine.hip); 0 = never
+    bool small_wide;       // the small-matrix step of long windows (k_ialm_small_wide) instead of k_ialm_small
+};
+
+IalmPlan plan_ialm(const swk_ctx *ctx, int n, int P, int nwin, bool want_AE, int force_variant)
 {
-    if (n < 1 || n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be in 1..128");
-    const bool wide = n > kMaxN;          // 65 .. 128 frames: the plain f64 kernels (A/Y state, Jacobi in global memory)
-    IalmBuffers b{};
-    b.X = dX; b.S = dS; b.nwin = nwin; b.n = n; b.P = P; b.wpix = wpix;
     // auto: the M-state pass (k-step-templated, 21 B/element) unless the caller wants the f64 low-rank / sparse matrices,
-    // which only the A/Y-state pass (v2, 34 B/element) materialises
+    // which only the A/Y-state pass (v2, 34 B/element) materialises; 65 .. 128 frames: the plain f64 kernels (A/Y state, Jacobi in
+    // global memory)
     int variant = force_variant ? force_variant : ctx->ialm_variant;
     if (variant == 0) variant = 4;
-    if (variant >= 4 && variant != 6 && (want_A || want_E)) variant = 2;
-    if (wide) variant = 6;
-    const bool mstate = variant == 4 || variant == 5;          // the M-state pass (ialm_mstate.hip), with / without the software pipeline
-    b.nblk = ialm_pass_nblk(variant, n, P, nwin);   // blocks per window, sized per launch
+    if (variant >= 4 && variant != 6 && want_AE) variant = 2;
+    if (n > kMaxN) variant = 6;
+    IalmPlan pl{};
+    pl.variant = variant;
+    pl.mstate = variant == 4 || variant == 5;
+    pl.fpad = ialm_fpad(pl.mstate, n);
+    pl.pstride = ialm_pstride(P);
+    pl.nblk = ialm_pass_nblk(variant, n, P, nwin);
+    pl.gram8 = (pl.mstate || variant == 2 || variant == 1) && ctx->use_gram8;
+    pl.refine = n > kMaxN ? 0.0 : ctx->start_refine;          // (by the window length: a forced variant 6 below 65 frames refines)
+    pl.small_wide = variant == 6;
+    return pl;
+}
+
+// One IALM call's windows: nwin windows of n frames x P pixels side by side in X; their sparse images go to S.
+struct IalmJob {
+    const uint8_t *X;
+    uint8_t *S;
+    int nwin, n, P;
+    const PnWin *wpix;          // each window's true pixel count (several groups: the rest of its P is zero padding); null: P
+    double lmbda, tol;
+    int maxiter;
+};
+
+// What run_ialm leaves on the device for its caller: the final per-window state and the A / E workspaces (when asked for).
+struct IalmRun {
+    IalmWin *win;
+    int nwin;
+    int64_t pstride;
+    int fpad;
+    const double *A, *E;
+};
+
+// Copies the per-window IALM state of nwin windows to the host (waits for it).
+int copy_windows(swk_ctx *ctx, const IalmWin *win, int nwin, IalmWin *dst)
+{
+    // (on the context's own, non-blocking stream: a copy on the null stream would wait for every blocking stream of the process, and
+    //  fails outright while another thread captures a HIP graph on one -- the classifier does, segment_classification.py)
+    HIPCHK(ctx, hipMemcpyAsync(dst, win, (size_t)nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return SWK_OK;
+}
+
+// One chain over the job's windows on the context's stream: start, then per iteration pass -> (slab sum) -> small-matrix step, until
+// every window has stopped.  speculate: the M-state pass may guess (sparse-image stores and stopping norms skipped far from the
+// tolerance).  *bp describes the buffers the chain worked in.
+int ialm_chain(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want_A, bool want_E, bool speculate, IalmBuffers *bp)
+{
+    const int nwin = job.nwin, n = job.n, P = job.P;
+    IalmBuffers &b = *bp;
+    b = IalmBuffers{};
+    b.X = job.X; b.S = job.S; b.nwin = nwin; b.n = n; b.P = P; b.wpix = job.wpix;
+    b.nblk = plan.nblk;
     b.nred = b.nblk > 4 ? 1 : b.nblk;       // several slabs: reduce them chip-wide first (k_gram_reduce)
-    b.pstride = ((int64_t)P + 127) & ~(int64_t)127;      // whole groups of 8 tiles
-    b.fpad = mstate ? ialm_mstate_fpad(n) : (n + 15) & ~15;
-    ctx->pstride = b.pstride;
-    ctx->fpad = b.fpad;
+    b.pstride = plan.pstride;
+    b.fpad = plan.fpad;
     if ((int64_t)b.fpad * b.pstride >= (1ll << 28)) return fail(ctx, SWK_ERR_ARG, "window too large: frames x ROI pixels must stay below 2^28");
     const size_t elems = (size_t)nwin * n * P;
     const size_t felems = (size_t)nwin * b.fpad * b.pstride;
     NEED(ctx, SL_A, felems * 8, b.A);
     NEED(ctx, SL_Y, felems * 8, b.Y);
-    if (mstate) {
+    if (plan.mstate) {
         b.U = (uint16_t *)b.Y;               // binary16 planes in the Y slot
         b.spec = (speculate && ctx->sparse_backoff == 0) ? ctx->sparse_spec : 0.0;
         b.nspec = (speculate && ctx->norm_backoff == 0) ? ctx->norm_spec : 0.0;
@@ -328,12 +384,12 @@ int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmb
     NEED(ctx, SL_WIN, (size_t)nwin * sizeof(IalmWin), b.win);
     NEED(ctx, SL_ACTIVE, 16 * sizeof(int), b.active);
     double *wide_work = nullptr;
-    if (variant == 6) NEED(ctx, SL_WIDE, (size_t)nwin * ialm_small_wide_doubles(n) * sizeof(double), wide_work);
+    if (plan.small_wide) NEED(ctx, SL_WIDE, (size_t)nwin * ialm_small_wide_doubles(n) * sizeof(double), wide_work);
     hipStream_t s = ctx->stream;
     HIPCHK(ctx, hipMemsetAsync(b.win, 0, (size_t)nwin * sizeof(IalmWin), s));
     HIPCHK(ctx, hipMemsetAsync(b.active, 0, 16 * sizeof(int), s));
-    HIPCHK(ctx, hipMemsetAsync(dS, 0, elems, s));
-    if (mstate) {
+    HIPCHK(ctx, hipMemsetAsync(b.S, 0, elems, s));
+    if (plan.mstate) {
         HIPCHK(ctx, hipMemsetAsync(b.Salt, 0, elems, s));
     } else {
         // a window that stops before writing A (all-zero input) must still read back zeros
@@ -343,26 +399,25 @@ int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmb
     }
     if (want_E) HIPCHK(ctx, hipMemsetAsync(b.E, 0, felems * 8, s));
 
-    // One chain on the context's stream: start, then per iteration pass -> (slab sum) -> small-matrix step.  (Rounds 1 / 2 cut the
-    // batch into window groups whose eigen-solves ran on CU-masked side streams beside the other groups' passes; with the
-    // Newton-Schulz solver the small-matrix kernel is ~3 % of a step and the overlap stopped paying: removed in round 3.)
     int rc = ensure_poll_events(ctx);
     if (rc) return rc;
     const int check_from = 6;     // no window converges earlier (mu grows 1.5x per iteration)
+    const double lmbda = job.lmbda, tol = job.tol;
+    const int maxiter = job.maxiter;
     // window statistics (||X||_F, max) and, for the M-state pass, the first Gram matrix in the same read of X
     // on the integer matrix cores; windows it does not cover get the f64 start pass below
-    b.use_gram8 = ((mstate || variant == 2 || variant == 1) && ctx->use_gram8 && gram_u8_supported(b)) ? 1 : 0;
-    b.refine = wide ? 0.0 : ctx->start_refine;
+    b.use_gram8 = (plan.gram8 && gram_u8_supported(b)) ? 1 : 0;
+    b.refine = plan.refine;
     { Timed t(ctx, SWK_K_IALM_STATS);
       if (b.use_gram8) launch_gram_u8(s, b); else launch_ialm_stats(s, b);
       launch_ialm_init(s, b, lmbda); }
     // the Gram-only start pass reads X alone (1 B/element): booked with the statistics family so
     // SWK_K_IALM_PASS times only the full streaming passes
-    { Timed t(ctx, SWK_K_IALM_STATS); launch_ialm_pass(s, b, 0, variant, 0, ctx->pass_tune); }
+    { Timed t(ctx, SWK_K_IALM_STATS); launch_ialm_pass(s, b, 0, plan.variant, 0, ctx->pass_tune); }
     auto small_step = [&](int k) {
         Timed t(ctx, SWK_K_IALM_SMALL);
         if (b.nblk > 4) launch_gram_reduce(s, b);
-        if (variant == 6) launch_ialm_small_wide(s, b, k, lmbda, tol, maxiter, wide_work);
+        if (plan.small_wide) launch_ialm_small_wide(s, b, k, lmbda, tol, maxiter, wide_work);
         else launch_ialm_small(s, b, k, lmbda, tol, maxiter, ctx->eig_method);
     };
     small_step(0);
@@ -379,99 +434,113 @@ int run_ialm(swk_ctx *ctx, const uint8_t *dX, int nwin, int n, int P, double lmb
             if (ctx->h_active[kc & 1] <= 0) break;
         }
         if (k > maxiter) break;
-        { Timed t(ctx, SWK_K_IALM_PASS); launch_ialm_pass(s, b, k == 1 ? 1 : 2, variant, k, ctx->pass_tune); }
+        { Timed t(ctx, SWK_K_IALM_PASS); launch_ialm_pass(s, b, k == 1 ? 1 : 2, plan.variant, k, ctx->pass_tune); }
         small_step(k);
         if (k >= check_from) {
             HIPCHK(ctx, hipMemcpyAsync(&ctx->h_active[k & 1], b.active, sizeof(int), hipMemcpyDeviceToHost, s));
             HIPCHK(ctx, hipEventRecord(ctx->ev_poll[k & 1], s));
         }
     }
-    if (mstate) { Timed t(ctx, SWK_K_IALM_STATS); launch_select_sparse(s, b); }
-    ctx->last_win = b.win;
-    ctx->last_nwin = nwin;
-    if (mstate && (b.spec > 0.0 || b.nspec > 0.0 || b.guard > 0.0)) {
-        // Windows the M-state pass could not finish on its own terms (IalmWin::redo): bits 0 / 1 = a guess failed (the window stopped
-        // right after a pass that had its sparse-image stores switched off, or a partial norm could not rule out that an iteration
-        // was the last); bit 2 = the float32 stopping norm fell inside the guard band around the tolerance.  Only THOSE windows run
-        // again -- the first kind together, in one call with the guesses off; the second kind through the A/Y-state pass (norm in
-        // float64, statement by statement the reference's :293-297) -- and their sparse images, iteration counts and diagnostics
-        // replace the windows' entries.  (Until round 3 one failed guess reran the whole batch.)
-        std::vector<IalmWin> hw(nwin);
-        HIPCHK(ctx, hipMemcpyAsync(hw.data(), b.win, (size_t)nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        std::vector<int> guess, band;
-        int redo = 0;
-        for (int w = 0; w < nwin; ++w) {
-            redo |= hw[w].redo;
-            if (hw[w].redo & 3) guess.push_back(w);
-            else if (hw[w].redo & 4) band.push_back(w);
-        }
-        if (redo & 3) {
-            // windows of one video behave alike: a guess that failed stays off for the next batches
-            ctx->redo_batches += 1;
-            ctx->redo_windows += (int64_t)guess.size();
-            if (redo & 1) ctx->sparse_backoff = 64;
-            if (redo & 2) ctx->norm_backoff = 64;
-        }
-        ctx->guard_windows += (int64_t)band.size();
-        const int64_t pstride = ctx->pstride;
-        const int fpad = ctx->fpad;
-        for (int kind = 0; kind < 2; ++kind) {
-            const std::vector<int> &list = kind == 0 ? guess : band;
-            if (list.empty()) continue;
-            const int cnt = (int)list.size();
-            const size_t wbytes = (size_t)n * P;
-            // the listed windows side by side: their pixels gathered, their sparse images scattered back
-            // (a slot pair per kind: the run of the first kind may itself send windows of ITS batch through the second)
-            uint8_t *gx, *gs;
-            NEED(ctx, kind == 0 ? SL_REDO_X : SL_REDO_X2, (size_t)cnt * wbytes + 4, gx);
-            NEED(ctx, kind == 0 ? SL_REDO_S : SL_REDO_S2, (size_t)cnt * wbytes, gs);
-            for (int i = 0; i < cnt; ++i)
-                HIPCHK(ctx, hipMemcpyAsync(gx + (size_t)i * wbytes, dX + (size_t)list[i] * wbytes, wbytes, hipMemcpyDeviceToDevice, s));
-            PnWin *gp = nullptr;          // ... and their true pixel counts
-            if (wpix) {
-                NEED(ctx, kind == 0 ? SL_REDO_P : SL_REDO_P2, (size_t)cnt * sizeof(PnWin), gp);
-                for (int i = 0; i < cnt; ++i)
-                    HIPCHK(ctx, hipMemcpyAsync(gp + i, wpix + list[i], sizeof(PnWin), hipMemcpyDeviceToDevice, s));
-            }
-            const int rc1 = run_ialm(ctx, gx, cnt, n, P, lmbda, tol, maxiter, false, false, gs, false, kind == 0 ? variant : 2, gp);
-            if (rc1) return rc1;
-            std::vector<IalmWin> sub(cnt);
-            HIPCHK(ctx, hipMemcpyAsync(sub.data(), ctx->last_win, (size_t)cnt * sizeof(IalmWin), hipMemcpyDeviceToHost, s));
-            for (int i = 0; i < cnt; ++i)
-                HIPCHK(ctx, hipMemcpyAsync(dS + (size_t)list[i] * wbytes, gs + (size_t)i * wbytes, wbytes, hipMemcpyDeviceToDevice, s));
-            HIPCHK(ctx, hipStreamSynchronize(s));
-            for (int i = 0; i < cnt; ++i) {
-                IalmWin one = sub[i];
-                one.pass_b16 += hw[list[i]].pass_b16;          // the roofline books every pass a window ran, the abandoned ones included
-                hw[list[i]] = one;
-            }
-        }
-        if (!guess.empty() || !band.empty()) {
-            // the nested runs used the window-state slot and the A / Y workspaces for their own (smaller) batches: this batch's
-            // entries go back, and the context describes THIS batch again
-            NEED(ctx, SL_WIN, (size_t)nwin * sizeof(IalmWin), b.win);
-            HIPCHK(ctx, hipMemcpyAsync(b.win, hw.data(), (size_t)nwin * sizeof(IalmWin), hipMemcpyHostToDevice, s));
-            HIPCHK(ctx, hipStreamSynchronize(s));
-            ctx->pstride = pstride;
-            ctx->fpad = fpad;
-            ctx->last_win = b.win;
-            ctx->last_nwin = nwin;
-        }
+    if (plan.mstate) { Timed t(ctx, SWK_K_IALM_STATS); launch_select_sparse(s, b); }
+    return SWK_OK;
+}
+
+// Runs the job's windows `list` again, side by side as a chain of their own through `variant`, with the guesses off: their pixels
+// (and pixel counts) gathered into the rerun slots, their sparse images scattered back into the job's S, their final state into
+// hw[list[i]] (pass_b16 keeps counting the abandoned passes).  band (optional): the windows of `list` that chain sent to the guard band.
+int rerun_windows(swk_ctx *ctx, const IalmJob &job, const std::vector<int> &list, int variant, std::vector<IalmWin> &hw,
+                  std::vector<int> *band)
+{
+    hipStream_t s = ctx->stream;
+    const int cnt = (int)list.size();
+    const size_t wbytes = (size_t)job.n * job.P;
+    IalmJob sub = job;
+    sub.nwin = cnt;
+    uint8_t *gx, *gs;
+    NEED(ctx, SL_REDO_X, (size_t)cnt * wbytes + 4, gx);
+    NEED(ctx, SL_REDO_S, (size_t)cnt * wbytes, gs);
+    for (int i = 0; i < cnt; ++i)
+        HIPCHK(ctx, hipMemcpyAsync(gx + (size_t)i * wbytes, job.X + (size_t)list[i] * wbytes, wbytes, hipMemcpyDeviceToDevice, s));
+    PnWin *gp = nullptr;
+    if (job.wpix) {
+        NEED(ctx, SL_REDO_P, (size_t)cnt * sizeof(PnWin), gp);
+        for (int i = 0; i < cnt; ++i)
+            HIPCHK(ctx, hipMemcpyAsync(gp + i, job.wpix + list[i], sizeof(PnWin), hipMemcpyDeviceToDevice, s));
+    }
+    sub.X = gx; sub.S = gs; sub.wpix = gp;
+    IalmBuffers b;
+    int rc = ialm_chain(ctx, sub, plan_ialm(ctx, job.n, job.P, cnt, false, variant), false, false, false, &b);
+    if (rc) return rc;
+    for (int i = 0; i < cnt; ++i)
+        HIPCHK(ctx, hipMemcpyAsync(job.S + (size_t)list[i] * wbytes, gs + (size_t)i * wbytes, wbytes, hipMemcpyDeviceToDevice, s));
+    std::vector<IalmWin> sw(cnt);
+    if ((rc = copy_windows(ctx, b.win, cnt, sw.data()))) return rc;
+    if (band) band->clear();
+    for (int i = 0; i < cnt; ++i) {
+        if (band && (sw[i].redo & 4)) band->push_back(list[i]);
+        sw[i].pass_b16 += hw[list[i]].pass_b16;          // the roofline books every pass a window ran, the abandoned ones included
+        hw[list[i]] = sw[i];
     }
     return SWK_OK;
 }
 
-// Appends the per-window IALM state of the last run_ialm to hw (waits for it).
-int read_windows(swk_ctx *ctx, std::vector<IalmWin> &hw)
+// The IALM over the job's windows: one chain, then the chains that finish the windows the M-state pass could not finish on its own
+// terms (IalmWin::redo): bits 0 / 1 = a guess failed (the window stopped right after a pass that had its sparse-image stores
+// switched off, or a partial norm could not rule out that an iteration was the last); bit 2 = the float32 stopping norm fell inside
+// the guard band around the tolerance.  Only those windows run again, in this order, each list as a chain of its own (the batch size
+// sets nblk and with it the summation order, so the lists are not merged):
+//   1. the windows whose guess failed, with the guesses off (the guard band stays);
+//   2. those of them that this rerun sent to the guard band, through the A/Y-state pass (norm in float64, statement by statement the
+//      reference's :293-297);
+//   3. the windows the first chain sent to the guard band, the same way.
+// A rerun makes no guesses, so it cannot set bits 0 / 1, and the A/Y-state pass has no guard band: no rerun needs one of its own.
+// The reruns' sparse images, iteration counts and diagnostics replace the windows' entries.
+int run_ialm(swk_ctx *ctx, const IalmJob &job, bool want_A, bool want_E, IalmRun *run)
+{
+    const int nwin = job.nwin;
+    if (job.n < 1 || job.n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be in 1..128");
+    const IalmPlan plan = plan_ialm(ctx, job.n, job.P, nwin, want_A || want_E, 0);
+    IalmBuffers b;
+    int rc = ialm_chain(ctx, job, plan, want_A, want_E, true, &b);
+    if (rc) return rc;
+    *run = IalmRun{b.win, nwin, b.pstride, b.fpad, want_A ? b.A : nullptr, b.E};          // (reruns follow M-state chains: no A / E)
+    if (!plan.mstate || !(b.spec > 0.0 || b.nspec > 0.0 || b.guard > 0.0)) return SWK_OK;
+    std::vector<IalmWin> hw(nwin);
+    if ((rc = copy_windows(ctx, b.win, nwin, hw.data()))) return rc;
+    std::vector<int> guess, band, guess_band;
+    int redo = 0;
+    for (int w = 0; w < nwin; ++w) {
+        redo |= hw[w].redo;
+        if (hw[w].redo & 3) guess.push_back(w);
+        else if (hw[w].redo & 4) band.push_back(w);
+    }
+    if (redo & 3) {
+        // windows of one video behave alike: a guess that failed stays off for the next batches
+        ctx->redo_batches += 1;
+        ctx->redo_windows += (int64_t)guess.size();
+        if (redo & 1) ctx->sparse_backoff = 64;
+        if (redo & 2) ctx->norm_backoff = 64;
+    }
+    ctx->guard_windows += (int64_t)band.size();
+    if (!guess.empty() && (rc = rerun_windows(ctx, job, guess, plan.variant, hw, &guess_band))) return rc;
+    ctx->guard_windows += (int64_t)guess_band.size();
+    if (!guess_band.empty() && (rc = rerun_windows(ctx, job, guess_band, 2, hw, nullptr))) return rc;
+    if (!band.empty() && (rc = rerun_windows(ctx, job, band, 2, hw, nullptr))) return rc;
+    if (!guess.empty() || !band.empty()) {
+        // the reruns used the window-state slot for their own (smaller) batches: this batch's entries go back
+        NEED(ctx, SL_WIN, (size_t)nwin * sizeof(IalmWin), run->win);
+        HIPCHK(ctx, hipMemcpyAsync(run->win, hw.data(), (size_t)nwin * sizeof(IalmWin), hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return SWK_OK;
+}
+
+// Appends the per-window IALM state of a run to hw (waits for it).
+int read_windows(swk_ctx *ctx, const IalmRun &run, std::vector<IalmWin> &hw)
 {
     const size_t w0 = hw.size();
-    hw.resize(w0 + ctx->last_nwin);
-    // (on the context's own, non-blocking stream: a copy on the null stream would wait for every blocking stream of the process, and
-    //  fails outright while another thread captures a HIP graph on one -- the classifier does, segment_classification.py)
-    HIPCHK(ctx, hipMemcpyAsync(hw.data() + w0, ctx->last_win, (size_t)ctx->last_nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    return SWK_OK;
+    hw.resize(w0 + run.nwin);
+    return copy_windows(ctx, run.win, run.nwin, hw.data() + w0);
 }
 
 // Books the per-window IALM state of a call (counters, diagnostics) and hands out its iteration counts (host, optional).
@@ -588,14 +657,14 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
     std::vector<int> sub_of(G);
     for (size_t k = 0; k < subs.size(); ++k)
         for (int g : subs[k].gs) sub_of[g] = (int)k;
-    // capacity: run_ialm's limit on the padded plane (at the widest fpad, which its reruns may take), checked here so that a refused
-    // call launches nothing
-    const int fpad_max = std::max(ialm_mstate_fpad(n), (n + 15) & ~15);
+    // capacity: run_ialm's limit on the padded plane (at the wider fpad of the two pass families: its reruns may take the other),
+    // checked here so that a refused call launches nothing
+    const int fpad_max = std::max(ialm_fpad(true, n), ialm_fpad(false, n));
     size_t total = 0;                     // stage-plane bytes: sub-batches one after the other, each 256-byte aligned
     int sub_first = 0;                    // windows in sub-batch order
     for (Sub &sb : subs) {
         Pmax = sb.P > Pmax ? sb.P : Pmax;
-        if ((int64_t)fpad_max * (((int64_t)sb.P + 127) & ~(int64_t)127) >= (1ll << 28))
+        if ((int64_t)fpad_max * ialm_pstride(sb.P) >= (1ll << 28))
             return fail(ctx, SWK_ERR_ARG, "window too large: frames x padded ROI pixels must stay below 2^28");
         sb.off = (int64_t)total;
         total += ((size_t)sb.nwin * n * sb.P + 255) & ~(size_t)255;
@@ -780,20 +849,22 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
 
     // ---- IALM per sub-batch; its float64 factors leave before the next sub-batch reuses the workspaces ----
     std::vector<IalmWin> hw_sub;          // window state, sub-batch order
+    IalmRun run{};
     for (size_t k = 0; k < subs.size(); ++k) {
         const Sub &sb = subs[k];
         // (several groups: each window's own pixel count, from the scatter table, bounds the accurate first iteration's work)
-        rc = run_ialm(ctx, dX + sb.off, sb.nwin, n, sb.P, p->lmbda, p->tol, p->maxiter, sb.A, sb.E, dS + sb.off, true, 0,
-                      single ? nullptr : (const PnWin *)(dtab + o_pa) + sb.w0);
+        const IalmJob job{dX + sb.off, dS + sb.off, sb.nwin, n, sb.P, single ? nullptr : (const PnWin *)(dtab + o_pa) + sb.w0,
+                          p->lmbda, p->tol, p->maxiter};
+        rc = run_ialm(ctx, job, sb.A, sb.E, &run);
         if (rc) return rc;
         for (int which = 0; which < 2; ++which) {
             if (!(which == 0 ? sb.A : sb.E)) continue;
-            const double *planes = (const double *)ctx->slot[which == 0 ? SL_A : SL_E];
+            const double *planes = which == 0 ? run.A : run.E;
             {
                 Timed t(ctx, SWK_K_COPY);
-                if (single) launch_planes_to_pn(s, planes, ae_dst(0, which), sb.nwin, n, sb.P, ctx->pstride, ctx->fpad);
+                if (single) launch_planes_to_pn(s, planes, ae_dst(0, which), sb.nwin, n, sb.P, run.pstride, run.fpad);
                 else launch_planes_to_pn_groups(s, planes, (const PnWin *)(dtab + (which == 0 ? o_pa : o_pe)) + sb.w0, sb.nwin, n,
-                                                sb.P, ctx->pstride, ctx->fpad);
+                                                sb.P, run.pstride, run.fpad);
             }
             for (int g : sb.gs) {
                 double *dst = which == 0 ? outs[g].A : outs[g].E;
@@ -804,7 +875,7 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
         }
         // the next sub-batch reuses the window-state slot: this one's state is read now (the last one's after the final sync)
         if (k + 1 < subs.size()) {
-            rc = read_windows(ctx, hw_sub);
+            rc = read_windows(ctx, run, hw_sub);
             if (rc) return rc;
         }
     }
@@ -866,7 +937,7 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
     if (rc) return rc;
 
     // ---- iteration counts (sub-batch order -> call order) and the record swk_segment_inputs_last reads ----
-    rc = read_windows(ctx, hw_sub);
+    rc = read_windows(ctx, run, hw_sub);
     if (rc) return rc;
     std::vector<IalmWin> hw(nwin);
     for (int g = 0; g < G; ++g)
@@ -957,7 +1028,7 @@ int32_t swk_ctx_create(int32_t device, int32_t max_windows, int32_t max_n, int32
         rc = rc ? rc : need(ctx, SL_S, elems, &p);
         rc = rc ? rc : need(ctx, SL_OPEN, elems, &p);
         rc = rc ? rc : need(ctx, SL_LAB8, elems, &p);
-        const size_t felems = (size_t)max_windows * ((max_n + 15) & ~15) * (((size_t)max_Hc * max_Wc + 127) & ~(size_t)127);
+        const size_t felems = (size_t)max_windows * ialm_fpad(false, max_n) * ialm_pstride((int64_t)max_Hc * max_Wc);
         rc = rc ? rc : need(ctx, SL_A, felems * 8, &p);
         rc = rc ? rc : need(ctx, SL_Y, felems * 8, &p);
         if (rc) { g_create_error = ctx->err; swk_ctx_destroy(ctx); return rc; }
@@ -1208,21 +1279,22 @@ int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, doub
     NEED(ctx, SL_X, elems + 4, dX);
     NEED(ctx, SL_S, elems, dS);
     HIPCHK(ctx, hipMemcpyAsync(dX, planes, elems, hipMemcpyHostToDevice, ctx->stream));
-    int rc = run_ialm(ctx, dX, 1, n, P, lmbda, tol, maxiter, A != nullptr, E != nullptr, dS);
+    IalmRun run{};
+    int rc = run_ialm(ctx, IalmJob{dX, dS, 1, n, P, nullptr, lmbda, tol, maxiter}, A != nullptr, E != nullptr, &run);
     if (rc) return rc;
     for (int which = 0; which < 2; ++which) {
         double *dst = which == 0 ? A : E;
         if (!dst) continue;
         double *pn;
         NEED(ctx, SL_PN, elems * 8, pn);
-        launch_planes_to_pn(ctx->stream, (const double *)ctx->slot[which == 0 ? SL_A : SL_E], pn, 1, n, P, ctx->pstride, ctx->fpad);
+        launch_planes_to_pn(ctx->stream, which == 0 ? run.A : run.E, pn, 1, n, P, run.pstride, run.fpad);
         HIPCHK(ctx, hipMemcpyAsync(dst, pn, elems * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     }
     rc = sync(ctx);
     if (rc) return rc;
     std::vector<IalmWin> hw;
-    rc = read_windows(ctx, hw);
+    rc = read_windows(ctx, run, hw);
     if (rc) return rc;
     account_iters(ctx, hw, iters);
     return SWK_OK;
@@ -1293,7 +1365,7 @@ int32_t swk_grey_open_u8(swk_ctx *ctx, const uint8_t *src, int32_t count, int32_
     uint8_t *din, *dout, *dtmp;
     NEED(ctx, SL_TMP_IN, px, din);
     NEED(ctx, SL_TMP_OUT, px, dout);
-    NEED(ctx, SL_REDO_S2, px, dtmp);          // (a scratch plane: the rerun slots are idle outside run_ialm)
+    NEED(ctx, SL_TMP_AUX, px, dtmp);
     HIPCHK(ctx, hipMemcpyAsync(din, src, px, hipMemcpyHostToDevice, ctx->stream));
     launch_grey_open(ctx->stream, din, count, H, W, kh, kw, dtmp, dout);
     HIPCHK(ctx, hipMemcpyAsync(dst, dout, px, hipMemcpyDeviceToHost, ctx->stream));
@@ -1329,7 +1401,7 @@ int32_t swk_resize_linear_u8(swk_ctx *ctx, const uint8_t *src, int32_t count, in
     int *dix; short *dw;
     NEED(ctx, SL_TMP_IN, in_b, din);
     NEED(ctx, SL_TMP_OUT, out_b, dout);
-    NEED(ctx, SL_REDO_S2, idx.size() * 4 + wts.size() * 2, dix);
+    NEED(ctx, SL_TMP_AUX, idx.size() * 4 + wts.size() * 2, dix);
     dw = (short *)(dix + idx.size());
     HIPCHK(ctx, hipMemcpyAsync(din, src, in_b, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(dix, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, ctx->stream));

@@ -9,7 +9,7 @@
 namespace swk {
 
 constexpr int kMaxN = 64;          // frames per window supported by the matrix-core IALM kernels
-constexpr int kMaxNWide = 128;     // ... and by the plain f64 kernels that take over above that (k_ialm_pass_wide, k_ialm_small_wide)
+constexpr int kMaxNWide = 128;     // ... and by the plain f64 kernels that take over above that (k_ialm_pass_lds<4>, k_ialm_small_wide)
 
 // Kernels that take more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize, and the attribute
 // belongs to the (kernel, device) pair: `mask` (one static per kernel instantiation) keeps a bit per device it has been

@@ -103,7 +103,7 @@ def main():
     alt.set_start_refine(1e-12)
     # "--rotate": two more contexts take turns -- the Jacobi solver under the A/Y-state pass, and guesses that fail on purpose (the
     # stores of the sparse image start late, the stopping norm is formed every other iteration to the end, a guard band of 5 %): the
-    # per-window rerun paths of run_ialm (nested calls, gathered windows) get random windows and random batch sizes
+    # per-window rerun paths of run_ialm (follow-up chains over gathered windows) get random windows and random batch sizes
     rotate = "--rotate" in sys.argv
     jac = _lib.Context(0)
     jac.set_eig_method(1)

@@ -389,7 +389,7 @@ def test_only_the_windows_whose_guess_failed_run_again(orc):
     (swk_set_sparse_speculation); the answer is the image the pass BEFORE the last wrote, so a window fails the guess when its ratio two
     iterations before the end was still above the factor.  The reference's ratios there (numpy, tol units): 1.72-1.76 for the one kind
     (23 iterations), 2.47-2.55 for the other (22: 12 large birds, noisy sensor) -- with a factor of 2.1 exactly the second kind fails.
-    Those four windows -- and only those -- run again (one nested call, guesses off); every window's iteration count, sparse image,
+    Those four windows -- and only those -- run again (one chain of their own, guesses off); every window's iteration count, sparse image,
     labels and region records are the oracle's, the untouched windows' included."""
     from swiftwatcher_amd import _lib, synthetic
     n, Hc, Wc, nwin = 21, 64, 96, 8
@@ -502,7 +502,13 @@ def test_stopping_decision_guard_band(orc):
     window whose ratio ||Z|| / (tol ||X||) lands within the guard band of 1 (default 1e-3) is not decided on that number: it is
     run again by the A/Y-state pass, which forms the norm in float64 like the reference (image_filtering.py:293-297).  Forced here
     with a band of 0.9 (every window's stopping iteration falls inside): outputs and iteration counts are unchanged, and the
-    reruns are counted."""
+    reruns are counted.
+
+    Then a failed guess whose rerun lands in the guard band.  The norm speculation stays on to the end (factor 1e-9: the full norm is
+    formed every other iteration), so a window whose ratio first comes within the band on an unformed iteration fails its guess, and
+    one where that happens on a formed iteration goes to the band directly.  The rerun forms every norm, so it stops in the band as
+    well.  Every window is thus counted in the band exactly once, by the first chain or by its rerun: guard_windows == nwin together
+    with redo_windows >= 1 proves that at least one window went from a failed guess to the guard band and through the A/Y-state pass."""
     from swiftwatcher_amd import synthetic, _lib
     ctx = _lib.Context(0)                        # the default (M-state) pass; the parametrised fixture runs the A/Y-state kernels
     n, Hc, Wc = 21, 64, 96
@@ -527,6 +533,20 @@ def test_stopping_decision_guard_band(orc):
     before = ctx.guard_windows
     ctx.batch_run(many, 24, n, stages=())
     assert ctx.guard_windows - before <= 3
+    ctx.close()
+    # a failed guess, then the guard band (docstring)
+    nwin = 6
+    roi = np.concatenate([synthetic.roi_window(2100 + w, n, Hc, Wc, birds=3, bird_len=(8, 14), bird_wid=(3, 6)) for w in range(nwin)])
+    ctx = _lib.Context(0)
+    ctx.set_norm_speculation(1e-9)
+    ctx.set_norm_guard(0.9)
+    res = ctx.batch_run(roi, nwin, n, stages=("rpca", "labels"))
+    assert ctx.guard_windows == nwin and ctx.redo_windows >= 1, (ctx.guard_windows, ctx.redo_windows)
+    for w in range(nwin):
+        ref = orc.window(np.ascontiguousarray(roi[w * n:(w + 1) * n]))
+        assert int(res["iters"][w]) == ref["iters"], w
+        np.testing.assert_array_equal(res["rpca"][w * n:(w + 1) * n], ref["rpca"], err_msg="window %d" % w)
+        np.testing.assert_array_equal(res["labels"][w * n:(w + 1) * n], ref["labels"], err_msg="window %d" % w)
     ctx.close()
 
 
@@ -915,7 +935,7 @@ def test_roi_at_the_frame_corner_and_gray_frames(orc):
 
 def test_windows_of_more_than_64_frames(orc):
     """FrameQueue(queue_size) is free in the reference (data_structures.py:120).  Up to 64 frames the matrix-core kernels run; 65 .. 128
-    frames take the plain float64 kernels (k_ialm_pass_wide: variant 1 with four waves per tile; k_ialm_small_wide: cyclic Jacobi with
+    frames take the plain float64 kernels (k_ialm_pass_lds<4>: variant 1 with four waves per tile; k_ialm_small_wide: cyclic Jacobi with
     its matrices in global memory).  (a) below 65 frames the wide kernels agree with variant 1 + Jacobi: same iteration count, same u8
     image, A and E to the last bits (only the order of the stopping norm's sum differs); (b) windows of 65, 96 and 128 frames against
     the oracle: every stage image, the region records, A and E within 1e-5; (c) the drop-in: FrameQueue(queue_size=96)."""
