@@ -330,6 +330,17 @@ int32_t swk_nhwc_conv3x3_winograd_bias_relu_place(void *stream, const float *src
                                                   const float *bias, int32_t cout, float *dst, int32_t dH, int32_t dW, int32_t dC,
                                                   int32_t off_y, int32_t off_x, int32_t c_off);
 
+/* The same F(2x2, 3x3) convolution with every float32 product formed as six bf16 x bf16 matrix-core products of three-way split
+ * operands (float32-accurate; csrc/cnn_wino3x3_bf16s.hip), for the Fire shapes cin = cout / 4 in {16, 32, 48, 64}; other shapes are
+ * refused (SWK_ERR_ARG).  Same arguments and contract as swk_nhwc_conv3x3_winograd_bias_relu_place, but weight_s = the split filter
+ * transform made by swk_winograd_f2x2_3x3_weights_bf16s (host code): U = G g G^T in float64, rounded to float32 (the values
+ * swk_winograd_f2x2_3x3_weights makes), each split exactly into u1 + u2 + u3 of three round-to-nearest-even bf16 parts, into
+ * out[3 * 16 * cin * 32 * ceil(cout / 32)] bf16 bit patterns laid out as the matrix cores' A operands.  weight_s 16-byte aligned. */
+int32_t swk_winograd_f2x2_3x3_weights_bf16s(const float *weight, int32_t cout, int32_t cin, uint16_t *out);
+int32_t swk_nhwc_conv3x3_winograd_bf16s_bias_relu_place(void *stream, const float *src, int32_t n, int32_t t, int32_t cin,
+                                                        const uint16_t *weight_s, const float *bias, int32_t cout, float *dst, int32_t dH,
+                                                        int32_t dW, int32_t dC, int32_t off_y, int32_t off_x, int32_t c_off);
+
 /* ---- host-side tracker kernels (no GPU, no context): SURVEY section 8f rank 1 -----------------------
  * Cost matrix of SegmentTracker.formulate_cost_matrix (segment_tracking.py:46-102, 179-254): square, size
  * n_prev + n_curr, row-major.  Centroids are (row, col) float64 pairs; prev_hist0 = centroid of the first

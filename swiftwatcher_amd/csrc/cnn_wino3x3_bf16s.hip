@@ -1,0 +1,357 @@
+// The Winograd F(2x2, 3x3) expands of cnn_wino3x3.hip with every float32 product formed as SIX bf16 x bf16 products of three-way split
+// operands (the arithmetic of cnn_expand_bf16.hip):
+//
+//     U = u1 + u2 + u3,  V = v1 + v2 + v3  (each part bf16, the remainders exact: 3 x 8 bits cover float32's 24)
+//     U V  ~  u1 v3 + u2 v2 + u3 v1 + u1 v2 + u2 v1 + u1 v1          (smallest first; the three terms below 2^-24 |U V| are dropped)
+//
+// v_mfma_f32_32x32x16_bf16 accumulates in float32 at 16 times the rate of v_mfma_f32_32x32x2_f32: the six products cost 6 x 32 cycles per
+// 16 channels x 32 x 32 outputs where the float32 kernel pays 8 x 64, and the bf16 MFMA holds vector issue for 8 of its 32 cycles, so the
+// transforms, splits and output updates (which the float32 MFMA shares one execution unit with) run beside it.  Float32-grade results
+// (tests/test_wino_bf16s.py: at most the float32 kernel's error against float64).
+//
+// Kept from the float32 kernel: positions in sequence through ONE accumulator M per tile group, Y_ij += c M after each position, V_p formed
+// once per task by the workgroup (a signed sum of four patch pixels), double buffered in LDS, the filter operands streamed into LDS by
+// LDS-DMA with hand-placed counted waits (asm: see cnn_wino3x3.hip), the fused bias + ReLU + placement epilogue.
+// Changed:
+//   * a wave owns ONE column block of 32 output channels and TWO tile groups of 32 tiles: a workgroup = cout / 32 waves over 64 tiles, so
+//     each filter operand read from LDS feeds two tile groups, and the filter bytes streamed per output tile are 0.75 of the float32
+//     kernel's (1.5 x the bytes per value, over twice the tiles).  Y = 2 x 2 x 2 x 16 + M 2 x 16 accumulator registers: two waves per SIMD.
+//   * the filter slices are private to their wave ([phase][column block][SPP k-steps][part][lane][8 bf16], host-made by
+//     swk_winograd_f2x2_3x3_weights_bf16s): its own vmcnt tells a wave that they have landed, and the workgroup meets once per POSITION
+//     (for V), not once per phase.  SPP k-steps per phase: every k-step of a position where LDS allows, two of four for 64 -> 256.
+//   * V is split right after the signed sum and stored as three bf16 B operands [part][k / 8][tile (+ pad)][8]: one ds_read_b128 per part
+//     and tile group per k-step, 512 contiguous bytes per half wave; the pad makes the staging stores conflict-free.
+// Where it stands (MI355X, batch 4,096, tools/bench_convs.py, against the float32 kernel in the same call): 64 -> 256 on 16 x 16 outputs
+// 987 us against 1,303, on 11 x 11 533 against 714; 48 -> 192 430 / 612 against 499 / 714; 32 -> 128 281 / 153 against 329 / 168 --
+// the Winograd total of a forward 3.17 against 3.89 ms.  16 -> 64 measured slower (77 / 101 against 73 / 93 us) and stays on the float32
+// kernel in the classifier.  The matrix pipe is no longer the wall: the six products put 64 -> 256 near 0.33 ms of MFMA time, a third of
+// what it takes.  What remains is the filter stream (0.75 of the float32 kernel's bytes per tile, from L2 by LDS-DMA, one phase ahead),
+// the per-position V staging (eight patch loads, transform and split per thread, then a workgroup barrier) and LDS bank conflicts
+// (0.6-1.1 conflict cycles per LDS instruction, profiles/wino_bf16s_pmc_counters.txt); the counters do not separate these further.
+// Twice the tiles per filter byte would need 128 x 256 outputs in one CU's registers (Y alone fills the register file) or V formed
+// twice; see DESIGN section 10.
+// Launched on the CALLER's stream.
+#include "swk_internal.h"
+
+#include <cstring>
+
+namespace swk {
+
+typedef float f16v __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// k-steps (16 input channels) per filter phase of a shape: the host layout depends on it
+static int wino_bf16s_spp(int cin, int cout) { return cin == 64 && cout == 256 ? 2 : cin / 16; }
+
+// tile pad of a V row: 16 / (8-channel groups) tiles, so that a 16-lane pass of staging stores spreads over all banks
+template <int KG> struct WinoVPad { static constexpr int value = KG == 6 ? 3 : 16 / KG; };
+
+template <int NBLK, int SPP>
+__global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const float *__restrict__ src, int nseg, int t, int T,
+                                                                          const uint16_t *__restrict__ wu, const float *__restrict__ bias,
+                                                                          int cout, float *__restrict__ dst, int dH, int dW, int dC, int off_y,
+                                                                          int off_x, int c_off, FastDiv fTT, FastDiv fT)
+{
+    // NBLK column blocks = waves = 8-channel groups of the input (cout = 4 cin); S k-steps per position, PHS phases of SPP of them
+    constexpr int NW = NBLK, NT = 64 * NW, KG = NBLK, CIN = 8 * KG, S = CIN / 16, PHS = S / SPP, SLOTS = 64, NP = 32 * NBLK;
+    constexpr int VT = SLOTS + WinoVPad<KG>::value;          // 16-byte rows of a V part
+    constexpr int WPB = SPP * 3 * 1024;                       // bytes of a wave's filter slice of one phase
+    static_assert(S % SPP == 0 && NT == SLOTS * KG, "one staging item per thread");
+    extern __shared__ uint4 lds_w[];          // W[2][NW][WPB], V[2][3][KG][VT] x 16 B, the bias padded to NP
+    char *const Wl = (char *)lds_w;
+    uint4 *const V0 = (uint4 *)(Wl + 2 * NW * WPB), *const V1 = V0 + 3 * KG * VT;
+    float *const lbias = (float *)(V1 + 3 * KG * VT);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+    const int o = t - 2, TT = T * T;
+    const int64_t ntiles = (int64_t)nseg * TT, src_floats = (int64_t)nseg * t * t * CIN;
+    const int64_t ntasks = (ntiles + SLOTS - 1) / SLOTS;
+    for (int i = tid; i < NP; i += NT) lbias[i] = i < cout ? bias[i] : 0.0f;
+
+    // ---- the staging item of this thread: (tile slot, 8-channel group), channel group fastest (a wave reads whole pixels) ----
+    const int sg = tid % KG, sslot = tid / KG;
+    unsigned sbase;          // byte offset of the item's patch origin in src
+    int slim;                // largest byte offset a patch load of the item may add (the last 32 bytes of src)
+    const char *const srcb = (const char *)src;
+    auto stage_setup = [&](int64_t task) {
+        int64_t m = task * SLOTS + sslot;
+        if (m >= ntiles) m = ntiles - 1;
+        const unsigned bu = fTT.div((unsigned)m), rem = (unsigned)m - bu * (unsigned)TT, ty = fT.div(rem), tx = rem - ty * (unsigned)T;
+        const int64_t b = bu;
+        const int64_t base = (((b * t + 2 * ty) * t + 2 * tx) * (int64_t)CIN + 8 * sg) * 4;
+        const int64_t lim = src_floats * 4 - 32 - base;          // a patch may reach one row / column past an odd-sized tile
+        sbase = (unsigned)base;
+        slim = (int)(lim < (1 << 30) ? lim : (1 << 30));
+    };
+    float4 st[4][2];
+    // patch rows (columns) position xi (nu) combines, as in cnn_wino3x3.hip: first row {0,1,2,1}, second {2,2,1,3}, sign {-,+,-,-}
+    auto stage_issue = [&](int p) {
+        const int xi = p >> 2, nu = p & 3;
+        const int ra0 = (0x1210 >> (4 * xi)) & 15, ra1 = (0x3122 >> (4 * xi)) & 15;
+        const int rb0 = (0x1210 >> (4 * nu)) & 15, rb1 = (0x3122 >> (4 * nu)) & 15;
+        const int os[4] = {(ra0 * t + rb0) * (CIN * 4), (ra0 * t + rb1) * (CIN * 4), (ra1 * t + rb0) * (CIN * 4), (ra1 * t + rb1) * (CIN * 4)};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const char *q = srcb + (sbase + (unsigned)(os[i] < slim ? os[i] : slim));
+            st[i][0] = *(const float4 *)q;
+            st[i][1] = *(const float4 *)(q + 16);
+        }
+    };
+    // V = (d00 + sn d01) + sx (d10 + sn d11), split three ways, stored as the parts' B operands
+    auto stage_store = [&](int p, uint4 *Vn) {
+        const float sx = (p >> 2) == 1 ? 1.0f : -1.0f, sn = (p & 3) == 1 ? 1.0f : -1.0f;
+        bf16x8 v1, v2, v3;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float a[4] = {st[0][h].x, st[0][h].y, st[0][h].z, st[0][h].w}, b[4] = {st[1][h].x, st[1][h].y, st[1][h].z, st[1][h].w},
+                        c[4] = {st[2][h].x, st[2][h].y, st[2][h].z, st[2][h].w}, d[4] = {st[3][h].x, st[3][h].y, st[3][h].z, st[3][h].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float v = __builtin_fmaf(__builtin_fmaf(d[e], sn, c[e]), sx, __builtin_fmaf(b[e], sn, a[e]));
+                const __bf16 x1 = (__bf16)v;
+                const float r1 = v - (float)x1;
+                const __bf16 x2 = (__bf16)r1;
+                v1[4 * h + e] = x1; v2[4 * h + e] = x2; v3[4 * h + e] = (__bf16)(r1 - (float)x2);
+            }
+        }
+        uint4 *q = Vn + sg * VT + sslot;
+        q[0] = __builtin_bit_cast(uint4, v1);
+        q[KG * VT] = __builtin_bit_cast(uint4, v2);
+        q[2 * KG * VT] = __builtin_bit_cast(uint4, v3);
+    };
+
+    // ---- this wave's filter slice of phase g: WPB contiguous bytes of wu, copied as they lie by LDS-DMA, three 1 KB pieces (the parts)
+    //      per k-step, addressed by the instruction offset (it advances the global and the LDS address alike) ----
+    const unsigned wvoff = (unsigned)(lane * 16);
+    auto w_issue = [&](int g, int buf) {
+        const char *gp = (const char *)wu + ((int64_t)g * NW + __builtin_amdgcn_readfirstlane(wave)) * WPB;          // uniform
+        const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(Wl + (buf * NW + wave) * WPB));
+#pragma unroll
+        for (int sub = 0; sub < SPP; ++sub) {
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
+                         "global_load_lds_dwordx4 %1, %3 offset:1024\n\tglobal_load_lds_dwordx4 %1, %3 offset:2048\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(wvoff), "s"(l + sub * 3072u), "s"(gp + sub * 3072) : "memory");
+        }
+    };
+    // the copies of a phase are issued BEFORE the patch loads: vmcnt(8) retires them and leaves the eight patch loads in flight
+    auto wait_copies = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
+    auto wait_copies_keep8 = [&]() { asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); };
+
+    int64_t task = blockIdx.x;
+    if (task < ntasks) {
+        stage_setup(task);
+        stage_issue(0);
+        stage_store(0, V0);
+        w_issue(0, 0);
+    }
+    wait_copies();
+    __syncthreads();
+    for (; task < ntasks; task += gridDim.x) {
+        // ---- this lane's two tiles as the matrix cores see them: destinations of their 2 x 2 outputs ----
+        int64_t ro[2];
+        bool valid[2], vy1[2], vx1[2];
+#pragma unroll
+        for (int tg = 0; tg < 2; ++tg) {
+            const int64_t m = task * SLOTS + tg * 32 + r;
+            valid[tg] = m < ntiles;
+            const int64_t mm = valid[tg] ? m : ntiles - 1;
+            const unsigned bu = fTT.div((unsigned)mm), rem = (unsigned)mm - bu * (unsigned)TT;
+            const int ty = (int)fT.div(rem), tx = (int)(rem - (unsigned)ty * (unsigned)T);
+            const int64_t b = bu;
+            ro[tg] = ((b * dH + off_y + 2 * ty) * dW + off_x + 2 * tx) * (int64_t)dC + c_off + 32 * wave + 4 * hh;
+            vy1[tg] = 2 * ty + 1 < o;
+            vx1[tg] = 2 * tx + 1 < o;
+        }
+        const bool more = task + gridDim.x < ntasks;
+        f16v Y[2][2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int tg = 0; tg < 2; ++tg)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) Y[i][j][tg][e] = 0.0f;
+        // one phase = SPP k-steps of this wave's column block: 6 SPP dependent MFMAs per tile group
+        auto phase = [&](const char *Wb, const uint4 *Vc, int s0, f16v *M) {
+            const uint4 *wq = (const uint4 *)Wb + lane;
+#pragma unroll
+            for (int sub = 0; sub < SPP; ++sub) {
+                const int s = s0 + sub;
+                const bf16x8 u1 = __builtin_bit_cast(bf16x8, wq[(3 * sub) * 64]), u2 = __builtin_bit_cast(bf16x8, wq[(3 * sub + 1) * 64]),
+                             u3 = __builtin_bit_cast(bf16x8, wq[(3 * sub + 2) * 64]);
+#pragma unroll
+                for (int tg = 0; tg < 2; ++tg) {
+                    const uint4 *vq = Vc + (2 * s + hh) * VT + 32 * tg + r;
+                    const bf16x8 x1 = __builtin_bit_cast(bf16x8, vq[0]), x2 = __builtin_bit_cast(bf16x8, vq[KG * VT]),
+                                 x3 = __builtin_bit_cast(bf16x8, vq[2 * KG * VT]);
+                    M[tg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u1, x3, M[tg], 0, 0, 0);
+                    M[tg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u2, x2, M[tg], 0, 0, 0);
+                    M[tg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u3, x1, M[tg], 0, 0, 0);
+                    M[tg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u1, x2, M[tg], 0, 0, 0);
+                    M[tg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u2, x1, M[tg], 0, 0, 0);
+                    M[tg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(u1, x1, M[tg], 0, 0, 0);
+                }
+            }
+        };
+        for (int p = 0; p < 16; ++p) {
+            const uint4 *Vc = (p & 1) ? V1 : V0;
+            uint4 *Vn = (p & 1) ? V0 : V1;
+            const int pn = (p + 1) & 15;
+            if (p == 15 && more) stage_setup(task + gridDim.x);
+            // Y_ij += A^T[i][xi] A^T[j][nu] M_p,   A^T = [1 1 1 0; 0 1 -1 -1]
+            const int xi = p >> 2, nu = p & 3;
+            const float ax[2] = {xi < 3 ? 1.0f : 0.0f, xi == 0 ? 0.0f : xi == 1 ? 1.0f : -1.0f};
+            const float an[2] = {nu < 3 ? 1.0f : 0.0f, nu == 0 ? 0.0f : nu == 1 ? 1.0f : -1.0f};
+            f16v M[2];
+#pragma unroll
+            for (int tg = 0; tg < 2; ++tg)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) M[tg][e] = 0.0f;
+#pragma unroll
+            for (int h = 0; h < PHS; ++h) {
+                // the next phase's filter slice travels while this one multiplies; the next position's patch pixels during the whole position
+                // (after a workgroup's last position they fetch position 0 of the same tiles again, unused: see cnn_wino3x3.hip)
+                const int g = p * PHS + h, gn = g + 1 == 16 * PHS ? 0 : g + 1;
+                w_issue(gn, (g + 1) & 1);
+                if (h == 0) stage_issue(pn);
+                phase(Wl + ((g & 1) * NW + wave) * WPB, Vc, h * SPP, M);
+                if (h == PHS - 1) {
+                    stage_store(pn, Vn);
+#pragma unroll
+                    for (int i = 0; i < 2; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            const float c = ax[i] * an[j];
+                            if (c != 0.0f) {          // uniform; 36 of the 64 (position, pair) combinations
+#pragma unroll
+                                for (int tg = 0; tg < 2; ++tg)
+#pragma unroll
+                                    for (int e = 0; e < 16; ++e) Y[i][j][tg][e] = __builtin_fmaf(M[tg][e], c, Y[i][j][tg][e]);
+                            }
+                        }
+                }
+                // this wave's slice of the next phase has landed (patch loads issued in a first phase of several stay in flight)
+                if (h == 0 && PHS > 1) wait_copies_keep8();
+                else wait_copies();
+                // the next position's V is complete, this one's buffer is free
+                if (h == PHS - 1) __syncthreads();
+            }
+        }
+        // ---- bias + ReLU + placement: register quads = four consecutive output channels of the lane's tile ----
+#pragma unroll
+        for (int tg = 0; tg < 2; ++tg) {
+            if (!valid[tg]) continue;
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    if ((i == 1 && !vy1[tg]) || (j == 1 && !vx1[tg])) continue;
+                    float *q = dst + ro[tg] + ((int64_t)i * dW + j) * dC;
+#pragma unroll
+                    for (int gq = 0; gq < 4; ++gq) {
+                        const int c = 32 * wave + 8 * gq + 4 * hh;
+                        if (c < cout) {
+                            const float4 b4 = *(const float4 *)(lbias + c);
+                            float4 v;
+                            v.x = fmaxf(Y[i][j][tg][4 * gq] + b4.x, 0.0f);
+                            v.y = fmaxf(Y[i][j][tg][4 * gq + 1] + b4.y, 0.0f);
+                            v.z = fmaxf(Y[i][j][tg][4 * gq + 2] + b4.z, 0.0f);
+                            v.w = fmaxf(Y[i][j][tg][4 * gq + 3] + b4.w, 0.0f);
+                            *(float4 *)(q + 8 * gq) = v;
+                        }
+                    }
+                }
+        }
+    }
+}
+
+template <int NBLK, int SPP>
+static int launch_wino3x3_bf16s(hipStream_t s, const float *src, int n, int t, const uint16_t *wu, const float *bias, int cout, float *dst,
+                                int dH, int dW, int dC, int off_y, int off_x, int c_off)
+{
+    constexpr int NW = NBLK, KG = NBLK, CIN = 8 * NBLK, VT = 64 + WinoVPad<KG>::value;
+    const size_t lds = (size_t)2 * NW * SPP * 3 * 1024 + (size_t)2 * 3 * KG * VT * 16 + 32 * NBLK * sizeof(float);
+    static_assert((size_t)2 * NW * SPP * 3 * 1024 + (size_t)2 * 3 * KG * VT * 16 + 32 * NBLK * 4 <= 160 * 1024 - 256, "LDS of one workgroup");
+    static unsigned long long attr_mask = 0;
+    if (!ensure_dyn_lds((const void *)k_wino3x3_bf16s_relu_place<NBLK, SPP>, 160 * 1024 - 256, attr_mask)) return SWK_ERR_HIP;
+    if ((int64_t)n * t * t * CIN * 4 >= ((int64_t)1 << 32)) return SWK_ERR_CAPACITY;          // 32-bit byte offsets into src (and tile indices)
+    const int T = (t - 2 + 1) / 2;
+    const int64_t ntiles = (int64_t)n * T * T;
+    int64_t blocks = (ntiles + 63) / 64;
+    // persistent workgroups, two waves per SIMD: as many per CU as eight waves and the LDS allow
+    const int64_t by_lds = (int64_t)((160 * 1024 - 256) / lds), by_waves = 8 / NW;
+    const int64_t per_cu = by_waves < 1 ? 1 : (by_lds < by_waves ? by_lds : by_waves);
+    if (blocks > 256 * per_cu) blocks = 256 * per_cu;
+    hipLaunchKernelGGL((k_wino3x3_bf16s_relu_place<NBLK, SPP>), dim3((unsigned)blocks), dim3(64 * NW), lds, s, src, n, t, T, wu, bias, cout, dst,
+                       dH, dW, dC, off_y, off_x, c_off, FastDiv((unsigned)(T * T)), FastDiv((unsigned)T));
+    return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
+}
+
+}  // namespace swk
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int32_t swk_winograd_f2x2_3x3_weights_bf16s(const float *weight, int32_t cout, int32_t cin, uint16_t *out)
+{
+    if (!weight || !out || cout < 1 || cin < 16 || (cin & 15)) return SWK_ERR_ARG;
+    // A operands of v_mfma_f32_32x32x16_bf16 (lane l: output channel 32 cb + (l & 31), input channels 16 s + 8 (l >> 5) .. + 7), output
+    // channels padded to whole column blocks: [p][phase][cb][k-step of the phase][part][lane][8], a wave's slice of a phase contiguous
+    const int spp = swk::wino_bf16s_spp(cin, cout), S = cin / 16, PHS = S / spp, CG = (cout + 31) / 32;
+    if (S % spp) return SWK_ERR_ARG;
+    static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
+    for (int64_t i = 0, e = (int64_t)16 * cin * CG * 32 * 3; i < e; ++i) out[i] = 0;
+    auto bf16_rne = [](float f, float &back) -> uint16_t {          // round to nearest even (finite values)
+        uint32_t u;
+        memcpy(&u, &f, 4);
+        u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+        memcpy(&back, &u, 4);
+        return (uint16_t)(u >> 16);
+    };
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci) {
+            // U = G g G^T in float64, rounded to float32: the same operations as swk_winograd_f2x2_3x3_weights
+            const float *g = weight + ((int64_t)co * cin + ci) * 9;
+            double tmp[4][3], U[4][4];
+            for (int a = 0; a < 4; ++a)
+                for (int c = 0; c < 3; ++c) tmp[a][c] = G[a][0] * g[c] + G[a][1] * g[3 + c] + G[a][2] * g[6 + c];
+            for (int a = 0; a < 4; ++a)
+                for (int c = 0; c < 4; ++c) U[a][c] = tmp[a][0] * G[c][0] + tmp[a][1] * G[c][1] + tmp[a][2] * G[c][2];
+            const int s = ci >> 4, ph = s / spp, sub = s % spp, lane = ((ci >> 3) & 1) * 32 + (co & 31), j = ci & 7, cb = co >> 5;
+            for (int p = 0; p < 16; ++p) {
+                const float u = (float)U[p >> 2][p & 3];
+                float b1, b2, b3;
+                const uint16_t h1 = bf16_rne(u, b1);
+                const float r1 = u - b1;
+                const uint16_t h2 = bf16_rne(r1, b2);
+                const uint16_t h3 = bf16_rne(r1 - b2, b3);
+                const int64_t blk = (((int64_t)p * PHS + ph) * CG + cb) * spp + sub;
+                out[((blk * 3 + 0) * 64 + lane) * 8 + j] = h1;
+                out[((blk * 3 + 1) * 64 + lane) * 8 + j] = h2;
+                out[((blk * 3 + 2) * 64 + lane) * 8 + j] = h3;
+            }
+        }
+    return SWK_OK;
+}
+
+int32_t swk_nhwc_conv3x3_winograd_bf16s_bias_relu_place(void *stream, const float *src, int32_t n, int32_t t, int32_t cin,
+                                                        const uint16_t *weight_s, const float *bias, int32_t cout, float *dst, int32_t dH,
+                                                        int32_t dW, int32_t dC, int32_t off_y, int32_t off_x, int32_t c_off)
+{
+    if (!src || !weight_s || !bias || !dst || n < 1 || t < 3 || cout < 4 || (cout & 3) || (dC & 3) || (c_off & 3) || off_y < 0 || off_x < 0 ||
+        off_y + t - 2 > dH || off_x + t - 2 > dW || c_off < 0 || c_off + cout > dC || (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)weight_s) & 15))
+        return SWK_ERR_ARG;
+    using namespace swk;
+    hipStream_t s = (hipStream_t)stream;
+#define SWK_W3S_ARGS s, src, n, t, weight_s, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off
+    if (cin == 16 && cout == 64) return launch_wino3x3_bf16s<2, 1>(SWK_W3S_ARGS);
+    if (cin == 32 && cout == 128) return launch_wino3x3_bf16s<4, 2>(SWK_W3S_ARGS);
+    if (cin == 48 && cout == 192) return launch_wino3x3_bf16s<6, 3>(SWK_W3S_ARGS);
+    if (cin == 64 && cout == 256) return launch_wino3x3_bf16s<8, 2>(SWK_W3S_ARGS);
+#undef SWK_W3S_ARGS
+    return SWK_ERR_ARG;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop

@@ -170,11 +170,15 @@ class CroppedSqueezeNet10:
         self.own_kernels = os.environ.get("SWK_OWN_CNN_KERNELS", "1") == "1"
         self._head = None
         self.winograd = True
+        # the Winograd expands with float32 products as six bf16 matrix-core products of split operands (csrc/cnn_wino3x3_bf16s.hip);
+        # False (or SWK_WINO_SPLIT_BF16=0) keeps them on the f32 matrix cores (csrc/cnn_wino3x3.hip)
+        self.wino_split_bf16 = os.environ.get("SWK_WINO_SPLIT_BF16", "1") == "1"
         # max-pool + the squeeze behind it as one kernel (csrc/cnn_poolsq.hip): the pooled tensor never goes to memory
         self.fuse_pool = os.environ.get("SWK_FUSE_POOL", "1") == "1"
         self._w1 = None
         self._wt3 = {}
         self._ww3 = {}
+        self._ws3 = {}
 
     def macs_per_segment(self):
         """Multiply-accumulates of one forward per segment: (executed, useful).  "useful" prices every convolution output the next
@@ -245,10 +249,72 @@ class CroppedSqueezeNet10:
             kind != "fire" or not (pad[0] or pad[1]) for kind, _, _, _, _, pad, _ in self.plan)
 
     def reserve(self, batch):
-        """Persistent tiles for `batch` segments, made now (on the current stream)."""
+        """Persistent tiles for `batch` segments and every per-layer operand tensor, made now (on the current stream)."""
         self._buffers(batch)
         if self.ring_sum.is_cuda:
             self._aux_buffers(batch)
+            self._prepare_operands()
+
+    def _prepare_operands(self):
+        """The operand tensors the own kernels read (conv1's weights, the 3x3 expands' in the layout of the kernel each one runs on, the
+        head's), made on the current stream.  Made lazily by the first forward that needs one, they would be enqueued on whichever stream
+        that forward runs on: in a two-chain forward (SegmentClassifier._forward_two_streams) the side stream, whose copy the other chain
+        then may read before it has landed -- so reserve() makes them all before the chains fork."""
+        if not (self.own_kernels and self.ring_sum.is_cuda and self.memory_format == torch.channels_last):
+            return
+        self._conv1_operand()
+        for j, (kind, layer, tile, off, n, pad, crop) in enumerate(self.plan):
+            if kind == "fire":
+                self._w3_operand(j, layer.expand3x3)
+        self._head_operand()
+
+    def _conv1_operand(self):
+        if self._w1 is None:
+            self._w1 = self.model.features[0].weight.detach().contiguous(memory_format=torch.contiguous_format).clone()
+        return self._w1
+
+    def _head_operand(self):
+        if self._head is None:
+            head = self.model.classifier[1]
+            self._head = (head.weight.detach().reshape(head.out_channels, -1).contiguous(), head.bias.detach().contiguous(),
+                          self.ring_sum.reshape(-1).contiguous())
+        return self._head
+
+    def _w3_kind(self, conv):
+        """The kernel a 3x3 expand runs on: "bf16s" / "f32" (Winograd F(2x2, 3x3), split-bf16 or f32 products) or "direct"."""
+        cin, cout = conv.in_channels, conv.out_channels
+        if self.winograd and cout == 4 * cin and cin in (16, 32, 48, 64):
+            # (16 -> 64 measured slower on the split kernel, 77 / 101 against 73 / 93 us per 4,096 rows: it stays on the f32 one)
+            return "bf16s" if self.wino_split_bf16 and cin != 16 else "f32"
+        return "direct"
+
+    def _w3_operand(self, j, conv, kind=None):
+        """The weights of the 3x3 expand of plan entry j in the layout of the kernel `kind` runs on, made once per layer."""
+        from . import _lib
+        kind = kind or self._w3_kind(conv)
+        cache = {"bf16s": self._ws3, "f32": self._ww3, "direct": self._wt3}[kind]
+        w = cache.get(j)
+        if w is not None:
+            return w
+        cin, cout = conv.in_channels, conv.out_channels
+        dev = conv.weight.device
+        if kind == "direct":          # [co][ci][3][3] -> [tap][ci][co]
+            w = conv.weight.detach().permute(2, 3, 1, 0).contiguous(memory_format=torch.contiguous_format)
+        else:                         # G g G^T in the kernel's operand layout (host code of the library)
+            lib = _lib.load()
+            wc = conv.weight.detach().to("cpu", torch.float32).contiguous()
+            ncol = 32 * (-(-cout // 32))
+            if kind == "bf16s":
+                out = torch.empty(3 * 16 * cin * ncol, dtype=torch.int16)          # bf16 bit patterns
+                if lib.swk_winograd_f2x2_3x3_weights_bf16s(wc.data_ptr(), cout, cin, out.data_ptr()):
+                    raise RuntimeError("swk_winograd_f2x2_3x3_weights_bf16s failed")
+            else:
+                out = torch.empty(16 * cin * ncol, dtype=torch.float32)
+                if lib.swk_winograd_f2x2_3x3_weights(wc.data_ptr(), cout, cin, out.data_ptr()):
+                    raise RuntimeError("swk_winograd_f2x2_3x3_weights failed")
+            w = out.to(dev)
+        cache[j] = w
+        return w
 
     @torch.no_grad()
     def __call__(self, tiles, row0=0):
@@ -327,23 +393,16 @@ class CroppedSqueezeNet10:
         def conv3x3(src, j, conv, dest, off, c_off):
             src = nhwc(src)
             cin, cout = conv.in_channels, conv.out_channels
-            if self.winograd and cout == 4 * cin and cin in (16, 32, 48, 64) and k * src.shape[2] * src.shape[2] * cin * 4 < (1 << 32):
-                ww = self._ww3.get(j)
-                if ww is None:       # G g G^T in the kernel's operand layout, once per layer (host code of the library)
-                    w = conv.weight.detach().to("cpu", torch.float32).contiguous()
-                    out = torch.empty(16 * cin * cout, dtype=torch.float32)
-                    if lib.swk_winograd_f2x2_3x3_weights(w.data_ptr(), cout, cin, out.data_ptr()):
-                        raise RuntimeError("swk_winograd_f2x2_3x3_weights failed")
-                    ww = self._ww3[j] = out.to(src.device)
-                rc = lib.swk_nhwc_conv3x3_winograd_bias_relu_place(stream, src.data_ptr(), k, src.shape[2], cin, ww.data_ptr(),
-                                                                   conv.bias.data_ptr(), cout, dest.data_ptr(), dest.shape[2],
-                                                                   dest.shape[3], dest.shape[1], off, off, c_off)
+            kind = self._w3_kind(conv)
+            if kind != "direct" and k * src.shape[2] * src.shape[2] * cin * 4 < (1 << 32):
+                ww = self._w3_operand(j, conv, kind)
+                fn = "swk_nhwc_conv3x3_winograd_bf16s_bias_relu_place" if kind == "bf16s" else "swk_nhwc_conv3x3_winograd_bias_relu_place"
+                rc = getattr(lib, fn)(stream, src.data_ptr(), k, src.shape[2], cin, ww.data_ptr(), conv.bias.data_ptr(), cout,
+                                      dest.data_ptr(), dest.shape[2], dest.shape[3], dest.shape[1], off, off, c_off)
                 if rc:
-                    raise RuntimeError("swk_nhwc_conv3x3_winograd_bias_relu_place failed (%d)" % rc)
+                    raise RuntimeError("%s failed (%d)" % (fn, rc))
                 return
-            wt = self._wt3.get(j)
-            if wt is None:       # [co][ci][3][3] -> [tap][ci][co], once per layer
-                wt = self._wt3[j] = conv.weight.detach().permute(2, 3, 1, 0).contiguous(memory_format=torch.contiguous_format)
+            wt = self._w3_operand(j, conv, "direct")
             assert src.shape[2] == src.shape[3]
             rc = lib.swk_nhwc_conv3x3_bias_relu_place(stream, src.data_ptr(), k, src.shape[2], src.shape[1], wt.data_ptr(),
                                                       conv.bias.data_ptr(), conv.out_channels, dest.data_ptr(), dest.shape[2],
@@ -373,10 +432,9 @@ class CroppedSqueezeNet10:
         side = tiles.shape[2]
         if self.own_kernels and conv1.out_channels == 96 and side % 2 == 0 and 2 * (b - 1) + 8 <= side:
             # conv1 + bias + ReLU on the rows the first pool reads, one kernel (csrc/cnn_conv1.hip)
-            if self._w1 is None:
-                self._w1 = conv1.weight.detach().contiguous(memory_format=torch.contiguous_format).clone()
+            w1 = self._conv1_operand()
             xin = nhwc(tiles)
-            rc = lib.swk_nhwc_conv7x7s2_bias_relu(stream, xin.data_ptr(), k, side, a, b - a, self._w1.data_ptr(), conv1.bias.data_ptr(),
+            rc = lib.swk_nhwc_conv7x7s2_bias_relu(stream, xin.data_ptr(), k, side, a, b - a, w1.data_ptr(), conv1.bias.data_ptr(),
                                                   conv1.out_channels, c1buf.data_ptr())
             if rc:
                 raise RuntimeError("swk_nhwc_conv7x7s2_bias_relu failed (%d)" % rc)
@@ -433,10 +491,7 @@ class CroppedSqueezeNet10:
         head = m.classifier[1]
         if self.own_kernels and head.out_channels == 2 and x.shape[1] in (256, 512, 768, 1024) and x.is_contiguous(memory_format=cl):
             # the head as one kernel with a fixed summation order (csrc/cnn_aux.hip): scores that do not depend on the batch's row count
-            if self._head is None:
-                self._head = (head.weight.detach().reshape(2, -1).contiguous(), head.bias.detach().contiguous(),
-                              self.ring_sum.reshape(-1).contiguous())
-            hw, hb, ring = self._head
+            hw, hb, ring = self._head_operand()
             out = torch.empty((k, 2), dtype=torch.float32, device=x.device)
             rc = lib.swk_nhwc_head2_relu_mean(stream, x.data_ptr(), k, x.shape[2] * x.shape[3], x.shape[1], hw.data_ptr(), hb.data_ptr(),
                                               ring.data_ptr(), self.n_pos, out.data_ptr())

@@ -47,11 +47,11 @@ def describe(name, a):
     if name == "swk_nhwc_conv1x1_bias_relu_place":
         n, cin, h, w, cout = a[2], a[5], a[8], a[9], a[12]
         return "1x1 %3d->%3d %2dx%2d" % (cin, cout, h, w), n * h * w * cin * cout, 4 * n * h * w * (cin + cout)
-    if name in ("swk_nhwc_conv3x3_bias_relu_place", "swk_nhwc_conv3x3_winograd_bias_relu_place"):
+    if name in ("swk_nhwc_conv3x3_bias_relu_place", "swk_nhwc_conv3x3_winograd_bias_relu_place", "swk_nhwc_conv3x3_winograd_bf16s_bias_relu_place"):
         n, t, cin, cout = a[2], a[3], a[4], a[7]
         o = t - 2
         # direct-convolution multiply-accumulates for both (the Winograd kernel executes 16/36 of them, padded to even sizes)
-        return ("w3x3" if "winograd" in name else "3x3 ") + "%3d->%3d %2dx%2d" % (cin, cout, o, o), n * o * o * 9 * cin * cout, 4 * n * (t * t * cin + o * o * cout)
+        return ("s3x3" if "bf16s" in name else "w3x3" if "winograd" in name else "3x3 ") + "%3d->%3d %2dx%2d" % (cin, cout, o, o), n * o * o * 9 * cin * cout, 4 * n * (t * t * cin + o * o * cout)
     if name == "swk_nhwc_maxpool3s2_conv1x1_bias_relu_place":
         n, t, cin, cout = a[2], a[3], a[4], a[7]
         p = (t - 3) // 2 + 1
