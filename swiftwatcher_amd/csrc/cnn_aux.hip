@@ -3,7 +3,7 @@
 // themselves) -- bias + ReLU + crop behind conv1 (MIOpen), and the three max-pools (PyTorch's NHWC max-pool kernel runs far
 // below the memory rate).  Plain streaming jobs, launched on the CALLER's stream (PyTorch's current stream).
 // Layout: channels-last dense float32, tensor (n, c, h, w) = memory [n][h][w][c].
-#include "swk_internal.h"
+#include "cnn_common.h"
 
 namespace swk {
 
@@ -141,9 +141,10 @@ int32_t swk_nhwc_bias_relu_place(void *stream, const float *src, int32_t n, int3
                                  int32_t crop_x, int32_t h, int32_t w, const float *bias, float *dst, int32_t dH, int32_t dW,
                                  int32_t dC, int32_t off_y, int32_t off_x, int32_t c_off)
 {
-    if (!src || !bias || !dst || n < 1 || h < 1 || w < 1 || c < 4 || (c & 3) || (dC & 3) || (c_off & 3) || crop_y < 0 || crop_x < 0 ||
-        crop_y + h > sh || crop_x + w > sw || off_y < 0 || off_x < 0 || off_y + h > dH || off_x + w > dW || c_off < 0 || c_off + c > dC ||
-        (((uintptr_t)src | (uintptr_t)bias | (uintptr_t)dst) & 15))
+    const swk::Place pl{dst, dH, dW, dC, off_y, off_x, c_off};
+    const swk::Crop cr{sh, sw, crop_y, crop_x};
+    // beyond the placement: float4 loads of src and bias (16-byte aligned)
+    if (!src || !bias || n < 1 || h < 1 || w < 1 || !swk::place_ok(pl, h, w, c, true, &cr) || (((uintptr_t)src | (uintptr_t)bias) & 15))
         return SWK_ERR_ARG;
     const int64_t total = (int64_t)n * h * w * (c / 4);
     hipLaunchKernelGGL(swk::k_bias_relu_place, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,

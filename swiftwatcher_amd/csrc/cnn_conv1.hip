@@ -16,11 +16,9 @@
 //   * A operand (weights): all of W, re-laid [dy][j][half][co] with pitch 97, sits in LDS (65 KB); one ds_read_b32 per MFMA.
 //   * three accumulators (96 channels) per 32 pixels; a register quad = four consecutive channels of the lane's pixel: float4 stores.
 // Launched on the CALLER's stream (PyTorch's current stream).
-#include "swk_internal.h"
+#include "cnn_common.h"
 
 namespace swk {
-
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(512, 4) void k_conv7x7s2_relu(const float *__restrict__ src, int64_t rows, int side, int lo, int m,
                                                         const float *__restrict__ wgt, const float *__restrict__ bias, float *__restrict__ dst, FastDiv fmm, FastDiv fm)
@@ -94,13 +92,7 @@ __global__ __launch_bounds__(512, 4) void k_conv7x7s2_relu(const float *__restri
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int c = nb * 32 + 8 * g;
-                    const float4 b4 = *(const float4 *)(lbias + c + 4 * hh);
-                    float4 v;
-                    v.x = fmaxf(acc[nb][4 * g] + b4.x, 0.0f);
-                    v.y = fmaxf(acc[nb][4 * g + 1] + b4.y, 0.0f);
-                    v.z = fmaxf(acc[nb][4 * g + 2] + b4.z, 0.0f);
-                    v.w = fmaxf(acc[nb][4 * g + 3] + b4.w, 0.0f);
-                    *(float4 *)(o + c) = v;
+                    store_bias_relu(o + c, acc[nb], g, *(const float4 *)(lbias + c + 4 * hh));
                 }
         }
     }

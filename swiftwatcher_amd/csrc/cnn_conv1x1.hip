@@ -24,11 +24,9 @@
 //   * the weights (at most 512 x 64 or 64 x 256 floats) sit transposed in LDS, [ci][co] with pitch N + 1: the staging
 //     reads W coalesced along ci and writes conflict-free, and an operand read is 32 consecutive floats per half.
 // Launched on the CALLER's stream (PyTorch's current stream), like the other glue kernels (cnn_aux.hip).
-#include "swk_internal.h"
+#include "cnn_common.h"
 
 namespace swk {
-
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 // CS = column splits: CS waves share a row tile, each computing NBLK / CS of its 32-channel column blocks (they load the same
 // activations; the accumulators of a wave shrink to 16 NBLK / CS registers).  NWV = waves per workgroup: 16 (one workgroup per
@@ -131,15 +129,7 @@ __global__ __launch_bounds__(64 * NWV) void k_conv1x1_relu_place(const float *__
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int c = nb * 32 + 8 * g;          // relative to the wave's first column block
-                    if (32 * NB * cs + c + 4 * hh < cout) {
-                        const float4 b4 = *(const float4 *)(lbias + 32 * NB * cs + c + 4 * hh);
-                        float4 v;
-                        v.x = fmaxf(acc[nb][4 * g] + b4.x, 0.0f);
-                        v.y = fmaxf(acc[nb][4 * g + 1] + b4.y, 0.0f);
-                        v.z = fmaxf(acc[nb][4 * g + 2] + b4.z, 0.0f);
-                        v.w = fmaxf(acc[nb][4 * g + 3] + b4.w, 0.0f);
-                        *(float4 *)(o + c) = v;
-                    }
+                    if (32 * NB * cs + c + 4 * hh < cout) store_bias_relu(o + c, acc[nb], g, *(const float4 *)(lbias + 32 * NB * cs + c + 4 * hh));
                 }
         }
         p = pn;
@@ -148,8 +138,8 @@ __global__ __launch_bounds__(64 * NWV) void k_conv1x1_relu_place(const float *__
 }
 
 template <int NBLK, int KC, int D, int CS, int NWV>
-static int launch_conv1x1_d(hipStream_t s, const float *src, int64_t rows, int sh, int sw, int cin, int crop_y, int crop_x, int h, int w,
-                            const float *wgt, const float *bias, int cout, float *dst, int dH, int dW, int dC, int off_y, int off_x, int c_off)
+static int launch_conv1x1_d(hipStream_t s, const float *src, int64_t rows, const Crop &cr, int cin, int h, int w, const float *wgt,
+                            const float *bias, int cout, const Place &pl)
 {
     const size_t lds = (size_t)(((cin * (32 * NBLK + 1) + 3) & ~3) + 32 * NBLK) * sizeof(float);
     static unsigned long long attr_mask = 0;
@@ -164,8 +154,8 @@ static int launch_conv1x1_d(hipStream_t s, const float *src, int64_t rows, int s
     const int64_t per_cu = by_lds < 1 ? 1 : (by_lds < by_waves ? by_lds : by_waves);
     const int64_t cap = 256 * per_cu;
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((k_conv1x1_relu_place<NBLK, KC, D, CS, NWV>), dim3((unsigned)blocks), dim3(64 * NWV), lds, s, src, rows, sh, sw, cin, crop_y,
-                       crop_x, h, w, wgt, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off, FastDiv((unsigned)(h * w)), FastDiv((unsigned)w));
+    hipLaunchKernelGGL((k_conv1x1_relu_place<NBLK, KC, D, CS, NWV>), dim3((unsigned)blocks), dim3(64 * NWV), lds, s, src, rows, cr.sh, cr.sw, cin,
+                       cr.crop_y, cr.crop_x, h, w, wgt, bias, cout, pl.dst, pl.dH, pl.dW, pl.dC, pl.off_y, pl.off_x, pl.c_off, FastDiv((unsigned)(h * w)), FastDiv((unsigned)w));
     return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
 }
 
@@ -173,10 +163,10 @@ int g_expand_split_bf16 = getenv("SWK_EXPAND_SPLIT_BF16") ? atoi(getenv("SWK_EXP
 int g_conv1x1_ring = 0;          // A/B knob: 0 = 16-wave workgroups, column blocks of the wide expands split over two waves; 1 = the
                                  // first layout (8 waves, every wave all column blocks, activation ring as deep as fits)
 
-#define SWK_C1_ARGS s, src, rows, sh, sw, cin, crop_y, crop_x, h, w, wgt, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off
+#define SWK_C1_ARGS s, src, rows, cr, cin, h, w, wgt, bias, cout, pl
 template <int NBLK>
-static int launch_conv1x1(hipStream_t s, const float *src, int64_t rows, int sh, int sw, int cin, int crop_y, int crop_x, int h, int w,
-                          const float *wgt, const float *bias, int cout, float *dst, int dH, int dW, int dC, int off_y, int off_x, int c_off)
+static int launch_conv1x1(hipStream_t s, const float *src, int64_t rows, const Crop &cr, int cin, int h, int w, const float *wgt, const float *bias,
+                          int cout, const Place &pl)
 {
     constexpr int CS = NBLK >= 6 ? 2 : 1;          // 64 accumulator registers per wave at most
     if (g_conv1x1_ring == 0) {
@@ -221,26 +211,26 @@ int32_t swk_nhwc_conv1x1_bias_relu_place(void *stream, const float *src, int32_t
                                          int32_t crop_x, int32_t h, int32_t w, const float *weight, const float *bias, int32_t cout,
                                          float *dst, int32_t dH, int32_t dW, int32_t dC, int32_t off_y, int32_t off_x, int32_t c_off)
 {
-    if (!src || !weight || !bias || !dst || n < 1 || h < 1 || w < 1 || cin < 16 || (cin & 15) || cin > 1024 || cout < 4 || cout > 256 ||
-        (cout & 3) || (dC & 3) || (c_off & 3) || (((uintptr_t)dst) & 15) ||
-        crop_y < 0 || crop_x < 0 || crop_y + h > sh || crop_x + w > sw || off_y < 0 || off_x < 0 || off_y + h > dH || off_x + w > dW ||
-        c_off < 0 || c_off + cout > dC || ((((uintptr_t)src) | ((uintptr_t)weight)) & 15))
+    const swk::Place pl{dst, dH, dW, dC, off_y, off_x, c_off};
+    const swk::Crop cr{sh, sw, crop_y, crop_x};
+    // beyond the placement: the channel counts the kernel is built for, float4 loads of src and weight (16-byte aligned)
+    if (!src || !weight || !bias || n < 1 || h < 1 || w < 1 || cin < 16 || (cin & 15) || cin > 1024 || cout > 256 ||
+        !swk::place_ok(pl, h, w, cout, true, &cr) || ((((uintptr_t)src) | ((uintptr_t)weight)) & 15))
         return SWK_ERR_ARG;
     using namespace swk;
     const int64_t rows = (int64_t)n * h * w;
     hipStream_t s = (hipStream_t)stream;
     if (g_expand_split_bf16 && cout == 4 * cin) {          // the Fire modules' expand1x1 shapes: float32 products from split bf16 operands
-        const int rc = launch_expand1x1_split_bf16(s, src, rows, sh, sw, cin, crop_y, crop_x, h, w, weight, bias, cout, dst, dH, dW, dC, off_y, off_x,
-                                                   c_off);
+        const int rc = launch_expand1x1_split_bf16(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
         if (rc != SWK_ERR_ARG) return rc;
     }
     switch ((cout + 31) / 32) {
-    case 1: return launch_conv1x1<1>(s, src, rows, sh, sw, cin, crop_y, crop_x, h, w, weight, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 2: return launch_conv1x1<2>(s, src, rows, sh, sw, cin, crop_y, crop_x, h, w, weight, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 3: return launch_conv1x1<3>(s, src, rows, sh, sw, cin, crop_y, crop_x, h, w, weight, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 4: return launch_conv1x1<4>(s, src, rows, sh, sw, cin, crop_y, crop_x, h, w, weight, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 6: return launch_conv1x1<6>(s, src, rows, sh, sw, cin, crop_y, crop_x, h, w, weight, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 8: return launch_conv1x1<8>(s, src, rows, sh, sw, cin, crop_y, crop_x, h, w, weight, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
+    case 1: return launch_conv1x1<1>(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
+    case 2: return launch_conv1x1<2>(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
+    case 3: return launch_conv1x1<3>(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
+    case 4: return launch_conv1x1<4>(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
+    case 6: return launch_conv1x1<6>(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
+    case 8: return launch_conv1x1<8>(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
     default: return SWK_ERR_ARG;          // 5 and 7 blocks (129..160, 193..224 channels) do not occur in SqueezeNet-1.0
     }
 }

@@ -22,11 +22,9 @@
 //     so every chunk is 64 (48) back-to-back MFMAs between two barriers.
 //   * epilogue from the accumulator layout, as in the 1x1 kernel.
 // Launched on the CALLER's stream (PyTorch's current stream).
-#include "swk_internal.h"
+#include "cnn_common.h"
 
 namespace swk {
-
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 template <int NBLK, int RT>
 __global__ __launch_bounds__(512) void k_conv3x3_relu_place(const float *__restrict__ src, int64_t rows, int t, int cin, const float *__restrict__ wt,
@@ -150,14 +148,14 @@ __global__ __launch_bounds__(512) void k_conv3x3_relu_place(const float *__restr
 
 template <int NBLK, int RT>
 static int launch_conv3x3(hipStream_t s, const float *src, int64_t rows, int t, int cin, const float *wt, const float *bias, int cout,
-                          float *dst, int dH, int dW, int dC, int off_y, int off_x, int c_off)
+                          const Place &pl)
 {
     const size_t lds = (size_t)((2 * 16 * (32 * NBLK + 1) + 1) & ~1) * sizeof(float) + (size_t)8 * RT * 32 * sizeof(int64_t);
     const int64_t ntiles = (rows + 31) / 32;
     int64_t blocks = (ntiles + 8 * RT - 1) / (8 * RT);
     if (blocks > 512) blocks = 512;                // persistent over the super tiles; two workgroups fit a CU at 128 registers
-    hipLaunchKernelGGL((k_conv3x3_relu_place<NBLK, RT>), dim3((unsigned)blocks), dim3(512), lds, s, src, rows, t, cin, wt, bias, cout, dst,
-                       dH, dW, dC, off_y, off_x, c_off);
+    hipLaunchKernelGGL((k_conv3x3_relu_place<NBLK, RT>), dim3((unsigned)blocks), dim3(512), lds, s, src, rows, t, cin, wt, bias, cout, pl.dst,
+                       pl.dH, pl.dW, pl.dC, pl.off_y, pl.off_x, pl.c_off);
     return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
 }
 
@@ -170,19 +168,21 @@ int32_t swk_nhwc_conv3x3_bias_relu_place(void *stream, const float *src, int32_t
                                          const float *bias, int32_t cout, float *dst, int32_t dH, int32_t dW, int32_t dC, int32_t off_y,
                                          int32_t off_x, int32_t c_off)
 {
-    if (!src || !weight_t || !bias || !dst || n < 1 || t < 3 || cin < 16 || (cin & 15) || cin > 1024 || cout < 1 || cout > 256 ||
-        off_y < 0 || off_x < 0 || off_y + t - 2 > dH || off_x + t - 2 > dW || c_off < 0 || c_off + cout > dC || (((uintptr_t)src) & 15))
+    const swk::Place pl{dst, dH, dW, dC, off_y, off_x, c_off};
+    // scalar stores: no multiples of four, no alignment of dst asked for; float4 loads of src only
+    if (!src || !weight_t || !bias || n < 1 || t < 3 || cin < 16 || (cin & 15) || cin > 1024 || cout > 256 ||
+        !swk::place_ok(pl, t - 2, t - 2, cout, false) || (((uintptr_t)src) & 15))
         return SWK_ERR_ARG;
     using namespace swk;
     const int64_t rows = (int64_t)n * (t - 2) * (t - 2);
     hipStream_t s = (hipStream_t)stream;
     switch ((cout + 31) / 32) {
-    case 1: return launch_conv3x3<1, 4>(s, src, rows, t, cin, weight_t, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 2: return launch_conv3x3<2, 4>(s, src, rows, t, cin, weight_t, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 3: return launch_conv3x3<3, 2>(s, src, rows, t, cin, weight_t, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 4: return launch_conv3x3<4, 2>(s, src, rows, t, cin, weight_t, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 6: return launch_conv3x3<6, 1>(s, src, rows, t, cin, weight_t, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
-    case 8: return launch_conv3x3<8, 1>(s, src, rows, t, cin, weight_t, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off);
+    case 1: return launch_conv3x3<1, 4>(s, src, rows, t, cin, weight_t, bias, cout, pl);
+    case 2: return launch_conv3x3<2, 4>(s, src, rows, t, cin, weight_t, bias, cout, pl);
+    case 3: return launch_conv3x3<3, 2>(s, src, rows, t, cin, weight_t, bias, cout, pl);
+    case 4: return launch_conv3x3<4, 2>(s, src, rows, t, cin, weight_t, bias, cout, pl);
+    case 6: return launch_conv3x3<6, 1>(s, src, rows, t, cin, weight_t, bias, cout, pl);
+    case 8: return launch_conv3x3<8, 1>(s, src, rows, t, cin, weight_t, bias, cout, pl);
     default: return SWK_ERR_ARG;          // 5 and 7 blocks do not occur in SqueezeNet-1.0
     }
 }

@@ -24,23 +24,18 @@
 // channels 16 s + 8 h .. + 7 of its pixel for k-step s (two float4s), all steps of a tile at once (K <= 64: at most eight float4s), and
 // the next tile's while this one multiplies.  LDS: the split weights [step][column block][part][half][output channel][8] -- an operand
 // read is one ds_read_b128 per lane, conflict-free.  Launched on the CALLER's stream.
-#include "swk_internal.h"
+#include "cnn_common.h"
 
 namespace swk {
-
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ void split3(const float4 lo, const float4 hi, bf16x8 &p1, bf16x8 &p2, bf16x8 &p3)
 {
     const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const __bf16 a = (__bf16)v[j];
-        const float r = v[j] - (float)a;
-        const __bf16 b = (__bf16)r;
-        const float r2 = r - (float)b;
-        p1[j] = a; p2[j] = b; p3[j] = (__bf16)r2;
+        __bf16 a, b, c;
+        split3(v[j], a, b, c);
+        p1[j] = a; p2[j] = b; p3[j] = c;
     }
 }
 
@@ -138,15 +133,7 @@ __global__ __launch_bounds__(64 * NWV) void k_expand1x1_bf16s(const float *__res
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int c = nb * 32 + 8 * g;
-                    if (32 * NB * cs + c + 4 * hh < cout) {
-                        const float4 b4 = *(const float4 *)(lbias + 32 * NB * cs + c + 4 * hh);
-                        float4 v;
-                        v.x = fmaxf(acc[nb][4 * g] + b4.x, 0.0f);
-                        v.y = fmaxf(acc[nb][4 * g + 1] + b4.y, 0.0f);
-                        v.z = fmaxf(acc[nb][4 * g + 2] + b4.z, 0.0f);
-                        v.w = fmaxf(acc[nb][4 * g + 3] + b4.w, 0.0f);
-                        *(float4 *)(o + c) = v;
-                    }
+                    if (32 * NB * cs + c + 4 * hh < cout) store_bias_relu(o + c, acc[nb], g, *(const float4 *)(lbias + 32 * NB * cs + c + 4 * hh));
                 }
         }
         ro = ro_next;
@@ -154,8 +141,8 @@ __global__ __launch_bounds__(64 * NWV) void k_expand1x1_bf16s(const float *__res
 }
 
 template <int NBLK, int KS, int CS, int NWV>
-static int launch_expand_bf16s(hipStream_t s, const float *src, int64_t rows, int sh, int sw, int crop_y, int crop_x, int h, int w, const float *wgt,
-                               const float *bias, int cout, float *dst, int dH, int dW, int dC, int off_y, int off_x, int c_off)
+static int launch_expand_bf16s(hipStream_t s, const float *src, int64_t rows, const Crop &cr, int h, int w, const float *wgt, const float *bias,
+                               int cout, const Place &pl)
 {
     const size_t lds = (size_t)KS * NBLK * 3 * 64 * 16 + 32 * NBLK * sizeof(float);
     static unsigned long long attr_mask = 0;
@@ -167,21 +154,19 @@ static int launch_expand_bf16s(hipStream_t s, const float *src, int64_t rows, in
     const int64_t by_lds = (int64_t)((160 * 1024 - 256) / lds), by_waves = 16 / NWV;
     const int64_t per_cu = by_lds < 1 ? 1 : (by_lds < by_waves ? by_lds : by_waves);
     if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-    hipLaunchKernelGGL((k_expand1x1_bf16s<NBLK, KS, CS, NWV>), dim3((unsigned)blocks), dim3(64 * NWV), lds, s, src, rows, sh, sw, crop_y, crop_x, h, w,
-                       wgt, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off, FastDiv((unsigned)(h * w)), FastDiv((unsigned)w));
+    hipLaunchKernelGGL((k_expand1x1_bf16s<NBLK, KS, CS, NWV>), dim3((unsigned)blocks), dim3(64 * NWV), lds, s, src, rows, cr.sh, cr.sw, cr.crop_y,
+                       cr.crop_x, h, w, wgt, bias, cout, pl.dst, pl.dH, pl.dW, pl.dC, pl.off_y, pl.off_x, pl.c_off, FastDiv((unsigned)(h * w)), FastDiv((unsigned)w));
     return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
 }
 
 // the Fire shapes (cout = 4 cin): SWK_ERR_ARG for anything else (the caller then takes the float32 kernel)
-int launch_expand1x1_split_bf16(hipStream_t s, const float *src, int64_t rows, int sh, int sw, int cin, int crop_y, int crop_x, int h, int w,
-                                const float *wgt, const float *bias, int cout, float *dst, int dH, int dW, int dC, int off_y, int off_x, int c_off)
+int launch_expand1x1_split_bf16(hipStream_t s, const float *src, int64_t rows, const Crop &cr, int cin, int h, int w, const float *wgt,
+                                const float *bias, int cout, const Place &pl)
 {
-#define SWK_EB_ARGS s, src, rows, sh, sw, crop_y, crop_x, h, w, wgt, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off
-    if (cin == 16 && cout == 64) return launch_expand_bf16s<2, 1, 1, 8>(SWK_EB_ARGS);
-    if (cin == 32 && cout == 128) return launch_expand_bf16s<4, 2, 1, 8>(SWK_EB_ARGS);
-    if (cin == 48 && cout == 192) return launch_expand_bf16s<6, 3, 2, 8>(SWK_EB_ARGS);
-    if (cin == 64 && cout == 256) return launch_expand_bf16s<8, 4, 2, 8>(SWK_EB_ARGS);
-#undef SWK_EB_ARGS
+    if (cin == 16 && cout == 64) return launch_expand_bf16s<2, 1, 1, 8>(s, src, rows, cr, h, w, wgt, bias, cout, pl);
+    if (cin == 32 && cout == 128) return launch_expand_bf16s<4, 2, 1, 8>(s, src, rows, cr, h, w, wgt, bias, cout, pl);
+    if (cin == 48 && cout == 192) return launch_expand_bf16s<6, 3, 2, 8>(s, src, rows, cr, h, w, wgt, bias, cout, pl);
+    if (cin == 64 && cout == 256) return launch_expand_bf16s<8, 4, 2, 8>(s, src, rows, cr, h, w, wgt, bias, cout, pl);
     return SWK_ERR_ARG;
 }
 

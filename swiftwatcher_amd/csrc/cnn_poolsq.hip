@@ -14,11 +14,9 @@
 //     output channels of the lane's pixel: float4 stores after bias and ReLU.
 // Double-buffered LDS (chunk c + 1 is pooled and staged while chunk c multiplies), one barrier per chunk.  Launched on the CALLER's
 // stream (PyTorch's current stream), like the other classifier kernels.
-#include "swk_internal.h"
+#include "cnn_common.h"
 
 namespace swk {
-
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 template <int PT, int NB>
 __global__ __launch_bounds__(64 * PT * NB) void k_pool_squeeze(const float *__restrict__ src, int n, int T, int C, int P, const float *__restrict__ wgt,
@@ -98,27 +96,19 @@ __global__ __launch_bounds__(64 * PT * NB) void k_pool_squeeze(const float *__re
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int co = 32 * nb + 8 * g + 4 * hh;
-                if (co < S) {
-                    const float4 b4 = *(const float4 *)(bias + co);
-                    float4 v;
-                    v.x = fmaxf(acc[4 * g] + b4.x, 0.0f);
-                    v.y = fmaxf(acc[4 * g + 1] + b4.y, 0.0f);
-                    v.z = fmaxf(acc[4 * g + 2] + b4.z, 0.0f);
-                    v.w = fmaxf(acc[4 * g + 3] + b4.w, 0.0f);
-                    *(float4 *)(o + 8 * g) = v;
-                }
+                if (co < S) store_bias_relu(o + 8 * g, acc, g, *(const float4 *)(bias + co));
             }
         }
     }
 }
 
 template <int PT, int NB>
-static int launch_pool_squeeze(hipStream_t s, const float *src, int n, int T, int C, int P, const float *wgt, const float *bias, int S, float *dst,
-                               int dH, int dW, int dC, int off_y, int off_x, const float *ring, int live_lo, int live_n)
+static int launch_pool_squeeze(hipStream_t s, const float *src, int n, int T, int C, int P, const float *wgt, const float *bias, int S, const Place &pl,
+                               const float *ring, int live_lo, int live_n)
 {
     int blocks = n < 256 * 8 ? n : 256 * 8;          // persistent over the segments beyond a few workgroups per CU
-    hipLaunchKernelGGL((k_pool_squeeze<PT, NB>), dim3((unsigned)blocks), dim3(64 * PT * NB), 0, s, src, n, T, C, P, wgt, bias, S, dst, dH, dW, dC,
-                       off_y, off_x, ring, live_lo, live_n);
+    hipLaunchKernelGGL((k_pool_squeeze<PT, NB>), dim3((unsigned)blocks), dim3(64 * PT * NB), 0, s, src, n, T, C, P, wgt, bias, S, pl.dst, pl.dH, pl.dW,
+                       pl.dC, pl.off_y, pl.off_x, ring, live_lo, live_n);
     return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
 }
 
@@ -131,24 +121,24 @@ int32_t swk_nhwc_maxpool3s2_conv1x1_bias_relu_place(void *stream, const float *s
                                                     const float *bias, int32_t cout, float *dst, int32_t dH, int32_t dW, int32_t dC,
                                                     int32_t off_y, int32_t off_x, const float *ring, int32_t live_lo, int32_t live_n)
 {
-    if (!src || !weight || !bias || !dst || n < 1 || t < 3 || cin < 32 || (cin & 31) || cout < 4 || (cout & 3) || cout > 64 || (dC & 3) ||
-        off_y < 0 || off_x < 0 || (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)weight | (uintptr_t)bias) & 15))
+    const int P = (t - 3) / 2 + 1;
+    const swk::Place pl{dst, dH, dW, dC, off_y, off_x, 0};          // no c_off: the squeeze output starts at channel 0
+    // beyond the placement: the shapes the kernel is built for (32-channel chunks, at most 96 pooled pixels and 64 outputs per
+    // segment), float4 loads of src, weight and -- read from global memory here -- bias
+    if (!src || !weight || !bias || n < 1 || t < 3 || cin < 32 || (cin & 31) || cout > 64 || P * P > 96 || !swk::place_ok(pl, P, P, cout, true) ||
+        (((uintptr_t)src | (uintptr_t)weight | (uintptr_t)bias) & 15))
         return SWK_ERR_ARG;
     if (!ring) { ring = src; live_lo = 0; live_n = t; }
     if (live_lo < 0 || live_n < 0 || live_lo + live_n > t || ((uintptr_t)ring & 15)) return SWK_ERR_ARG;
-    const int P = (t - 3) / 2 + 1;
-    if (off_y + P > dH || off_x + P > dW || cout > dC || P * P > 96) return SWK_ERR_ARG;
     using namespace swk;
     hipStream_t s = (hipStream_t)stream;
     const int PT = (P * P + 31) / 32, NB = (cout + 31) / 32;
-#define SWK_PS_ARGS s, src, n, t, cin, P, weight, bias, cout, dst, dH, dW, dC, off_y, off_x, ring, live_lo, live_n
-    if (PT == 1 && NB == 1) return launch_pool_squeeze<1, 1>(SWK_PS_ARGS);
-    if (PT == 2 && NB == 1) return launch_pool_squeeze<2, 1>(SWK_PS_ARGS);
-    if (PT == 3 && NB == 1) return launch_pool_squeeze<3, 1>(SWK_PS_ARGS);
-    if (PT == 1 && NB == 2) return launch_pool_squeeze<1, 2>(SWK_PS_ARGS);
-    if (PT == 2 && NB == 2) return launch_pool_squeeze<2, 2>(SWK_PS_ARGS);
-    if (PT == 3 && NB == 2) return launch_pool_squeeze<3, 2>(SWK_PS_ARGS);
-#undef SWK_PS_ARGS
+    if (PT == 1 && NB == 1) return launch_pool_squeeze<1, 1>(s, src, n, t, cin, P, weight, bias, cout, pl, ring, live_lo, live_n);
+    if (PT == 2 && NB == 1) return launch_pool_squeeze<2, 1>(s, src, n, t, cin, P, weight, bias, cout, pl, ring, live_lo, live_n);
+    if (PT == 3 && NB == 1) return launch_pool_squeeze<3, 1>(s, src, n, t, cin, P, weight, bias, cout, pl, ring, live_lo, live_n);
+    if (PT == 1 && NB == 2) return launch_pool_squeeze<1, 2>(s, src, n, t, cin, P, weight, bias, cout, pl, ring, live_lo, live_n);
+    if (PT == 2 && NB == 2) return launch_pool_squeeze<2, 2>(s, src, n, t, cin, P, weight, bias, cout, pl, ring, live_lo, live_n);
+    if (PT == 3 && NB == 2) return launch_pool_squeeze<3, 2>(s, src, n, t, cin, P, weight, bias, cout, pl, ring, live_lo, live_n);
     return SWK_ERR_ARG;
 }
 

@@ -14,13 +14,13 @@
 // would be four times the outputs.  Instead the positions run one after the other, M_p is ONE accumulator, and after its
 // last k-step it is added with its coefficient A^T[i][xi] A^T[j][nu] in {0, +1, -1} into the four output accumulators Y_ij.
 //   * workgroup = CG x TGN waves: 32 TGN output tiles (2 x 2 pixels each, of any segments) x all output channels; wave
-//     (cg, tg) owns tile group tg (32 tiles) and NBW column blocks of 32 output channels: Y = 4 x NBW x 16 registers, M = 16.
-//     NBW = 1 is the default: 128 registers, four waves per SIMD (8-wave workgroups for 64 -> 256, 4-wave ones for 32 -> 128;
+//     (cg, tg) owns tile group tg (32 tiles) and ONE column block of 32 output channels: Y = 4 x 16 registers, M = 16:
+//     128 registers, four waves per SIMD (8-wave workgroups for 64 -> 256, 4-wave ones for 32 -> 128;
 //     48 -> 192 has six column blocks and runs as ONE 12-wave workgroup per CU, three waves on every SIMD -- two 6-wave
-//     workgroups do not become co-resident and leave two SIMDs half empty).  NBW = 2 (226 registers, two waves per SIMD)
-//     measured 6 % slower on 64 -> 256 and 15 % on 32 -> 128 (round 2) and is no longer instantiated.
+//     workgroups do not become co-resident and leave two SIMDs half empty).  (Two column blocks per wave, 226 registers and two
+//     waves per SIMD, measured 6 % slower on 64 -> 256 and 15 % on 32 -> 128 in round 2.)
 //   * V_p = B^T d B restricted to position p is a signed sum of FOUR patch pixels.  The workgroup forms V_p for its tiles
-//     once (NBW (tile, 4-channel) items per thread: 4 float4 loads, 3 fmas per component), transposes it into LDS as
+//     once (one (tile, 4-channel) item per thread: 4 float4 loads, 3 fmas per component), transposes it into LDS as
 //     [channel][tile] -- the matrix cores' pixel operand -- double buffered: position p + 1 is staged while p multiplies
 //     (loads issued in the first, transform and LDS store in the last phase of the position).
 //   * U_p streams through LDS by LDS-DMA (global_load_lds_dwordx4: no registers, no ds_write pass) in phases of SPP k-chunks
@@ -36,13 +36,9 @@
 // (profiles/r2_f32_pipe_probe.txt) another 10 %; s_memtime brackets (tools/wino_stamp.py) put a wave's remaining time into
 // the barrier (19 %) and the phase prologue / epilogue; skipping the global loads altogether gains 9 %.
 // Launched on the CALLER's stream (PyTorch's current stream).
-#include "swk_internal.h"
-
-#include <type_traits>
+#include "cnn_common.h"
 
 namespace swk {
-
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 // Diagnostic build only (-DSWK_WINO_STAMP, tools/wino_stamp.py): s_memtime brackets around the parts of a phase, summed per wave
 // and stored to g_wino_stamp[wave][5] by lane 0.  Its fences forbid overlaps the real kernel has: read the shares, not the length.
@@ -62,15 +58,19 @@ __device__ unsigned long long *g_wino_stamp;
 #define SWK_STAMP(k) do { } while (0)
 #endif
 
-template <int NBLK, int NBW, int TGN, int SPP, int WPS, bool PRIV>
-__global__ __launch_bounds__(64 * (NBLK / NBW) * TGN, WPS) void k_wino3x3_relu_place(const float *__restrict__ src, int nseg, int t, int T,
+template <int NBLK, int TGN, int SPP, int WPS, bool PRIV>
+__global__ __launch_bounds__(64 * NBLK * TGN, WPS) void k_wino3x3_relu_place(const float *__restrict__ src, int nseg, int t, int T,
                                                                       const float *__restrict__ w2, const float *__restrict__ bias, int cout,
                                                                       float *__restrict__ dst, int dH, int dW, int dC, int off_y, int off_x,
                                                                       int c_off, FastDiv fTT, FastDiv fT)
 {
     // S k-chunks of 16 channels per position; a phase = SPP of them for one column block: PHS phases per (position, column block),
     // PPOS per position
-    // a wave owns NBW column blocks of 32 output channels (WPS waves per SIMD fit: NBW = 2 -> 2, NBW = 1 -> 4)
+    // The body is written for NBW column blocks of 32 output channels per wave, and NBW is 1: a local constant, not a configuration
+    // (the host filter layout knows one block per wave only).  Its one-trip loops stay because the compiler's output depends on
+    // them: without the ones around the prologue's staging and around the phases every instantiation came out with a differently
+    // laid out prologue, and 48 -> 192 measured 0.6-0.9 % slower (profiles/cnn_common_isa_compare.md).
+    constexpr int NBW = 1;
     constexpr int CG = NBLK / NBW, NW = CG * TGN, NT = 64 * NW, CIN = 8 * NBLK, S = CIN / 16, SLOTS = 32 * TGN, VP = SLOTS + 1, G4 = CIN / 4,
                   NP = 32 * NBLK, CGR = 32 * CG, PHS = S / SPP, PPOS = NBW * PHS;
     // PRIV (one column block per wave, 64 -> 256): every wave copies the 2 KB of filter operands of a phase that it reads itself
@@ -141,40 +141,17 @@ __global__ __launch_bounds__(64 * (NBLK / NBW) * TGN, WPS) void k_wino3x3_relu_p
         q[0] = v.x; q[VP] = v.y; q[2 * VP] = v.z; q[3 * VP] = v.w;
     };
 
-    // ---- filter operands of phase ph = 2 p + h: WPH floats, contiguous in w2, copied as they lie by LDS-DMA; PPW 1 KB pieces per
-    //      wave, addressed by the instruction offset (it advances the global and the LDS address alike).
-    // Written as an asm statement: through __builtin_amdgcn_global_load_lds the compiler treats the copy as an LDS store that
-    // every later ds_read may alias and waits for it (s_waitcnt vmcnt(0)) before the very next operand read -- the copy is then
-    // no longer asynchronous.  The waits are placed by hand instead (wait_copies(), before the barrier that ends a phase).
+    // ---- filter operands of phase ph: WPH floats, contiguous in w2, copied as they lie by LDS-DMA (cnn_common.h), PPW 1 KB pieces
+    //      per wave; the waits are placed by hand, before the barrier that ends a phase ----
     const unsigned wvoff = PRIV ? (unsigned)(lane * 16) : (unsigned)((wave * PPW) * 1024 + lane * 16);
     const unsigned wpiece = __builtin_amdgcn_readfirstlane((unsigned)(wave * PPW) * 1024u);
     const int cg_u = __builtin_amdgcn_readfirstlane(cg);
     auto w_issue = [&](int ph, float *Wb) {
         // shared: the phase's block as it lies; private: this wave's column block of the phase ([phase][cg][512 floats])
         const float *g = PRIV ? w2 + ((int64_t)ph * CG + cg_u) * 512 : w2 + (int64_t)ph * WPH;          // uniform
-        const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)Wb) + wpiece;
-        unsigned keep;
-        if constexpr (PPW == 1)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(wvoff), "s"(l), "s"(g) : "memory");
-        else if constexpr (PPW == 2)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-                         "global_load_lds_dwordx4 %1, %3 offset:1024\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(wvoff), "s"(l), "s"(g) : "memory");
-        else if constexpr (PPW == 3)
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-                         "global_load_lds_dwordx4 %1, %3 offset:1024\n\tglobal_load_lds_dwordx4 %1, %3 offset:2048\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(wvoff), "s"(l), "s"(g) : "memory");
-        else
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-                         "global_load_lds_dwordx4 %1, %3 offset:1024\n\tglobal_load_lds_dwordx4 %1, %3 offset:2048\n\t"
-                         "global_load_lds_dwordx4 %1, %3 offset:3072\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(wvoff), "s"(l), "s"(g) : "memory");
+        lds_dma_copy<PPW>(__builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)Wb) + wpiece, g, wvoff);
     };
-    static_assert(PPW >= 1 && PPW <= 4, "LDS-DMA pieces per wave and phase");
-    // the copies of a phase are issued BEFORE its patch loads: vmcnt(4) retires them and leaves the four patch loads in flight
-    auto wait_copies = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-    auto wait_copies_keep4 = [&]() { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); };
+    // the copies of a phase are issued BEFORE its patch loads: lds_dma_wait<4>() retires them and leaves the four patch loads in flight
     // this lane's operand quads in a phase buffer: [chunk][k half][quad][CGR channels][4]
     const int wlane = PRIV ? wave * (PPW * 256) + ((hh * 2) * 32 + r) * 4 : ((hh * 2) * CGR + cg * 32 + r) * 4;
     constexpr int CB = 32 * NBW;          // output channels of a wave
@@ -190,7 +167,7 @@ __global__ __launch_bounds__(64 * (NBLK / NBW) * TGN, WPS) void k_wino3x3_relu_p
         for (int k = 0; k < NBW; ++k) { stage_issue(0, k); stage_store(0, k, V0); }
         w_issue(0, W0);
     }
-    wait_copies();
+    lds_dma_wait<0>();
     __syncthreads();
     for (; task < ntasks; task += gridDim.x) {
         // ---- this lane's tile as the matrix cores see it: destination of its 2 x 2 outputs ----
@@ -292,8 +269,8 @@ __global__ __launch_bounds__(64 * (NBLK / NBW) * TGN, WPS) void k_wino3x3_relu_p
                     }
                     SWK_STAMP(2);
                     // patch loads issued in this phase and stored in a later one stay in flight across the barrier
-                    if (h == 0 && PHS > 1) wait_copies_keep4();
-                    else wait_copies();
+                    if (h == 0 && PHS > 1) lds_dma_wait<4>();
+                    else lds_dma_wait<0>();
                     SWK_STAMP(3);
                     // shared filter copies: every wave's pieces have landed, the other buffers are free.  Private ones: the
                     // workgroup meets only when the next position's V is complete
@@ -316,13 +293,7 @@ __global__ __launch_bounds__(64 * (NBLK / NBW) * TGN, WPS) void k_wino3x3_relu_p
                         for (int g = 0; g < 4; ++g) {
                             const int c = CB * cg + 32 * nb + 8 * g + 4 * hh;
                             if (c < cout) {
-                                const float4 b4 = *(const float4 *)(lbias + c);
-                                float4 v;
-                                v.x = fmaxf(Y[i][j][nb][4 * g] + b4.x, 0.0f);
-                                v.y = fmaxf(Y[i][j][nb][4 * g + 1] + b4.y, 0.0f);
-                                v.z = fmaxf(Y[i][j][nb][4 * g + 2] + b4.z, 0.0f);
-                                v.w = fmaxf(Y[i][j][nb][4 * g + 3] + b4.w, 0.0f);
-                                *(float4 *)(q + 32 * nb + 8 * g) = v;
+                                store_bias_relu(q + 32 * nb + 8 * g, Y[i][j][nb], g, *(const float4 *)(lbias + c));
                             }
                         }
                 }
@@ -337,20 +308,17 @@ __global__ __launch_bounds__(64 * (NBLK / NBW) * TGN, WPS) void k_wino3x3_relu_p
 #endif
 }
 
-// column blocks per wave of the configuration a shape runs on (the filter layout depends on it): one for every Fire shape
-static int wino_nbw(int, int) { return 1; }
-// private per-wave filter slices (their own layout): the 64 -> 256 configuration with one column block per wave
-static bool wino_priv(int cin, int cout) { return cin == 64 && cout == 256 && wino_nbw(cin, cout) == 1; }
+// private per-wave filter slices (their own layout): the 64 -> 256 configuration
+static bool wino_priv(int cin, int cout) { return cin == 64 && cout == 256; }
 
-template <int NBLK, int NBW, int TGN, int SPP, int WPS, bool PRIV>
-static int launch_wino3x3(hipStream_t s, const float *src, int n, int t, const float *w2, const float *bias, int cout, float *dst, int dH,
-                          int dW, int dC, int off_y, int off_x, int c_off)
+template <int NBLK, int TGN, int SPP, int WPS, bool PRIV>
+static int launch_wino3x3(hipStream_t s, const float *src, int n, int t, const float *w2, const float *bias, int cout, const Place &pl)
 {
-    constexpr int CIN = 8 * NBLK, SLOTS = 32 * TGN, NT = 64 * (NBLK / NBW) * TGN, CGR = 32 * (NBLK / NBW);
+    constexpr int CIN = 8 * NBLK, SLOTS = 32 * TGN, NT = 64 * NBLK * TGN, CGR = 32 * NBLK;
     constexpr int WPH = PRIV ? (NT / 64) * 16 * SPP * 32 : 16 * SPP * CGR;
     const size_t lds = (size_t)(2 * WPH + 2 * CIN * (SLOTS + 1) + 32 * NBLK) * sizeof(float);
     static unsigned long long attr_mask = 0;
-    if (!ensure_dyn_lds((const void *)k_wino3x3_relu_place<NBLK, NBW, TGN, SPP, WPS, PRIV>, 160 * 1024 - 256, attr_mask)) return SWK_ERR_HIP;
+    if (!ensure_dyn_lds((const void *)k_wino3x3_relu_place<NBLK, TGN, SPP, WPS, PRIV>, 160 * 1024 - 256, attr_mask)) return SWK_ERR_HIP;
     if ((int64_t)n * t * t * CIN * 4 >= ((int64_t)1 << 32)) return SWK_ERR_CAPACITY;          // 32-bit byte offsets into src (and tile indices)
     const int T = (t - 2 + 1) / 2;
     const int64_t ntiles = (int64_t)n * T * T;
@@ -359,8 +327,8 @@ static int launch_wino3x3(hipStream_t s, const float *src, int n, int t, const f
     // are independent -- one's phase change (drain, update, barrier, first operand reads) is covered by the other's MFMAs
     const int64_t cap = 256 * ((4 * WPS) / (NT / 64));
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL((k_wino3x3_relu_place<NBLK, NBW, TGN, SPP, WPS, PRIV>), dim3((unsigned)blocks), dim3(NT), lds, s, src, n, t, T, w2, bias, cout, dst, dH, dW,
-                       dC, off_y, off_x, c_off, FastDiv((unsigned)(T * T)), FastDiv((unsigned)T));
+    hipLaunchKernelGGL((k_wino3x3_relu_place<NBLK, TGN, SPP, WPS, PRIV>), dim3((unsigned)blocks), dim3(NT), lds, s, src, n, t, T, w2, bias, cout, pl.dst,
+                       pl.dH, pl.dW, pl.dC, pl.off_y, pl.off_x, pl.c_off, FastDiv((unsigned)(T * T)), FastDiv((unsigned)T));
     return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
 }
 
@@ -380,29 +348,23 @@ int32_t swk_winograd_f2x2_3x3_weights(const float *weight, int32_t cout, int32_t
 {
     if (!weight || !out || cout < 1 || cin < 16 || (cin & 15)) return SWK_ERR_ARG;
     // operand layout of k_wino3x3_relu_place, input channel = 16 chunk + 8 (k half) + 4 quad + j, output channels padded to whole
-    // column blocks; NBW = column blocks per wave of the kernel configuration this shape runs on (see the loop below)
+    // column blocks of 32
     const bool priv = swk::wino_priv(cin, cout);
-    const int NBW = swk::wino_nbw(cin, cout), CB = 32 * NBW, CG = (cout + CB - 1) / CB, CGR = 32 * CG, S = cin / 16;
-    static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-    for (int64_t i = 0, e = (int64_t)16 * cin * NBW * CGR; i < e; ++i) out[i] = 0.0f;
+    const int CG = (cout + 31) / 32, CGR = 32 * CG, S = cin / 16;
+    for (int64_t i = 0, e = (int64_t)16 * cin * CGR; i < e; ++i) out[i] = 0.0f;
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci) {
-            const float *g = weight + ((int64_t)co * cin + ci) * 9;
-            double tmp[4][3], U[4][4];
-            for (int a = 0; a < 4; ++a)
-                for (int c = 0; c < 3; ++c) tmp[a][c] = G[a][0] * g[c] + G[a][1] * g[3 + c] + G[a][2] * g[6 + c];
-            for (int a = 0; a < 4; ++a)
-                for (int c = 0; c < 4; ++c) U[a][c] = tmp[a][0] * G[c][0] + tmp[a][1] * G[c][1] + tmp[a][2] * G[c][2];
+            double U[4][4];
+            swk::winograd_U(weight + ((int64_t)co * cin + ci) * 9, U);
             const int sub = ci >> 4, hh = (ci >> 3) & 1, q = (ci >> 2) & 1, j = ci & 3;
-            const int cg = co / CB, h = (co % CB) >> 5, r = co & 31;
+            const int cg = co >> 5, r = co & 31;
             for (int p = 0; p < 16; ++p) {
                 int64_t idx;
                 if (priv) {              // [p][chunk][cg][k half][quad][r][4]: a wave's 2 KB of a phase are contiguous
                     idx = ((int64_t)p * S + sub) * CG + cg;
                     idx = ((idx * 2 + hh) * 2 + q) * 32 + r;
-                } else {                 // [p][h][chunk][k half][quad][cg * 32 + r][4]: the phase's block as it sits in LDS
-                    idx = (int64_t)p * NBW + h;
-                    idx = idx * S + sub;
+                } else {                 // [p][chunk][k half][quad][cg * 32 + r][4]: the phase's block as it sits in LDS
+                    idx = (int64_t)p * S + sub;
                     idx = (idx * 2 + hh) * 2 + q;
                     idx = idx * CGR + cg * 32 + r;
                 }
@@ -416,20 +378,19 @@ int32_t swk_nhwc_conv3x3_winograd_bias_relu_place(void *stream, const float *src
                                                   const float *bias, int32_t cout, float *dst, int32_t dH, int32_t dW, int32_t dC,
                                                   int32_t off_y, int32_t off_x, int32_t c_off)
 {
-    if (!src || !weight_w || !bias || !dst || n < 1 || t < 3 || cout < 4 || (cout & 3) || (dC & 3) || (c_off & 3) || off_y < 0 || off_x < 0 ||
-        off_y + t - 2 > dH || off_x + t - 2 > dW || c_off < 0 || c_off + cout > dC || (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)weight_w) & 15))
+    const swk::Place pl{dst, dH, dW, dC, off_y, off_x, c_off};
+    // beyond the placement: float4 patch loads and LDS-DMA filter copies (src, weight_w 16-byte aligned)
+    if (!src || !weight_w || !bias || n < 1 || t < 3 || !swk::place_ok(pl, t - 2, t - 2, cout, true) || (((uintptr_t)src | (uintptr_t)weight_w) & 15))
         return SWK_ERR_ARG;
     using namespace swk;
     hipStream_t s = (hipStream_t)stream;
     // the squeeze ratio of SqueezeNet's Fire modules: 8 input channels per 32 output channels
-#define SWK_W3_ARGS s, src, n, t, weight_w, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off
-    if (cin == 16 && cout == 64) return launch_wino3x3<2, 1, 2, 1, 4, false>(SWK_W3_ARGS);
-    if (cin == 32 && cout == 128) return launch_wino3x3<4, 1, 1, 1, 4, false>(SWK_W3_ARGS);
+    if (cin == 16 && cout == 64) return launch_wino3x3<2, 2, 1, 4, false>(s, src, n, t, weight_w, bias, cout, pl);
+    if (cin == 32 && cout == 128) return launch_wino3x3<4, 1, 1, 4, false>(s, src, n, t, weight_w, bias, cout, pl);
     // (48 -> 192: one k-chunk per phase since round 4 -- three times the barriers of SPP = 3, a third of the filter buffers: 3 % faster;
     //  the other shapes re-checked against 4 / 8-wave workgroups and two chunks per phase: as they are)
-    if (cin == 48 && cout == 192) return launch_wino3x3<6, 1, 2, 1, 3, false>(SWK_W3_ARGS);
-    if (cin == 64 && cout == 256) return launch_wino3x3<8, 1, 1, 1, 4, true>(SWK_W3_ARGS);
-#undef SWK_W3_ARGS
+    if (cin == 48 && cout == 192) return launch_wino3x3<6, 2, 1, 3, false>(s, src, n, t, weight_w, bias, cout, pl);
+    if (cin == 64 && cout == 256) return launch_wino3x3<8, 1, 1, 4, true>(s, src, n, t, weight_w, bias, cout, pl);
     return SWK_ERR_ARG;
 }
 

@@ -31,14 +31,9 @@
 // Twice the tiles per filter byte would need 128 x 256 outputs in one CU's registers (Y alone fills the register file) or V formed
 // twice; see DESIGN section 10.
 // Launched on the CALLER's stream.
-#include "swk_internal.h"
-
-#include <cstring>
+#include "cnn_common.h"
 
 namespace swk {
-
-typedef float f16v __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // k-steps (16 input channels) per filter phase of a shape: the host layout depends on it
 static int wino_bf16s_spp(int cin, int cout) { return cin == 64 && cout == 256 ? 2 : cin / 16; }
@@ -107,10 +102,9 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float v = __builtin_fmaf(__builtin_fmaf(d[e], sn, c[e]), sx, __builtin_fmaf(b[e], sn, a[e]));
-                const __bf16 x1 = (__bf16)v;
-                const float r1 = v - (float)x1;
-                const __bf16 x2 = (__bf16)r1;
-                v1[4 * h + e] = x1; v2[4 * h + e] = x2; v3[4 * h + e] = (__bf16)(r1 - (float)x2);
+                __bf16 x1, x2, x3;
+                split3(v, x1, x2, x3);
+                v1[4 * h + e] = x1; v2[4 * h + e] = x2; v3[4 * h + e] = x3;
             }
         }
         uint4 *q = Vn + sg * VT + sslot;
@@ -119,23 +113,16 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
         q[2 * KG * VT] = __builtin_bit_cast(uint4, v3);
     };
 
-    // ---- this wave's filter slice of phase g: WPB contiguous bytes of wu, copied as they lie by LDS-DMA, three 1 KB pieces (the parts)
-    //      per k-step, addressed by the instruction offset (it advances the global and the LDS address alike) ----
+    // ---- this wave's filter slice of phase g: WPB contiguous bytes of wu, copied as they lie by LDS-DMA (cnn_common.h), three 1 KB
+    //      pieces (the parts) per k-step ----
     const unsigned wvoff = (unsigned)(lane * 16);
     auto w_issue = [&](int g, int buf) {
         const char *gp = (const char *)wu + ((int64_t)g * NW + __builtin_amdgcn_readfirstlane(wave)) * WPB;          // uniform
         const unsigned l = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(Wl + (buf * NW + wave) * WPB));
 #pragma unroll
-        for (int sub = 0; sub < SPP; ++sub) {
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-                         "global_load_lds_dwordx4 %1, %3 offset:1024\n\tglobal_load_lds_dwordx4 %1, %3 offset:2048\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(wvoff), "s"(l + sub * 3072u), "s"(gp + sub * 3072) : "memory");
-        }
+        for (int sub = 0; sub < SPP; ++sub) lds_dma_copy<3>(l + sub * 3072u, gp + sub * 3072, wvoff);
     };
-    // the copies of a phase are issued BEFORE the patch loads: vmcnt(8) retires them and leaves the eight patch loads in flight
-    auto wait_copies = [&]() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-    auto wait_copies_keep8 = [&]() { asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); };
+    // the copies of a phase are issued BEFORE the patch loads: lds_dma_wait<8>() retires them and leaves the eight patch loads in flight
 
     int64_t task = blockIdx.x;
     if (task < ntasks) {
@@ -144,7 +131,7 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
         stage_store(0, V0);
         w_issue(0, 0);
     }
-    wait_copies();
+    lds_dma_wait<0>();
     __syncthreads();
     for (; task < ntasks; task += gridDim.x) {
         // ---- this lane's two tiles as the matrix cores see them: destinations of their 2 x 2 outputs ----
@@ -232,8 +219,8 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
                         }
                 }
                 // this wave's slice of the next phase has landed (patch loads issued in a first phase of several stay in flight)
-                if (h == 0 && PHS > 1) wait_copies_keep8();
-                else wait_copies();
+                if (h == 0 && PHS > 1) lds_dma_wait<8>();
+                else lds_dma_wait<0>();
                 // the next position's V is complete, this one's buffer is free
                 if (h == PHS - 1) __syncthreads();
             }
@@ -251,15 +238,7 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
 #pragma unroll
                     for (int gq = 0; gq < 4; ++gq) {
                         const int c = 32 * wave + 8 * gq + 4 * hh;
-                        if (c < cout) {
-                            const float4 b4 = *(const float4 *)(lbias + c);
-                            float4 v;
-                            v.x = fmaxf(Y[i][j][tg][4 * gq] + b4.x, 0.0f);
-                            v.y = fmaxf(Y[i][j][tg][4 * gq + 1] + b4.y, 0.0f);
-                            v.z = fmaxf(Y[i][j][tg][4 * gq + 2] + b4.z, 0.0f);
-                            v.w = fmaxf(Y[i][j][tg][4 * gq + 3] + b4.w, 0.0f);
-                            *(float4 *)(q + 8 * gq) = v;
-                        }
+                        if (c < cout) store_bias_relu(q + 8 * gq, Y[i][j][tg], gq, *(const float4 *)(lbias + c));
                     }
                 }
         }
@@ -267,8 +246,7 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
 }
 
 template <int NBLK, int SPP>
-static int launch_wino3x3_bf16s(hipStream_t s, const float *src, int n, int t, const uint16_t *wu, const float *bias, int cout, float *dst,
-                                int dH, int dW, int dC, int off_y, int off_x, int c_off)
+static int launch_wino3x3_bf16s(hipStream_t s, const float *src, int n, int t, const uint16_t *wu, const float *bias, int cout, const Place &pl)
 {
     constexpr int NW = NBLK, KG = NBLK, CIN = 8 * NBLK, VT = 64 + WinoVPad<KG>::value;
     const size_t lds = (size_t)2 * NW * SPP * 3 * 1024 + (size_t)2 * 3 * KG * VT * 16 + 32 * NBLK * sizeof(float);
@@ -283,8 +261,8 @@ static int launch_wino3x3_bf16s(hipStream_t s, const float *src, int n, int t, c
     const int64_t by_lds = (int64_t)((160 * 1024 - 256) / lds), by_waves = 8 / NW;
     const int64_t per_cu = by_waves < 1 ? 1 : (by_lds < by_waves ? by_lds : by_waves);
     if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-    hipLaunchKernelGGL((k_wino3x3_bf16s_relu_place<NBLK, SPP>), dim3((unsigned)blocks), dim3(64 * NW), lds, s, src, n, t, T, wu, bias, cout, dst,
-                       dH, dW, dC, off_y, off_x, c_off, FastDiv((unsigned)(T * T)), FastDiv((unsigned)T));
+    hipLaunchKernelGGL((k_wino3x3_bf16s_relu_place<NBLK, SPP>), dim3((unsigned)blocks), dim3(64 * NW), lds, s, src, n, t, T, wu, bias, cout, pl.dst,
+                       pl.dH, pl.dW, pl.dC, pl.off_y, pl.off_x, pl.c_off, FastDiv((unsigned)(T * T)), FastDiv((unsigned)T));
     return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
 }
 
@@ -300,36 +278,17 @@ int32_t swk_winograd_f2x2_3x3_weights_bf16s(const float *weight, int32_t cout, i
     // channels padded to whole column blocks: [p][phase][cb][k-step of the phase][part][lane][8], a wave's slice of a phase contiguous
     const int spp = swk::wino_bf16s_spp(cin, cout), S = cin / 16, PHS = S / spp, CG = (cout + 31) / 32;
     if (S % spp) return SWK_ERR_ARG;
-    static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
     for (int64_t i = 0, e = (int64_t)16 * cin * CG * 32 * 3; i < e; ++i) out[i] = 0;
-    auto bf16_rne = [](float f, float &back) -> uint16_t {          // round to nearest even (finite values)
-        uint32_t u;
-        memcpy(&u, &f, 4);
-        u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
-        memcpy(&back, &u, 4);
-        return (uint16_t)(u >> 16);
-    };
     for (int co = 0; co < cout; ++co)
         for (int ci = 0; ci < cin; ++ci) {
-            // U = G g G^T in float64, rounded to float32: the same operations as swk_winograd_f2x2_3x3_weights
-            const float *g = weight + ((int64_t)co * cin + ci) * 9;
-            double tmp[4][3], U[4][4];
-            for (int a = 0; a < 4; ++a)
-                for (int c = 0; c < 3; ++c) tmp[a][c] = G[a][0] * g[c] + G[a][1] * g[3 + c] + G[a][2] * g[6 + c];
-            for (int a = 0; a < 4; ++a)
-                for (int c = 0; c < 4; ++c) U[a][c] = tmp[a][0] * G[c][0] + tmp[a][1] * G[c][1] + tmp[a][2] * G[c][2];
+            double U[4][4];          // rounded to float32 as in swk_winograd_f2x2_3x3_weights, then split
+            swk::winograd_U(weight + ((int64_t)co * cin + ci) * 9, U);
             const int s = ci >> 4, ph = s / spp, sub = s % spp, lane = ((ci >> 3) & 1) * 32 + (co & 31), j = ci & 7, cb = co >> 5;
             for (int p = 0; p < 16; ++p) {
-                const float u = (float)U[p >> 2][p & 3];
-                float b1, b2, b3;
-                const uint16_t h1 = bf16_rne(u, b1);
-                const float r1 = u - b1;
-                const uint16_t h2 = bf16_rne(r1, b2);
-                const uint16_t h3 = bf16_rne(r1 - b2, b3);
+                uint16_t part[3];
+                swk::split3_host((float)U[p >> 2][p & 3], part);
                 const int64_t blk = (((int64_t)p * PHS + ph) * CG + cb) * spp + sub;
-                out[((blk * 3 + 0) * 64 + lane) * 8 + j] = h1;
-                out[((blk * 3 + 1) * 64 + lane) * 8 + j] = h2;
-                out[((blk * 3 + 2) * 64 + lane) * 8 + j] = h3;
+                for (int k = 0; k < 3; ++k) out[((blk * 3 + k) * 64 + lane) * 8 + j] = part[k];
             }
         }
     return SWK_OK;
@@ -339,17 +298,16 @@ int32_t swk_nhwc_conv3x3_winograd_bf16s_bias_relu_place(void *stream, const floa
                                                         const uint16_t *weight_s, const float *bias, int32_t cout, float *dst, int32_t dH,
                                                         int32_t dW, int32_t dC, int32_t off_y, int32_t off_x, int32_t c_off)
 {
-    if (!src || !weight_s || !bias || !dst || n < 1 || t < 3 || cout < 4 || (cout & 3) || (dC & 3) || (c_off & 3) || off_y < 0 || off_x < 0 ||
-        off_y + t - 2 > dH || off_x + t - 2 > dW || c_off < 0 || c_off + cout > dC || (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)weight_s) & 15))
+    const swk::Place pl{dst, dH, dW, dC, off_y, off_x, c_off};
+    // beyond the placement: float4 patch loads and LDS-DMA filter copies (src, weight_s 16-byte aligned)
+    if (!src || !weight_s || !bias || n < 1 || t < 3 || !swk::place_ok(pl, t - 2, t - 2, cout, true) || (((uintptr_t)src | (uintptr_t)weight_s) & 15))
         return SWK_ERR_ARG;
     using namespace swk;
     hipStream_t s = (hipStream_t)stream;
-#define SWK_W3S_ARGS s, src, n, t, weight_s, bias, cout, dst, dH, dW, dC, off_y, off_x, c_off
-    if (cin == 16 && cout == 64) return launch_wino3x3_bf16s<2, 1>(SWK_W3S_ARGS);
-    if (cin == 32 && cout == 128) return launch_wino3x3_bf16s<4, 2>(SWK_W3S_ARGS);
-    if (cin == 48 && cout == 192) return launch_wino3x3_bf16s<6, 3>(SWK_W3S_ARGS);
-    if (cin == 64 && cout == 256) return launch_wino3x3_bf16s<8, 2>(SWK_W3S_ARGS);
-#undef SWK_W3S_ARGS
+    if (cin == 16 && cout == 64) return launch_wino3x3_bf16s<2, 1>(s, src, n, t, weight_s, bias, cout, pl);
+    if (cin == 32 && cout == 128) return launch_wino3x3_bf16s<4, 2>(s, src, n, t, weight_s, bias, cout, pl);
+    if (cin == 48 && cout == 192) return launch_wino3x3_bf16s<6, 3>(s, src, n, t, weight_s, bias, cout, pl);
+    if (cin == 64 && cout == 256) return launch_wino3x3_bf16s<8, 2>(s, src, n, t, weight_s, bias, cout, pl);
     return SWK_ERR_ARG;
 }
 

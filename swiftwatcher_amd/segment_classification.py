@@ -1,7 +1,8 @@
 """Drop-in for the reference's swiftwatcher/segment_classification.py (SegmentClassifier :14-44,
 setup_model :47-67): same constructor and call signature, same preprocessing chain, same
 keep-if-argmax==1 rule and 1..k relabelling -- with the SqueezeNet-1.0 forward batched over all
-segments of the call and run by PyTorch-ROCm (MIOpen picks the MFMA convolution kernels).
+segments of the call; PyTorch-ROCm holds the tensors and streams, and the convolutions run on the library's own
+HIP kernels (csrc/cnn_*.hip; MIOpen only with SWK_OWN_CNN_KERNELS=0, the tests' cross-check).
 
 Differences from the reference, all deliberate:
   * the network is built in plain torch (torchvision is not needed) and is NOT fetched from the
