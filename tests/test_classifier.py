@@ -313,7 +313,8 @@ def test_fused_conv1x1_kernel_against_torch(split_bf16):
     swk_nhwc_conv1x1_bias_relu_place (convolution + bias + ReLU + placement on the f32 matrix cores) against
     torch.nn.functional.conv2d on the shapes the Fire modules use and on ragged ones (pixel count not a multiple of 32,
     output channels not a multiple of 32, crop inside the source, channel offset in the destination).  float32 in a
-    different summation order: 2e-5 relative to the output scale."""
+    different summation order: 2e-5 relative to the output scale.  (Placement and agreement with MIOpen only: 2e-5 is some 300 float32
+    ulps.  That the kernel is float32-accurate is held against float64 in tests/test_cnn_accuracy.py.)"""
     import ctypes
     from swiftwatcher_amd import _lib
     lib = _lib.load()
@@ -364,7 +365,8 @@ def test_split_bf16_expand_kernel_is_float32_accurate():
     """k_expand1x1_bf16s (off by default; swk_set_cnn_tuning knob 1): every float32 product as six bf16 x bf16 MFMA products of three-way split
     operands, accumulated in float32.  Against float64 its error must be that of a float32 multiply-add chain -- it is held to the error of the
     float32 kernel (swk_set_cnn_tuning knob 1 = 0) on the same data, with a floor of 4e-7 of the output scale -- on post-ReLU
-    activations, on activations with a large dynamic range, and with a ragged last tile; and the two kernels place the same block."""
+    activations, on activations with a large dynamic range, and with a ragged last tile; and the two kernels place the same block.
+    (Bounded here by the float32 kernel's own error; both kernels against a CPU float32 yardstick and float64: tests/test_cnn_accuracy.py.)"""
     import ctypes
     from swiftwatcher_amd import _lib
     lib = _lib.load()
@@ -401,7 +403,8 @@ def test_split_bf16_expand_kernel_is_float32_accurate():
 def test_own_kernels_match_miopen_path_at_bench_batch(tmp_path):
     """The cropped network on the library's own kernels (conv1, 1 x 1, Winograd 3 x 3, pools) against the same network with every
     convolution on MIOpen, at a ragged batch of the bench's size (2,377 rows: row tiles, Winograd tasks and workgroups that end in
-    the middle of a segment) and at a single row; then the direct 3 x 3 kernel in place of the Winograd one."""
+    the middle of a segment) and at a single row; then the direct 3 x 3 kernel in place of the Winograd one.  (Both sides are float32 on
+    the GPU; every route against a float64 network: tests/test_cnn_accuracy.py::test_forward_against_float64_network.)"""
     from swiftwatcher_amd.segment_classification import SegmentClassifier
     from oracle import classifier_ref as ref
     path = tmp_path / "w.pt"
@@ -429,7 +432,8 @@ def test_own_kernels_match_miopen_path_at_bench_batch(tmp_path):
 def test_fused_conv1_kernel_against_torch():
     """swk_nhwc_conv7x7s2_bias_relu (the 7 x 7 stride-2 first convolution + bias + ReLU on the f32 matrix cores, patch rows split
     between the MFMA's k halves) against torch.nn.functional.conv2d: the cropped network's 40 x 40 window, a crop inside a larger
-    image, batches that do not fill the last row tile."""
+    image, batches that do not fill the last row tile.  (2e-5 against another float32 convolution; float32 accuracy against float64:
+    tests/test_cnn_accuracy.py.)"""
     import ctypes
     from swiftwatcher_amd import _lib
     lib = _lib.load()
@@ -457,7 +461,7 @@ def test_fused_conv3x3_kernel_against_torch():
     """swk_nhwc_conv3x3_bias_relu_place (valid 3 x 3 convolution over the squeeze tile + bias + ReLU + placement behind the
     expand1x1 channels, weights streamed through LDS) against torch.nn.functional.conv2d: every (channels, tile) shape the
     Fire modules use, batches whose pixel count is not a multiple of the row tiles, and a channel count that is not a
-    multiple of 32."""
+    multiple of 32.  (2e-5 against another float32 convolution; float32 accuracy against float64: tests/test_cnn_accuracy.py.)"""
     import ctypes
     from swiftwatcher_amd import _lib
     lib = _lib.load()
@@ -531,7 +535,8 @@ def test_winograd_conv3x3_kernel_against_torch():
     """swk_nhwc_conv3x3_winograd_bias_relu_place (F(2x2, 3x3) on the f32 matrix cores) against torch.nn.functional.conv2d and
     against the direct kernel, on the three Fire shapes it takes: even and odd output sizes (the odd one computes a half-used
     last tile row / column whose patch reaches past the tile), batches that do not fill the last workgroup task, one segment.
-    Tolerance 1e-5 of the output scale (the transform adds a few roundings to the direct kernel's 2e-5 bound... measured 2e-6)."""
+    Tolerance 1e-5 of the output scale (the transform adds a few roundings to the direct kernel's 2e-5 bound... measured 2e-6).
+    (Against float64 and a float32 restatement of F(2x2, 3x3), bit-exact on integer inputs: tests/test_cnn_accuracy.py.)"""
     import ctypes
     from swiftwatcher_amd import _lib
     lib = _lib.load()
@@ -789,7 +794,8 @@ def test_head_kernel_against_torch_and_batch_independence():
 def test_fused_maxpool_squeeze_kernel_against_torch():
     """swk_nhwc_maxpool3s2_conv1x1_bias_relu_place (MaxPool2d(3, 2) + a Fire module's squeeze + bias + ReLU + placement as one kernel)
     against torch on the network's three pool -> squeeze pairs (96 -> 16 on 17 x 17, 256 -> 32 on 17 x 17, 512 -> 64 on 19 x 19) and
-    on ragged ones; the pooled values are exact, the product is float32 in another summation order: 2e-5 of the output scale."""
+    on ragged ones; the pooled values are exact, the product is float32 in another summation order: 2e-5 of the output scale.
+    (Float32 accuracy against float64, with and without the shared ring: tests/test_cnn_accuracy.py.)"""
     import ctypes
     from swiftwatcher_amd import _lib
     lib = _lib.load()

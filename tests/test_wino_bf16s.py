@@ -120,7 +120,8 @@ CASES = [  # n, cin, cout, t, dH, off, dC, c_off (those of test_winograd_conv3x3
 def test_split_winograd_kernel_is_float32_accurate(spread):
     """swk_nhwc_conv3x3_winograd_bf16s_bias_relu_place against a float64 convolution: its error is at most 1.5 x the float32 Winograd
     kernel's on the same data, or 4e-7 of the output scale; activations spread over 1e4 in the second run.  The sentinel outside the
-    placed block is untouched, and a segment's outputs do not depend on the batch it is in."""
+    placed block is untouched, and a segment's outputs do not depend on the batch it is in.  (The bound here is the float32 kernel's own
+    error; both kernels against float64 and a CPU float32 F(2x2, 3x3), and bit-exact on integer inputs: tests/test_cnn_accuracy.py.)"""
     lib = _lib()
     dev = torch.device("cuda", 0)
     g = torch.Generator(device="cpu").manual_seed(17 + spread)
