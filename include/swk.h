@@ -61,7 +61,9 @@ typedef struct swk_params {
     double  lmbda;            /* IALM lambda = 0.01          image_filtering.py:256 */
     double  tol;              /* IALM tolerance = 0.001      image_filtering.py:256 */
     int32_t maxiter;          /* IALM max iterations = 100   image_filtering.py:257 */
-    int32_t bil_d;            /* bilateral diameter = 7      data_structures.py:194 */
+    int32_t bil_d;            /* bilateral diameter = 7      data_structures.py:194.  The batch calls and swk_bilateral_u8 run
+                                 radius bil_d / 2 = 1..4 (bil_d 2..9); bil_d <= 0: radius lrint(1.5 * bil_sigma_space), at
+                                 least 1, as OpenCV derives it.  A radius above 4 is SWK_ERR_ARG. */
     double  bil_sigma_color;  /* = 15                        data_structures.py:194 */
     double  bil_sigma_space;  /* = 1                         data_structures.py:194 */
     int32_t bil_fma;          /* 0: sum += v*w (mul, add); 1: fused multiply-add.

@@ -150,7 +150,6 @@ __device__ __forceinline__ int clampi(int p, int len) { return p < 0 ? 0 : (p >=
 
 constexpr int kMaxTaps = 81;   // radius <= 4 (d <= 9)
 constexpr int kTH = 32, kTW = 64;        // output tile of the tiled kernels
-constexpr int kHalo = 5;                 // fused kernel: bilateral radius 3 + erosion 1 + dilation 1
 
 // Generic bilateral (any radius <= 4), one thread per pixel, global reads (L1/L2 absorb the reuse).
 // Stage-level entry point; the hot path uses the fused tile kernel below.
@@ -333,26 +332,37 @@ void launch_open3x3(hipStream_t s, const uint8_t *src, int F, int H, int W, uint
 }
 
 // ---------------------------------------------------------------------------------
-// Fused hot-path kernel: bilateral (radius 3, 29 taps) -> to-zero threshold -> 3x3 opening, one 32x64 output
-// tile per workgroup.  Opening needs the thresholded image on a 2-px ring, the bilateral filter the sparse image
-// 3 px beyond that: a 42-row source tile in LDS (80 columns: the window starts 8 px left of the tile so interior
-// tiles load it as aligned dwords).  The stage is instruction-bound, so the work is made as sparse as the data:
+// Fused hot-path kernel: bilateral (radius R = 1..4; the reference's d = 7 is R = 3, 29 taps) -> to-zero threshold -> 3x3
+// opening, one 32x64 output tile per workgroup.  Opening needs the thresholded image on a 2-px ring, the bilateral filter the
+// sparse image R px beyond that: a source tile of 32 + 2 (R + 2) rows in LDS, whose window starts a multiple of 4 px left of the
+// tile so interior tiles load it as aligned dwords (R = 3: 42 rows, 80 columns from 8 px left of the tile).  The stage is
+// instruction-bound, so the work is made as sparse as the data:
 //   * outputs are pre-cleared and a tile whose source window is all zero ends right after loading it;
-//   * the nonzero pixels of the source tile are kept as one 80-bit mask per row; shifts and ORs of those masks give
-//     the ring cells whose 7x7 neighbourhood holds any nonzero pixel, and only those cells -- listed from the set
-//     bits -- run the 29-tap loop (a cell with an all-zero neighbourhood filters to 0);
+//   * the nonzero pixels of the source tile are kept as one bit mask per row; shifts and ORs of those masks give the ring
+//     cells whose (2R+1) x (2R+1) neighbourhood holds any nonzero pixel, and only those cells -- listed from the set bits --
+//     run the tap loop (a cell with an all-zero neighbourhood filters to 0);
 //   * erosion runs over the same list (a zero pixel erodes to zero); an all-zero eroded tile ends the block.
 // ---------------------------------------------------------------------------------
-constexpr int kR = 3;                    // bilateral radius of the fused kernel
-constexpr int kSH = kTH + 2 * kHalo;     // 42 source rows
-constexpr int kSP = 80;                  // source pitch: image columns c0-8 .. c0+71
-constexpr int kSX = 8;                   // column of the source window = image column - c0 + kSX
 constexpr int kBH = kTH + 4, kBW = kTW + 4;      // thresholded ring 36 x 68
 constexpr int kEH = kTH + 2, kEW = kTW + 2;      // eroded ring 34 x 66
 
+// Source-tile geometry of one radius.
+template <int R>
+struct FusedTile {
+    static_assert(R >= 1 && R <= 4, "the fused filter kernel serves bilateral radius 1..4");
+    static constexpr int halo = R + 2;                           // bilateral R + erosion 1 + dilation 1
+    static constexpr int rows = kTH + 2 * halo;                  // source rows r0-halo .. r0+kTH+halo-1
+    static constexpr int sx = (halo + 3) & ~3;                   // column of the source window = image column - c0 + sx
+    static constexpr int pitch = (sx + kTW + halo + 3) & ~3;     // image columns c0-sx .. c0+pitch-sx-1
+    static constexpr int taps = R == 1 ? 5 : R == 2 ? 13 : R == 3 ? 29 : 49;          // offsets with i^2 + j^2 <= R^2
+    static constexpr int table = (taps + 31) & ~31;
+    static_assert(pitch > 64 && pitch <= 96, "a row mask is one 64-bit word and one 32-bit word");
+    static_assert(kBW - 1 + sx - 2 + R < pitch, "the rightmost ring cell's taps stay inside the source row");
+};
+
 // GEOM: frame f's H, W and plane offset come from geom[f] (swk_batch_run_groups: the grid is sized by the largest frame, the
 // workgroups beyond a frame's extent leave at once); otherwise every frame is H x W, planes packed densely.
-template <bool GEOM>
+template <bool GEOM, int R>
 __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict__ src, int H, int W,
                                                       const float *__restrict__ color_w, const float *__restrict__ space_w,
                                                       const int8_t *__restrict__ tdr, const int8_t *__restrict__ tdc,
@@ -360,16 +370,17 @@ __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict_
                                                       uint8_t *__restrict__ bil_out, uint8_t *__restrict__ thr_out,
                                                       uint8_t *__restrict__ open_out, const FrameGeom *__restrict__ geom)
 {
+    constexpr int kR = R, kHalo = FusedTile<R>::halo, kSH = FusedTile<R>::rows, kSP = FusedTile<R>::pitch, kSX = FusedTile<R>::sx;
     __shared__ __attribute__((aligned(16))) uint8_t s_src[kSH * kSP];
-    __shared__ uint32_t s_nz[kSH * 3];             // per source row: 80-bit mask of its nonzero pixels
-    __shared__ unsigned long long s_hlo[kSH];      // per source row: bit lc = some nonzero among source columns lc+3 .. lc+9
+    __shared__ uint32_t s_nz[kSH * 3];             // per source row: mask of its nonzero pixels (kSP bits)
+    __shared__ unsigned long long s_hlo[kSH];      // per source row: bit lc = some nonzero among the 2R+1 source columns under ring column lc
     __shared__ uint32_t s_hhi[kSH];
     __shared__ __attribute__((aligned(4))) uint8_t s_thr[kBH * kBW];
     __shared__ __attribute__((aligned(4))) uint8_t s_er[kEH * kEW];
     __shared__ uint16_t s_list[kBH * kBW];
     __shared__ float s_cw[256];
-    __shared__ float s_sw[32];
-    __shared__ int s_ofs[32];
+    __shared__ float s_sw[FusedTile<R>::table];
+    __shared__ int s_ofs[FusedTile<R>::table];
     __shared__ int s_count, s_er_any;
     const int f = blockIdx.z, tid = threadIdx.x;
     const int r0 = blockIdx.y * kTH, c0 = blockIdx.x * kTW;
@@ -382,10 +393,10 @@ __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict_
     if (tid == 0) { s_count = 0; s_er_any = 0; }
     if (tid < kSH * 3) s_nz[tid] = 0u;
     __syncthreads();
-    // ---- source tile: rows r0-5 .. r0+36, columns c0-8 .. c0+71; its nonzero pixels also go into row bit masks ----
+    // ---- source tile: rows r0-kHalo .. r0+kTH+kHalo-1, columns c0-kSX .. c0+kSP-kSX-1; its nonzero pixels also go into row bit masks ----
     int seen = 0;                                  // this thread loaded a nonzero pixel
     // One dword (4 columns) per step.  Rows and columns outside the image are BORDER_REFLECT_101 copies (the taps of
-    // in-image pixels reach up to kR beyond it); cells farther out are never consumed.  Inside the image the load is
+    // in-image pixels reach up to kR beyond it, over as many reflections as a small image needs); cells farther out are never consumed.  Inside the image the load is
     // as wide as the address allows (rows of a 214- or 850-pixel ROI start on alternating 4- and 2-byte boundaries).
     for (int i = tid; i < kSH * (kSP / 4); i += 256) {
         const int sr = i / (kSP / 4), q = i - sr * (kSP / 4);
@@ -415,28 +426,28 @@ __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict_
     // empty source window: every stage outputs zero, which the (cleared) buffers already hold
     if (!__syncthreads_or(seen)) return;
     for (int i = tid; i < 256; i += 256) s_cw[i] = color_w[i];
-    if (tid < maxk) {
+    if (tid < maxk) {                              // maxk <= FusedTile<R>::taps: the launcher checks it
         s_sw[tid] = space_w[tid];
         s_ofs[tid] = (int)tdr[tid] * kSP + (int)tdc[tid];
     }
     for (int i = tid; i < kBH * kBW / 4; i += 256) ((uint32_t *)s_thr)[i] = 0u;
     for (int i = tid; i < kEH * kEW / 4; i += 256) ((uint32_t *)s_er)[i] = 0u;
-    // ---- horizontal 7-wide OR, one source row per thread, as shifts of the row mask ----
+    // ---- horizontal (2R+1)-wide OR, one source row per thread, as shifts of the row mask ----
     if (tid < kSH) {
         const unsigned long long lo = (unsigned long long)s_nz[tid * 3] | ((unsigned long long)s_nz[tid * 3 + 1] << 32);
         const unsigned long long hi = s_nz[tid * 3 + 2];
         unsigned long long alo = 0, ahi = 0;
 #pragma unroll
-        for (int d = kSX - kHalo; d <= kSX - kHalo + 2 * kR; ++d) {       // ring column lc = source columns lc+3 .. lc+9
-            alo |= (lo >> d) | (hi << (64 - d));
+        for (int d = kSX - kHalo; d <= kSX - kHalo + 2 * kR; ++d) {       // ring column lc = source columns lc+kSX-2-kR .. lc+kSX-2+kR
+            alo |= d ? (lo >> d) | (hi << (64 - d)) : lo;
             ahi |= hi >> d;
         }
         s_hlo[tid] = alo;
         s_hhi[tid] = (uint32_t)ahi;
     }
     __syncthreads();
-    // ---- live ring cells: in the image and with a nonzero pixel somewhere in their 7x7 neighbourhood.
-    //      One ring row per thread: vertical OR of seven row masks, then the set bits go to the list. ----
+    // ---- live ring cells: in the image and with a nonzero pixel somewhere in their (2R+1)^2 neighbourhood.
+    //      One ring row per thread: vertical OR of 2R+1 row masks, then the set bits go to the list. ----
     if (tid < kBH) {
         const int lr = tid;
         const int r = r0 - 2 + lr;
@@ -468,7 +479,7 @@ __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict_
     for (int j = tid; j < nlive; j += 256) {
         const int i = s_list[j];
         const int lr = i / kBW, lc = i - lr * kBW;
-        const int ctr = (lr + kR) * kSP + lc + (kSX - 2);             // ring (lr, lc) = source (lr+3, lc+6)
+        const int ctr = (lr + kR) * kSP + lc + (kSX - 2);             // ring (lr, lc) = source (lr+kR, lc+kSX-2)
         const int v0 = s_src[ctr];
         float sum = 0.f, wsum = 0.f;
         for (int k = 0; k < maxk; ++k) {
@@ -525,6 +536,29 @@ __global__ __launch_bounds__(256) void k_filter_fused(const uint8_t *__restrict_
     }
 }
 
+// The instantiation of a radius; t.maxk taps must fit that radius's tables (ensure_bilateral makes both from the same radius).
+template <bool GEOM, int R>
+static void launch_fused_r(hipStream_t s, dim3 grid, const uint8_t *src, int H, int W, const BilateralTables &t, int use_fma, int thresh,
+                           uint8_t *bil_out, uint8_t *thr_out, uint8_t *open_out, const FrameGeom *geom)
+{
+    if (t.maxk < 1 || t.maxk > FusedTile<R>::taps) { g_launch_error = (int)hipErrorInvalidValue; return; }
+    hipLaunchKernelGGL((k_filter_fused<GEOM, R>), grid, dim3(256), 0, s, src, H, W, t.color_w, t.space_w, t.tap_dr, t.tap_dc, t.maxk,
+                       use_fma, thresh, bil_out, thr_out, open_out, geom);
+}
+
+template <bool GEOM>
+static void launch_fused(hipStream_t s, dim3 grid, const uint8_t *src, int H, int W, const BilateralTables &t, int use_fma, int thresh,
+                         uint8_t *bil_out, uint8_t *thr_out, uint8_t *open_out, const FrameGeom *geom)
+{
+    switch (t.radius) {
+    case 1: launch_fused_r<GEOM, 1>(s, grid, src, H, W, t, use_fma, thresh, bil_out, thr_out, open_out, geom); break;
+    case 2: launch_fused_r<GEOM, 2>(s, grid, src, H, W, t, use_fma, thresh, bil_out, thr_out, open_out, geom); break;
+    case 3: launch_fused_r<GEOM, 3>(s, grid, src, H, W, t, use_fma, thresh, bil_out, thr_out, open_out, geom); break;
+    case 4: launch_fused_r<GEOM, 4>(s, grid, src, H, W, t, use_fma, thresh, bil_out, thr_out, open_out, geom); break;
+    default: g_launch_error = (int)hipErrorInvalidValue;          // a missing instantiation is an error, not a fall-back
+    }
+}
+
 void launch_filter_fused(hipStream_t s, const uint8_t *src, int F, int H, int W, const BilateralTables &t,
                          int use_fma, int thresh, uint8_t *bil_out, uint8_t *thr_out, uint8_t *open_out)
 {
@@ -538,9 +572,8 @@ void launch_filter_fused(hipStream_t s, const uint8_t *src, int F, int H, int W,
     for (int f0 = 0; f0 < F; f0 += 32768) {
         const int fc = F - f0 < 32768 ? F - f0 : 32768;
         const int64_t o = (int64_t)f0 * H * W;
-        hipLaunchKernelGGL(k_filter_fused<false>, dim3(ntx, nty, fc), dim3(256), 0, s,
-                           src + o, H, W, t.color_w, t.space_w, t.tap_dr, t.tap_dc, t.maxk, use_fma, thresh,
-                           bil_out ? bil_out + o : nullptr, thr_out ? thr_out + o : nullptr, open_out + o, nullptr);
+        launch_fused<false>(s, dim3(ntx, nty, fc), src + o, H, W, t, use_fma, thresh,
+                            bil_out ? bil_out + o : nullptr, thr_out ? thr_out + o : nullptr, open_out + o, nullptr);
     }
 }
 
@@ -554,9 +587,7 @@ void launch_filter_fused_geom(hipStream_t s, const uint8_t *src, int F, int Hmax
     if (me != hipSuccess) { g_launch_error = (int)me; return; }
     for (int f0 = 0; f0 < F; f0 += 32768) {
         const int fc = F - f0 < 32768 ? F - f0 : 32768;
-        hipLaunchKernelGGL(k_filter_fused<true>, dim3(ntx, nty, fc), dim3(256), 0, s,
-                           src, 0, 0, t.color_w, t.space_w, t.tap_dr, t.tap_dc, t.maxk, use_fma, thresh,
-                           bil_out, thr_out, open_out, geom + f0);
+        launch_fused<true>(s, dim3(ntx, nty, fc), src, 0, 0, t, use_fma, thresh, bil_out, thr_out, open_out, geom + f0);
     }
 }
 

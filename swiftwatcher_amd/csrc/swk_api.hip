@@ -172,13 +172,20 @@ int sync(swk_ctx *ctx)
 }
 
 // ---- bilateral weight tables (OpenCV 4.1.0 bilateralFilter_8u set-up, host side) ----
+// radius of a diameter: d <= 0 derives it from sigma_space; at least 1
+int bilateral_radius(int d, double sigma_space)
+{
+    const double ss = sigma_space <= 0 ? 1 : sigma_space;
+    const int radius = d <= 0 ? (int)lrint(ss * 1.5) : d / 2;
+    return radius < 1 ? 1 : radius;
+}
+
 int ensure_bilateral(swk_ctx *ctx, int d, double sigma_color, double sigma_space)
 {
     if (ctx->bil_d == d && ctx->bil_sc == sigma_color && ctx->bil_ss == sigma_space) return SWK_OK;
     double sc = sigma_color <= 0 ? 1 : sigma_color, ss = sigma_space <= 0 ? 1 : sigma_space;
     const double gc = -0.5 / (sc * sc), gs = -0.5 / (ss * ss);
-    int radius = d <= 0 ? (int)lrint(ss * 1.5) : d / 2;
-    if (radius < 1) radius = 1;
+    const int radius = bilateral_radius(d, sigma_space);
     if (radius > 4) return fail(ctx, SWK_ERR_ARG, "bilateral diameter > 9 is not supported");
     float cw[256], sw[81];
     int8_t dr[81], dc[81];
@@ -619,7 +626,9 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
 {
     if (p->open_kh != 3 || p->open_kw != 3) return fail(ctx, SWK_ERR_ARG, "only the (3,3) opening window is implemented");
     if (p->connectivity != 4 && p->connectivity != 8) return fail(ctx, SWK_ERR_ARG, "connectivity must be 4 or 8");
-    if (p->bil_d / 2 != 3) return fail(ctx, SWK_ERR_ARG, "the fused filter kernel implements bilateral d=7 (radius 3) only");
+    // the fused filter kernel has one instantiation per radius 1..4; refused here, before any buffer or launch (ensure_bilateral's own check
+    // comes after the buffers)
+    if (bilateral_radius(p->bil_d, p->bil_sigma_space) > 4) return fail(ctx, SWK_ERR_ARG, "bilateral diameter > 9 is not supported");
     const int n = groups[0].n;
     int64_t nwin64 = 0;
     for (int g = 0; g < G; ++g) {

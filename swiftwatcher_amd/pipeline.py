@@ -12,12 +12,13 @@ from . import image_filtering as img
 
 
 def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size=21, classifier=None, min_seg_size=(24, 24),
-                             device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None):
+                             device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None):
     """Same call order as __main__.py:62-100.  corners = ((x1, y1), (x2, y2)) of the chimney's top edge: crop region
     and ROI mask are then generated from the video's first frame (:62-63) instead of being passed in.  Returns the tracker's detected events (lists of Segment objects,
     the structure the reference hands to event classification).  windows_per_call > 1 reads that many queue-fuls
     ahead and segments (and classifies) them in one GPU call each; the tracker still sees the frames one by one in
-    the reference's order, so the events are the same."""
+    the reference's order, so the events are the same.  params: a _lib.default_params(...) struct for the segment path (bilateral
+    diameter and sigmas, threshold, ...); None = the reference's values."""
     if corners is not None:
         first_frame = reader.read_frame(0, increment=False)                        # :62
         crop_region, roi_mask, _ = img.generate_regions(first_frame, corners)      # :63
@@ -45,7 +46,7 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
                         triple = reader.get_n_frames(n=queue_size)                  # :73 (pads with null frames)
                         windows.append(triple)
                         ahead += sum(1 for k in triple[1] if k >= 0)                # null frames are not counted (:146-147)
-                    ready.put(segment_windows(windows, crop_region, min_seg_size, device=device, classifier=classifier))
+                    ready.put(segment_windows(windows, crop_region, min_seg_size, device=device, params=params, classifier=classifier))
                 ready.put(None)
             except BaseException as exc:                                            # surfaces in the consumer
                 ready.put(exc)
@@ -65,7 +66,7 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
                     tracker.step(frame)
         worker.join()
         return tracker.detected_events
-    queue = FrameQueue(queue_size, device=device, keep_stages=keep_stages)
+    queue = FrameQueue(queue_size, device=device, params=params, keep_stages=keep_stages)
     while queue.frames_processed < reader.total_frames:
         frames, numbers, stamps = reader.get_n_frames(n=queue.maxlen)          # :73 (pads with null frames)
         queue.push_list_of_frames(frames, numbers, stamps)                     # :74
@@ -86,9 +87,10 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     return tracker.detected_events
 
 
-def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, **kw):
-    """Decoded frames (oldest first) -> (swift count, events).  Regions either explicit or from corners=..."""
-    events = swift_counting_algorithm(ArrayReader(frames, fps=fps), crop_region, roi_mask, **kw)
+def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, **kw):
+    """Decoded frames (oldest first) -> (swift count, events).  Regions either explicit or from corners=...; params as in
+    swift_counting_algorithm."""
+    events = swift_counting_algorithm(ArrayReader(frames, fps=fps), crop_region, roi_mask, params=params, **kw)
     return ec.count_swifts(events), events
 
 
