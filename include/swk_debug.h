@@ -65,6 +65,11 @@ int32_t swk_last_stopping_norms(swk_ctx *ctx, double *ratio, double *err_bound, 
 int32_t swk_set_integer_start(swk_ctx *ctx, int32_t on);
 /* Windows of the last swk_batch_run / swk_ialm whose start came from the integer kernel (the others ran the f64 start pass). */
 int32_t swk_last_integer_start_windows(swk_ctx *ctx, int32_t *windows);
+/* Diagnostic: how each group of the last swk_batch_run / swk_batch_run_groups reached the device, one value per group (up to cap):
+ * 0 = one copy of a packed ROI, 1 = the whole buffer as it lies, read at (x0, y0) with the caller's strides, 2 = one copy per frame
+ * (full-width rows), 3 = one 2-D copy per frame; -1 = a device group, read in place.  Returns the number of groups of that call (0 before
+ * the first; a refused call leaves the previous call's values; negative: error). */
+int32_t swk_last_host_stage(swk_ctx *ctx, int32_t *kinds, int32_t cap);
 /* Diagnostic: iterations the G^(-1/2) solver took in the LAST small-matrix step of the last batch, maximum over its
  * windows: Newton-Schulz iterations, or 100 + Jacobi sweeps where that solver ran. */
 int32_t swk_last_eig_sweeps(swk_ctx *ctx, int32_t *sweeps);

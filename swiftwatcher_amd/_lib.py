@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SWK_LIB", os.path.join(_HERE, "libswk.so"))     # SWK
 ABI_VERSION = 2
 MEM_HOST, MEM_DEVICE = 0, 1
 ERR_STALE = -6
+STAGE_DENSE, STAGE_WHOLE, STAGE_ROWS, STAGE_2D, STAGE_DEVICE = 0, 1, 2, 3, -1          # swk_last_host_stage
 STAGES = ("gray", "rpca", "bilateral", "thresh", "opened", "labels")
 ORDER_RASTER, ORDER_BLOCK2X2 = 0, 1
 GRAY_Q14, GRAY_Q15 = 0, 1
@@ -94,6 +95,7 @@ _SIGS = {
     "swk_set_sparse_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
     "swk_set_integer_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
     "swk_last_integer_start_windows": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
+    "swk_last_host_stage": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "swk_last_eig_sweeps": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "swk_set_norm_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
     "swk_set_norm_guard": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
@@ -388,6 +390,15 @@ class Context:
         v = ctypes.c_int32(0)
         self._check(self._lib.swk_last_integer_start_windows(self._h, ctypes.byref(v)))
         return v.value
+
+    def last_host_stage(self, cap=256):
+        """How each group of the last batch call reached the device (swk_last_host_stage): a list of STAGE_DENSE / STAGE_WHOLE /
+        STAGE_ROWS / STAGE_2D, STAGE_DEVICE for a group read in place."""
+        kinds = np.zeros(cap, np.int32)
+        n = self._lib.swk_last_host_stage(self._h, _ptr(kinds), cap)
+        if n < 0:
+            self._check(n)
+        return [int(k) for k in kinds[:min(n, cap)]]
 
     @property
     def redo_batches(self):

@@ -64,6 +64,7 @@ struct swk_ctx {
     int sparse_backoff = 0, norm_backoff = 0;   // batches for which a guess stays off after it failed (same video, same behaviour)
     int eig_method = 0;                  // 0 Newton-Schulz (MFMA), 1 Jacobi
     hipEvent_t ev_poll[2] = {nullptr, nullptr};   // the host polls convergence two iterations late (ialm_chain)
+    std::vector<int32_t> last_stage;     // staging route of each group of the last batch call (host_stage_plan's kind; -1: a device group)
     std::vector<IalmWin> last_hw;        // host copy of the last batch's per-window IALM state (account_iters): diagnostics
     // what the last batch call left on the device for swk_segment_inputs_last: its frames (SL_ROI copy of a host input,
     // or the caller's device frames) and region records; valid until a call reuses those buffers
@@ -704,6 +705,8 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
             roi_off[g] = roi_bytes;
             roi_bytes += (st[g].bytes + 255) & ~(size_t)255;
         }
+    ctx->last_stage.resize(G);
+    for (int g = 0; g < G; ++g) ctx->last_stage[g] = groups[g].mem == SWK_MEM_HOST ? st[g].kind : -1;
     size_t pn_bytes = 0;
     std::vector<size_t> pn_off(G, 0);
     for (int g = 0; g < G; ++g)
@@ -1200,6 +1203,13 @@ int32_t swk_last_integer_start_windows(swk_ctx *ctx, int32_t *windows)
     if (!ctx || !windows) return SWK_ERR_ARG;
     *windows = ctx->last_int_start;
     return SWK_OK;
+}
+int32_t swk_last_host_stage(swk_ctx *ctx, int32_t *kinds, int32_t cap)
+{
+    if (!ctx || (!kinds && cap > 0)) return SWK_ERR_ARG;
+    const int32_t G = (int32_t)ctx->last_stage.size();
+    for (int32_t g = 0; g < G && g < cap; ++g) kinds[g] = ctx->last_stage[g];
+    return G;
 }
 int32_t swk_prof_redo_batches(swk_ctx *ctx, int64_t *batches)
 {
