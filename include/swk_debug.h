@@ -60,11 +60,26 @@ int32_t swk_prof_guard_windows(swk_ctx *ctx, int64_t *windows);
  * against (float32 sum over a binary16 copy of Y/mu: csrc/ialm_small_dev.h; the effective band is max(rel, 4 x bound) per window).
  * Returns the number of windows of that batch (negative: error).  The A/Y-state pass forms the norm in float64: bound 0. */
 int32_t swk_last_stopping_norms(swk_ctx *ctx, double *ratio, double *err_bound, int32_t cap);
-/* M-state pass only: 1 (default) = statistics and the first iteration's Gram matrix come from one read of X on the
- * integer matrix cores wherever the first shrinkage provably removes nothing; 0 = always the f64 start pass. */
+/* Pass variants 1, 2, 4 and 5 (variant 6 always takes the f64 start pass): 1 (default) = statistics and the first iteration's
+ * Gram matrix come from one read of X on the integer matrix cores wherever the first shrinkage provably removes nothing;
+ * 0 = always the f64 start pass. */
 int32_t swk_set_integer_start(swk_ctx *ctx, int32_t on);
 /* Windows of the last swk_batch_run / swk_ialm whose start came from the integer kernel (the others ran the f64 start pass). */
 int32_t swk_last_integer_start_windows(swk_ctx *ctx, int32_t *windows);
+/* Diagnostic: the start of the IALM alone, on nwin host windows X[nwin][n][P] (u8), staged like swk_ialm's window and run with the
+ * context's current switches (swk_set_ialm_variant, swk_set_integer_start): statistics and, where it may run, the integer Gram
+ * kernel; the start choice; the start pass of the selected variant; the chip-wide slab sum when a window has more than 4 slabs.
+ * Returns what the first small-matrix step would read, per window:
+ *   G[nwin][n][n]   the Gram slabs summed in that step's order, frame-block pairs below the diagonal mirrored, UNSCALED: the exact
+ *                   integer X^T X where int_gram is 1, M_1^T M_1 of the f64 start pass otherwise (zeros for an all-zero window,
+ *                   which is done before it starts);
+ *   sumsq, maxv     exact sum of squares and maximum of the window;
+ *   int_gram        1 = the window starts from the integer kernel's matrix;
+ *   scal[nwin][4]   dual_norm, mu_0, thr_0 = lmbda / mu_0, dnorm (image_filtering.py:271-276);
+ *   *nblk_out       Gram slabs per window of this batch, *gram8_ran = 1 when the integer kernel ran for the batch.
+ * Every output but G may be NULL.  No IALM iteration runs; the counters of the context do not move. */
+int32_t swk_debug_ialm_start(swk_ctx *ctx, const uint8_t *X, int32_t nwin, int32_t n, int32_t P, double lmbda, double *G,
+                             uint64_t *sumsq, uint32_t *maxv, int32_t *int_gram, double *scal, int32_t *nblk_out, int32_t *gram8_ran);
 /* Diagnostic: how each group of the last swk_batch_run / swk_batch_run_groups reached the device, one value per group (up to cap):
  * 0 = one copy of a packed ROI, 1 = the whole buffer as it lies, read at (x0, y0) with the caller's strides, 2 = one copy per frame
  * (full-width rows), 3 = one 2-D copy per frame; -1 = a device group, read in place.  Returns the number of groups of that call (0 before

@@ -95,6 +95,7 @@ _SIGS = {
     "swk_set_sparse_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
     "swk_set_integer_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
     "swk_last_integer_start_windows": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
+    "swk_debug_ialm_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double] + [ctypes.c_void_p] * 7),
     "swk_last_host_stage": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "swk_last_eig_sweeps": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "swk_set_norm_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
@@ -390,6 +391,21 @@ class Context:
         v = ctypes.c_int32(0)
         self._check(self._lib.swk_last_integer_start_windows(self._h, ctypes.byref(v)))
         return v.value
+
+    def debug_ialm_start(self, windows, lmbda=0.01):
+        """The start of the IALM alone on uint8 windows [nwin][n][P] (swk_debug_ialm_start), with the context's current pass
+        variant and integer-start switch: dict of G [nwin][n][n] (the first Gram matrix as the small-matrix step reads it,
+        unscaled), sumsq, maxv, int_gram, dual_norm, mu_0, thr_0, dnorm per window, nblk and gram8_ran of the batch."""
+        x = np.ascontiguousarray(windows, np.uint8)
+        nwin, n, P = x.shape
+        G = np.zeros((nwin, n, n), np.float64)
+        sumsq, maxv = np.zeros(nwin, np.uint64), np.zeros(nwin, np.uint32)
+        int_gram, scal = np.zeros(nwin, np.int32), np.zeros((nwin, 4), np.float64)
+        nblk, ran = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._check(self._lib.swk_debug_ialm_start(self._h, _ptr(x), nwin, n, P, float(lmbda), _ptr(G), _ptr(sumsq), _ptr(maxv),
+                                                   _ptr(int_gram), _ptr(scal), _ptr(nblk), _ptr(ran)))
+        return dict(G=G, sumsq=sumsq, maxv=maxv, int_gram=int_gram, dual_norm=scal[:, 0], mu_0=scal[:, 1], thr_0=scal[:, 2],
+                    dnorm=scal[:, 3], nblk=int(nblk[0]), gram8_ran=int(ran[0]))
 
     def last_host_stage(self, cap=256):
         """How each group of the last batch call reached the device (swk_last_host_stage): a list of STAGE_DENSE / STAGE_WHOLE /

@@ -100,7 +100,7 @@ struct MCfg {
     static constexpr int TP = 17;                                  // LDS pitch of the transpose tile
     static constexpr int NPAIR = NB * (NB + 1) / 2;
     static constexpr size_t lds_bytes = (size_t)(NPAD * BP + 4 * NPAD * TP) * sizeof(double);
-    // the first-iteration pass (MODE 1) appends two 256-entry tables (M_1 and U_0 as functions of the pixel value): + 4 KB, which at
+    // the start pass and the first-iteration pass (MODE 0 / 1) append two 256-entry tables (M_1 and U_0 as functions of the pixel value): + 4 KB, which at
     // 64 frames makes a workgroup exactly half of the CU's 160 KB
     static constexpr size_t lut_bytes = 2 * 256 * sizeof(double);
 };
@@ -112,7 +112,7 @@ constexpr unsigned ROWSTEP = 128u;           // (4 t) * ROWSTEP = t * 512 elemen
 struct PassCtx {
     __amdgpu_buffer_rsrc_t rX, rS, rM, rU;
     double *sB, *sT;
-    const double *lut;          // MODE 1: [256] M_1(x), then [256] U_0(x) = Y_0(x) / mu_0
+    const double *lut;          // MODE 0 / 1: [256] M_1(x), then [256] U_0(x) = Y_0(x) / mu_0
     double inv_mu, thr, inv_mu2, thr2, dual, rdual, ratio;
     float ratio_f;
     unsigned P32, fpad;
@@ -215,7 +215,7 @@ __device__ __forceinline__ void pass_loop(const PassCtx &cx, d4 (&G)[MCfg<NK>::N
                     }
                 }
                 const double c = fmin(fmax(raw, -cx.thr2), cx.thr2);
-                const double m2 = a_new + c;                                       // :284
+                const double m2 = MODE == 0 ? cx.lut[xi[t]] : a_new + c;           // :284 (M_1: the table of the kernel prologue)
                 cx.sT[(4 * t + cx.fr0) * TP + cx.pl] = m2;
                 if (MODE != 0) {         // the start pass leaves no state: pass 1 rebuilds M_1 from X
                     buf_st64(m2, cx.rM, vo8, (unsigned)(4 * t) * ROWSTEP * 8u);
@@ -303,14 +303,18 @@ __global__ __launch_bounds__(256, 2) void k_ialm_pass_m(IalmBuffers b, int sel, 
     }
     // first iteration: M_1 = (x - E_1) + U_0 with U_0 = Y_0 / mu_0, Y_0 = x / dual (:272, the correctly rounded quotient by one
     // Newton step) and E_1 = shrink(x + U_0) (:282-284) depend on the pixel's 8-bit value only: 256 threads tabulate them once
-    // (the same operations in the same order as the element-wise code they replace: 11 f64 instructions per element less)
+    // (the same operations in the same order as the element-wise code they replace: 11 f64 instructions per element less).
+    // The start pass (MODE 0) takes its M_1 from the same table, so that G_1 is the Gram matrix of the very matrix pass 1
+    // multiplies -- statement by statement the reference's (:282-284), not the A + clamp(raw) form of the later passes, which in a
+    // clipped element differs from it by the cancellation error of :284 (up to eps |raw| / thr); mu_0 is st.nxt there (k_ialm_init)
     double *lut = lds + NPAD * BP + 4 * NPAD * TP;
-    if (MODE == 1) {
+    if (MODE != 2) {
+        const double imu0 = MODE == 0 ? inv_mu2 : inv_mu, thr0 = MODE == 0 ? thr2 : thr;
         const double x = (double)tid;
         const double q = x * rdual;
         const double y0 = __builtin_fma(__builtin_fma(-q, dual, x), rdual, q);
-        const double u0 = inv_mu * y0;
-        const double e = shrink2(x + u0, thr);
+        const double u0 = imu0 * y0;
+        const double e = shrink2(x + u0, thr0);
         lut[tid] = (x - e) + u0;
         lut[256 + tid] = u0;
     }
@@ -398,7 +402,7 @@ template <int NK, int MODE>
 static void launch_m_one(hipStream_t s, const IalmBuffers &b, int sel, int tune)
 {
     static unsigned long long attr_mask = 0;
-    constexpr size_t lds = MCfg<NK>::lds_bytes + (MODE == 1 ? MCfg<NK>::lut_bytes : 0);
+    constexpr size_t lds = MCfg<NK>::lds_bytes + (MODE != 2 ? MCfg<NK>::lut_bytes : 0);
     if (!ensure_dyn_lds((const void *)k_ialm_pass_m<NK, MODE>, lds, attr_mask)) return;
     hipLaunchKernelGGL((k_ialm_pass_m<NK, MODE>), dim3(b.nblk, b.nwin), dim3(256), lds, s, b, sel, tune);
     note_launch();

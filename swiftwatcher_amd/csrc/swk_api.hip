@@ -355,10 +355,11 @@ int copy_windows(swk_ctx *ctx, const IalmWin *win, int nwin, IalmWin *dst)
     return SWK_OK;
 }
 
-// One chain over the job's windows on the context's stream: start, then per iteration pass -> (slab sum) -> small-matrix step, until
-// every window has stopped.  speculate: the M-state pass may guess (sparse-image stores and stopping norms skipped far from the
-// tolerance).  *bp describes the buffers the chain worked in.
-int ialm_chain(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want_A, bool want_E, bool speculate, IalmBuffers *bp)
+// The start of a chain (ialm_chain, and swk_debug_ialm_start, which stops after it): the chain's buffers, then window statistics,
+// start choice and the first iteration's Gram slabs -- k_gram_u8 or k_ialm_stats, k_ialm_init, the MODE 0 pass of the plan's variant.
+// speculate: the M-state pass may guess (ialm_chain).  *bp describes the buffers; *wide_work_out is the workspace of k_ialm_small_wide
+// (null unless the plan uses it).
+int ialm_start(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want_E, bool speculate, IalmBuffers *bp, double **wide_work_out)
 {
     const int nwin = job.nwin, n = job.n, P = job.P;
     IalmBuffers &b = *bp;
@@ -407,21 +408,34 @@ int ialm_chain(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want
     }
     if (want_E) HIPCHK(ctx, hipMemsetAsync(b.E, 0, felems * 8, s));
 
-    int rc = ensure_poll_events(ctx);
-    if (rc) return rc;
-    const int check_from = 6;     // no window converges earlier (mu grows 1.5x per iteration)
-    const double lmbda = job.lmbda, tol = job.tol;
-    const int maxiter = job.maxiter;
     // window statistics (||X||_F, max) and, for the M-state pass, the first Gram matrix in the same read of X
     // on the integer matrix cores; windows it does not cover get the f64 start pass below
     b.use_gram8 = (plan.gram8 && gram_u8_supported(b)) ? 1 : 0;
     b.refine = plan.refine;
     { Timed t(ctx, SWK_K_IALM_STATS);
       if (b.use_gram8) launch_gram_u8(s, b); else launch_ialm_stats(s, b);
-      launch_ialm_init(s, b, lmbda); }
+      launch_ialm_init(s, b, job.lmbda); }
     // the Gram-only start pass reads X alone (1 B/element): booked with the statistics family so
     // SWK_K_IALM_PASS times only the full streaming passes
     { Timed t(ctx, SWK_K_IALM_STATS); launch_ialm_pass(s, b, 0, plan.variant, 0, ctx->pass_tune); }
+    *wide_work_out = wide_work;
+    return SWK_OK;
+}
+
+// One chain over the job's windows on the context's stream: start, then per iteration pass -> (slab sum) -> small-matrix step, until
+// every window has stopped.  speculate: the M-state pass may guess (sparse-image stores and stopping norms skipped far from the
+// tolerance).  *bp describes the buffers the chain worked in.
+int ialm_chain(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want_A, bool want_E, bool speculate, IalmBuffers *bp)
+{
+    int rc = ensure_poll_events(ctx);
+    if (rc) return rc;
+    double *wide_work = nullptr;
+    if ((rc = ialm_start(ctx, job, plan, want_E, speculate, bp, &wide_work))) return rc;
+    IalmBuffers &b = *bp;
+    hipStream_t s = ctx->stream;
+    const int check_from = 6;     // no window converges earlier (mu grows 1.5x per iteration)
+    const double lmbda = job.lmbda, tol = job.tol;
+    const int maxiter = job.maxiter;
     auto small_step = [&](int k) {
         Timed t(ctx, SWK_K_IALM_SMALL);
         if (b.nblk > 4) launch_gram_reduce(s, b);
@@ -1316,6 +1330,55 @@ int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, doub
     rc = read_windows(ctx, run, hw);
     if (rc) return rc;
     account_iters(ctx, hw, iters);
+    return SWK_OK;
+}
+
+// Diagnostic (swk_debug.h): the start of ialm_chain on host windows, and what it left for the first small-matrix step.
+int32_t swk_debug_ialm_start(swk_ctx *ctx, const uint8_t *X, int32_t nwin, int32_t n, int32_t P, double lmbda, double *G,
+                             uint64_t *sumsq, uint32_t *maxv, int32_t *int_gram, double *scal, int32_t *nblk_out, int32_t *gram8_ran)
+{
+    if (!ctx || !X || !G || nwin < 1 || n < 1 || n > kMaxNWide || P < 1 || !(lmbda > 0.0)) return fail(ctx, SWK_ERR_ARG, "bad argument");
+    if ((int64_t)nwin * n * P >= (1ll << 31)) return fail(ctx, SWK_ERR_ARG, "too many pixels in one call");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    // staged like swk_ialm's window: the library's own allocation, padded to whole dwords past the last pixel (k_gram_u8)
+    const size_t elems = (size_t)nwin * n * P;
+    uint8_t *dX, *dS;
+    NEED(ctx, SL_X, elems + 4, dX);
+    NEED(ctx, SL_S, elems, dS);
+    HIPCHK(ctx, hipMemcpyAsync(dX, X, elems, hipMemcpyHostToDevice, s));
+    const IalmPlan plan = plan_ialm(ctx, n, P, nwin, false, 0);
+    IalmBuffers b;
+    double *wide_work = nullptr;
+    int rc = ialm_start(ctx, IalmJob{dX, dS, nwin, n, P, nullptr, lmbda, 1e-3, 100}, plan, false, false, &b, &wide_work);
+    if (rc) return rc;
+    if (b.nblk > 4) launch_gram_reduce(s, b);          // as the first small-matrix step does (ialm_chain)
+    // the slabs that step would sum: the first nred of every window
+    const size_t nn = (size_t)n * n;
+    std::vector<double> slabs((size_t)nwin * b.nred * nn);
+    HIPCHK(ctx, hipMemcpy2DAsync(slabs.data(), b.nred * nn * 8, b.gpart, (size_t)b.nblk * nn * 8, b.nred * nn * 8, nwin,
+                                 hipMemcpyDeviceToHost, s));
+    std::vector<IalmWin> hw(nwin);
+    HIPCHK(ctx, hipMemcpyAsync(hw.data(), b.win, (size_t)nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, s));
+    if ((rc = sync(ctx))) return rc;
+    for (int w = 0; w < nwin; ++w) {
+        const IalmWin &st = hw[w];
+        // gram_reduce's read (ialm_small_dev.h) without its scale: slabs in order, frame-block pairs ib > jb from their mirror
+        const double *gp = slabs.data() + (size_t)w * b.nred * nn;
+        for (int idx = 0; idx < (int)nn; ++idx) {
+            const int i = idx / n, j = idx - i * n;
+            const int src = (i >> 4) <= (j >> 4) ? idx : j * n + i;
+            double acc = 0.0;
+            for (int bk = 0; bk < b.nred && !st.done; ++bk) acc += gp[(size_t)bk * nn + src];
+            G[(size_t)w * nn + idx] = acc;
+        }
+        if (sumsq) sumsq[w] = st.sumsq;
+        if (maxv) maxv[w] = st.maxv;
+        if (int_gram) int_gram[w] = st.int_gram;
+        if (scal) { scal[4 * w] = st.dual_norm; scal[4 * w + 1] = st.cur.mu; scal[4 * w + 2] = st.cur.thr; scal[4 * w + 3] = st.dnorm; }
+    }
+    if (nblk_out) *nblk_out = b.nblk;
+    if (gram8_ran) *gram8_ran = b.use_gram8;
     return SWK_OK;
 }
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from helpers import oracle_events, oracle_frames, track, event_signature
+from ialm_start_cases import expected_integer_start as _expected_integer_start          # k_ialm_init's rule restated on the host
 
 pytestmark = pytest.mark.gpu
 ATOL_AE = 1e-5
@@ -49,16 +50,6 @@ def _downstream(orc, sparse):
     lab = [orc.labels_to_u8(orc.ccl_u8(f)[1]) for f in opened]
     return dict(bilateral=np.stack(bil), thresh=np.stack(thr), opened=np.stack(opened), labels=np.stack(lab),
                 segments=[orc.regionprops_u8(l) for l in lab])
-
-
-def _expected_integer_start(gray):
-    """k_ialm_init's rule restated on the host: the integer start stands iff the first shrinkage (:283) removes
-    nothing, i.e. max(X + Y0/mu0) = 1.8 max(X) <= lmbda/mu0 = 0.008 ||X||_F (when ||X||_F >= max(X)/lmbda)."""
-    x = gray.astype(np.float64)
-    fro = np.sqrt((x * x).sum())
-    dual = max(fro, x.max() / 0.01)
-    inv_mu = fro / 1.25
-    return x.max() + inv_mu * (x.max() / dual) <= 0.01 * inv_mu
 
 
 @pytest.mark.parametrize("name", ["ialm_212x424x64_seeded", "ialm_212x424x21_seeded", "ialm_425x850x21_seeded"])
