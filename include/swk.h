@@ -285,6 +285,26 @@ int32_t swk_nhwc_maxpool3s2(void *stream, const float *src, int32_t n, int32_t h
  * Fixed summation order: a segment's scores do not depend on the batch it is in. */
 int32_t swk_nhwc_head2_relu_mean(void *stream, const float *x, int32_t n, int32_t px, int32_t c, const float *w, const float *bias,
                                  const float *ring, float n_pos, float *out);
+/* head2_dropout_relu_mean: the same head with the reference's Dropout(0.5) LIVE in front of it (the reference never puts its model into
+ * eval mode, segment_classification.py:47-67: every decision it publishes is one draw), `samples` realisations per segment in one launch:
+ *   out[n][s][k] = (sum_{p < n_pos} max(sum_ch 2 m(n, s, p, ch) f(n, p, ch) w[k][ch] + bias[k], 0)) / n_pos,     s < samples, k = 0, 1
+ * x [n][px][c]: the px live positions of the last Fire's output; pos [px] (device, int32): the position 0 <= pos[j] < n_pos of live
+ * pixel j in the full map, raster order, all distinct; bg [n_pos][c]: the last Fire's output for the blank image.  f(n, p, ch) =
+ * x[n][j][ch] where pos[j] == p, bg[p][ch] at every other position (only those rows of bg are read; bg may be NULL when px == n_pos).
+ * The factor 2 = 1 / (1 - 0.5) is nn.Dropout's scaling.  keys [n] (device, uint64): one key per segment; seed: one per run.
+ * The mask m(n, s, p, ch) in {0, 1} is a pure function of (seed, keys[n], s, p, ch) -- not of the row n, the batch size, the launch or
+ * the stream:
+ *   Philox4x32-10 with the standard constants (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; ten rounds)
+ *   key      = (seed & 0xffffffff, seed >> 32)
+ *   counter  = (p * (c / 4) + ch / 4,  s >> 5,  keys[n] & 0xffffffff,  keys[n] >> 32)
+ *   m        = bit (s & 31) of output word (ch & 3);  the value is KEPT when the bit is 1.
+ * (One generator call serves four channels for 32 samples.)  It is this library's own stream of bits, not torch's: one draw cannot be
+ * matched against a run of the reference, the distribution can.
+ * c in {256, 512, 768, 1024}, 1 <= samples <= 256, px <= n_pos <= 8192; x, w and bg 16-byte aligned.  Fixed summation order (a function
+ * of c, px, n_pos and samples alone): a segment's samples x 2 scores are bit-identical whatever batch it is scored in. */
+int32_t swk_nhwc_head2_dropout_relu_mean(void *stream, const float *x, int32_t n, int32_t px, int32_t c, const int32_t *pos, const float *bg,
+                                         int32_t n_pos, const float *w, const float *bias, const uint64_t *keys, uint64_t seed,
+                                         int32_t samples, float *out);
 /* conv7x7s2_bias_relu: the network's first convolution (Conv2d(3, 96, 7, stride 2), no padding) with bias and ReLU on the f32 matrix
  * cores, for the m x m outputs starting at output (lo, lo) of a side x side channels-last input:
  *   dst[n][y][x][co] = max(sum src[n][2 (lo + y) + dy][2 (lo + x) + dx][c] * weight[co][c][dy][dx] + bias[co], 0)

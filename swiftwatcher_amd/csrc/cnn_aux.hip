@@ -132,6 +132,142 @@ __global__ __launch_bounds__(256) void k_head2_relu_mean(const float *__restrict
     }
 }
 
+// Philox4x32-10 (Salmon et al., SC'11; the constants of Random123): counter (c0..c3), key (k0, k1) -> four 32-bit words.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&o)[4])
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
+        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+
+// The same head with the reference's LIVE Dropout(0.5) in front of it (the reference never leaves train mode), S realisations per
+// segment in one launch:
+//     out[n][s][k] = (sum_{p < n_pos} max(sum_ch 2 m(n, s, p, ch) f(n, p, ch) w[k][ch] + bias[k], 0)) / n_pos
+// f = x[n][j] where pos[j] == p, bg[p] at the other positions (the ring is dropped per segment and sample like everything else, so it
+// cannot be a constant here).  The mask m is defined in swk.h: Philox4x32-10 keyed by the seed, counter (p c/4 + ch/4, s >> 5, segment
+// key): ONE generator call gives a lane the bits of its four channels for 32 samples.
+// One workgroup per segment, four waves, a wave takes positions wave, wave + 4, ... of the full map; lane l holds (twice) the weights
+// of channels 256 j + 4 l .. + 3 and reads its float4s ONCE per position.  Per block of 32 samples a lane keeps 64 partial sums
+// (value v = 32 k + s); they cross the wave as a transposing butterfly -- at distance h a lane hands over the half of its values whose
+// bit h differs from its own lane bit and adds what it receives to the half it keeps: 63 exchanges instead of 64 x 6, and lane l ends
+// with the complete sum of value l.  (A block of at most four samples takes a plain butterfly per value instead: same sums, fewer exchanges.)  Bias, ReLU and the sum over positions then run on all 64 lanes (one value each, in LDS per wave
+// and block of samples); the four waves add up in order.  Summation order: a function of (c, px, n_pos, S) alone.
+template <int CJ>
+__global__ __launch_bounds__(256) void k_head2_dropout_relu_mean(const float *__restrict__ x, int px, const int32_t *__restrict__ pos,
+                                                                 const float *__restrict__ bg, int n_pos, const float *__restrict__ w,
+                                                                 const float *__restrict__ bias, const uint64_t *__restrict__ keys,
+                                                                 uint64_t seed, int S, float inv_pos, float *__restrict__ out)
+{
+    constexpr int C = 256 * CJ;
+    extern __shared__ int32_t live_of[];          // [n_pos]: row of x that holds position p, or -1 (bg)
+    __shared__ float part[4][8][64];               // [wave][block of 32 samples][value]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = threadIdx.x; i < n_pos; i += 256) live_of[i] = -1;
+    for (int i = threadIdx.x; i < 4 * 8 * 64; i += 256) (&part[0][0][0])[i] = 0.0f;
+    __syncthreads();
+    for (int j = threadIdx.x; j < px; j += 256) {
+        const int q = pos[j];
+        if ((unsigned)q < (unsigned)n_pos) live_of[q] = j;
+    }
+    __syncthreads();
+    const float *xs = x + (int64_t)blockIdx.x * px * C + 4 * lane;
+    float4 w0[CJ], w1[CJ];
+#pragma unroll
+    for (int j = 0; j < CJ; ++j) {
+        w0[j] = *(const float4 *)(w + 256 * j + 4 * lane);
+        w1[j] = *(const float4 *)(w + C + 256 * j + 4 * lane);
+        // nn.Dropout scales what it keeps by 1 / (1 - 0.5): exact
+        w0[j].x *= 2.0f; w0[j].y *= 2.0f; w0[j].z *= 2.0f; w0[j].w *= 2.0f;
+        w1[j].x *= 2.0f; w1[j].y *= 2.0f; w1[j].z *= 2.0f; w1[j].w *= 2.0f;
+    }
+    const float b = bias[lane >> 5];
+    const uint64_t key = keys[blockIdx.x];
+    const uint32_t key_lo = (uint32_t)key, key_hi = (uint32_t)(key >> 32), seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32);
+    const int nblk = (S + 31) >> 5;
+    for (int p = wave; p < n_pos; p += 4) {
+        const int row = live_of[p];
+        float4 f[CJ];
+        if (row >= 0) {
+#pragma unroll
+            for (int j = 0; j < CJ; ++j) f[j] = *(const float4 *)(xs + (int64_t)row * C + 256 * j);
+        } else if (bg) {
+#pragma unroll
+            for (int j = 0; j < CJ; ++j) f[j] = *(const float4 *)(bg + (int64_t)p * C + 256 * j + 4 * lane);
+        } else {
+#pragma unroll
+            for (int j = 0; j < CJ; ++j) f[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        for (int blk = 0; blk < nblk; ++blk) {
+            const int ns = min(32, S - 32 * blk);
+            float a[64];
+#pragma unroll
+            for (int v = 0; v < 64; ++v) a[v] = 0.0f;
+#pragma unroll
+            for (int j = 0; j < CJ; ++j) {
+                uint32_t m[4];
+                philox4x32_10((uint32_t)(p * (C / 4) + 64 * j + lane), (uint32_t)blk, key_lo, key_hi, seed_lo, seed_hi, m);
+                const float fv[4] = {f[j].x, f[j].y, f[j].z, f[j].w};
+                const float u0[4] = {w0[j].x, w0[j].y, w0[j].z, w0[j].w};
+                const float u1[4] = {w1[j].x, w1[j].y, w1[j].z, w1[j].w};
+#pragma unroll
+                for (int s = 0; s < 32; ++s) {
+                    if (s < ns) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const bool keep = (m[q] >> s) & 1u;
+                            a[s] = keep ? fmaf(fv[q], u0[q], a[s]) : a[s];
+                            a[32 + s] = keep ? fmaf(fv[q], u1[q], a[32 + s]) : a[32 + s];
+                        }
+                    }
+                }
+            }
+            if (ns <= 4) {
+                // a few samples (S = 1 is how a counting loop decides): a plain butterfly per value, 12 ns exchanges instead of 63.  Lane
+                // v of a plain butterfly adds the same pairs in the same order as the transposing one below (a + b = b + a bit for
+                // bit), so a sample's score does not depend on which path its block takes.
+                float mine = 0.0f;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    if (s < ns) {
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            float t = a[32 * k + s];
+#pragma unroll
+                            for (int h = 32; h >= 1; h >>= 1) t += __shfl_xor(t, h, 64);
+                            mine = lane == 32 * k + s ? t : mine;
+                        }
+                    }
+                }
+                a[0] = mine;
+            } else {
+#pragma unroll
+                for (int half = 32; half >= 1; half >>= 1) {
+                    const bool up = lane & half;
+#pragma unroll
+                    for (int v = 0; v < half; ++v) {
+                        const float send = up ? a[v] : a[v + half];
+                        const float keep = up ? a[v + half] : a[v];
+                        a[v] = keep + __shfl_xor(send, half, 64);
+                    }
+                }
+            }
+            part[wave][blk][lane] += fmaxf(a[0] + b, 0.0f);
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nblk * 64; i += 256) {
+        const int blk = i >> 6, v = i & 63, s = 32 * blk + (v & 31);
+        const float t = ((part[0][blk][v] + part[1][blk][v]) + part[2][blk][v]) + part[3][blk][v];
+        if (s < S) out[((int64_t)blockIdx.x * S + s) * 2 + (v >> 5)] = t * inv_pos;
+    }
+}
+
 }  // namespace swk
 
 #pragma GCC visibility push(default)
@@ -176,6 +312,28 @@ int32_t swk_nhwc_head2_relu_mean(void *stream, const float *x, int32_t n, int32_
     case 2: hipLaunchKernelGGL(swk::k_head2_relu_mean<2>, grid, block, 0, st, x, px, w, bias, ring, inv, out); break;
     case 3: hipLaunchKernelGGL(swk::k_head2_relu_mean<3>, grid, block, 0, st, x, px, w, bias, ring, inv, out); break;
     default: hipLaunchKernelGGL(swk::k_head2_relu_mean<4>, grid, block, 0, st, x, px, w, bias, ring, inv, out); break;
+    }
+    return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
+}
+
+int32_t swk_nhwc_head2_dropout_relu_mean(void *stream, const float *x, int32_t n, int32_t px, int32_t c, const int32_t *pos, const float *bg,
+                                         int32_t n_pos, const float *w, const float *bias, const uint64_t *keys, uint64_t seed,
+                                         int32_t samples, float *out)
+{
+    // bg may be NULL only when every position is live
+    if (!x || !pos || !w || !bias || !keys || !out || n < 1 || px < 1 || n_pos < 1 || n_pos > 8192 || px > n_pos || (!bg && px != n_pos))
+        return SWK_ERR_ARG;
+    if (samples < 1 || samples > 256 || (((uintptr_t)x | (uintptr_t)w | (uintptr_t)bg) & 15) || ((uintptr_t)keys & 7)) return SWK_ERR_ARG;
+    if (c != 256 && c != 512 && c != 768 && c != 1024) return SWK_ERR_ARG;
+    const dim3 grid((unsigned)n), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    const float inv = 1.0f / (float)n_pos;
+    const size_t lds = (size_t)n_pos * sizeof(int32_t);
+    switch (c / 256) {
+    case 1: hipLaunchKernelGGL(swk::k_head2_dropout_relu_mean<1>, grid, block, lds, st, x, px, pos, bg, n_pos, w, bias, keys, seed, samples, inv, out); break;
+    case 2: hipLaunchKernelGGL(swk::k_head2_dropout_relu_mean<2>, grid, block, lds, st, x, px, pos, bg, n_pos, w, bias, keys, seed, samples, inv, out); break;
+    case 3: hipLaunchKernelGGL(swk::k_head2_dropout_relu_mean<3>, grid, block, lds, st, x, px, pos, bg, n_pos, w, bias, keys, seed, samples, inv, out); break;
+    default: hipLaunchKernelGGL(swk::k_head2_dropout_relu_mean<4>, grid, block, lds, st, x, px, pos, bg, n_pos, w, bias, keys, seed, samples, inv, out); break;
     }
     return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
 }

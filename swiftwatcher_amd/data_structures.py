@@ -57,6 +57,23 @@ def _window_crops(frames, nseg, live, min_seg_size, crop_region):
     return buf, offsets.tolist(), np.maximum(boxes[:, 1] - boxes[:, 0], 0).tolist(), np.maximum(boxes[:, 3] - boxes[:, 2], 0).tolist()
 
 
+def segment_keys(frame_numbers, labels):
+    """The uint64 key of a segment for the classifier's dropout sampling (SegmentClassifier.dropout_scores): (parent frame number << 8)
+    | label, two's complement for the negative numbers of null frames.  A segment gets the same draw whether it is scored in the serial
+    loop, in a batch of windows or in a group call."""
+    fn = np.asarray(frame_numbers, dtype=np.int64).reshape(-1)
+    lab = np.asarray(labels, dtype=np.int64).reshape(-1)
+    return np.ascontiguousarray((fn << 8) | lab).view(np.uint64)
+
+
+def batch_keys(segs, nseg, frame_numbers):
+    """segment_keys of every segment of a batch_run in batch order (frames in the batch's order, ascending label): segs / nseg its
+    region records, frame_numbers the frame number of each of its frames."""
+    cap = segs.shape[1]
+    live = segs[np.arange(cap)[None, :] < nseg[:, None]]
+    return segment_keys(np.repeat(np.asarray(frame_numbers, dtype=np.int64), np.minimum(nseg, cap)), live["label"])
+
+
 def window_segments(segs, nseg, slots, min_seg_size, crop_region, batch=None, first=0):
     """Segment objects of a whole batch_run at once: slots = the Frame objects in the batch's frame order; segs / nseg = its
     region records.  The same attributes Segment.__init__ sets (label, bbox, centroid = sum / area in float64, area), made
@@ -249,8 +266,11 @@ class WindowBatch:
     (_batch, _index = k); SegmentClassifier asks predictions(classifier) for the whole table once per window.  Returns None
     when the context has moved on (the caller then classifies from the segments' images, as before)."""
 
-    def __init__(self, ctx, generation, total, min_seg_size, queue=None):
+    def __init__(self, ctx, generation, total, min_seg_size, queue=None, keys=None):
         self.ctx, self.generation, self.total, self.min_seg_size = ctx, generation, total, tuple(min_seg_size)
+        # the segments' dropout keys in batch order (batch_keys), or a zero-argument callable that makes them: only a classifier with a
+        # dropout_seed asks for them
+        self.keys = keys
         self.queue = weakref.ref(queue) if queue is not None else None
         self._tables = {}          # id(classifier) -> numpy int array (total,) of predicted classes, or a pending device tensor
         self.used = False
@@ -266,8 +286,15 @@ class WindowBatch:
         dev = getattr(classifier, "device", None)
         if dev is None or dev.type != "cuda" or (dev.index or 0) != self.ctx.device:
             return                               # a classifier on another device scores the segments' images
+        extra = {}
+        if getattr(classifier, "dropout_seed", None) is not None:
+            if self.keys is None:
+                return                           # no keys: the segments' images are scored, with keys made from the segments
+            if callable(self.keys):
+                self.keys = self.keys()
+            extra["keys"] = self.keys
         try:
-            self._tables[key] = classifier.predict_last_batch(self.ctx, self.generation, self.total, self.min_seg_size)
+            self._tables[key] = classifier.predict_last_batch(self.ctx, self.generation, self.total, self.min_seg_size, **extra)
         except _lib.StaleBatch:
             pass
 
@@ -406,7 +433,9 @@ class FrameQueue(deque):
         prev, self._last_batch = self._last_batch, None
         if prev is not None and not prev.used:
             self._classifier_hint = None
-        batch = WindowBatch(ctx, generation, int(nseg.sum()), min_seg_size, queue=self) if stack.ndim == 4 else None
+        # (the closure binds the records, not res: res holds the window's stage planes)
+        batch = WindowBatch(ctx, generation, int(nseg.sum()), min_seg_size, queue=self,
+                            keys=lambda r=res["segs"], s=nseg, m=tuple(slot.frame_number for slot in self): batch_keys(r, s, m)) if stack.ndim == 4 else None
         self._last_batch = batch
         hint = self._classifier_hint() if self._classifier_hint is not None else None
         if hint is not None and batch is not None:
@@ -506,7 +535,11 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
     nseg = res["nseg"]
     if np.any(nseg > res["segs"].shape[1]):
         raise _lib.SwkError("more regions in a frame than seg_cap")
-    batch = WindowBatch(ctx, res["generation"], int(nseg.sum()), min_seg_size, queue=owner) if stack.ndim == 4 else None
+    # frame number of every frame of the batch: window w is the pos[w]-th, newest frame first
+    # (bound as default arguments: the loop below reuses the name `numbers`, and the keys may be made long after it)
+    batch_numbers = tuple(k for w in order for k in list(windows[w][1])[::-1])
+    batch = WindowBatch(ctx, res["generation"], int(nseg.sum()), min_seg_size, queue=owner,
+                        keys=lambda r=res["segs"], s=nseg, m=batch_numbers: batch_keys(r, s, m)) if stack.ndim == 4 else None
     if batch is not None and classifier is not None:
         batch.launch(classifier)
     if info is not None:
@@ -563,7 +596,12 @@ def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, 
             raise _lib.SwkError("more regions in a frame than seg_cap")
     total = sum(int(np.minimum(r["nseg"], r["segs"].shape[1]).sum()) for r in results)
     bgr = all(spec["frames"].ndim == 4 for spec in specs)
-    batch = WindowBatch(ctx, results[0]["generation"], total, min_seg_size) if bgr else None
+    records = [(r["segs"], r["nseg"], [k for _, numbers, _ in groups[i][0] for k in list(numbers)[::-1]]) for i, r in zip(live, results)]
+
+    def keys(records=tuple(records)):
+        return np.concatenate([batch_keys(*rec) for rec in records])
+
+    batch = WindowBatch(ctx, results[0]["generation"], total, min_seg_size, keys=keys) if bgr else None
     if batch is not None and classifier is not None:
         batch.launch(classifier)
     out = [[] for _ in groups]

@@ -12,6 +12,11 @@ Differences from the reference, all deliberate:
   * segments are classified in one batch instead of one 602 KB H2D copy + sync per segment;
   * by default only the part of each feature map the 24x24 patch can influence is evaluated
     (CroppedSqueezeNet10, 5.7x fewer MACs: 0.128 instead of 0.733 G per segment, same arithmetic per output); cropped=False runs the full network.
+
+The reference's own behaviour -- Dropout(0.5) live in front of the head, every decision one draw -- can be SAMPLED: dropout_scores /
+keep_probability score a segment under many dropout masks in one launch (swk_nhwc_head2_dropout_relu_mean), and
+SegmentClassifier(dropout_seed=...) decides by one such realisation.  The mask is the library's own counter-based one (include/swk.h),
+not torch's generator stream: the distribution of the reference's decision is reproduced, not a single run of it.
 """
 import ctypes
 import os
@@ -65,6 +70,24 @@ class SqueezeNet10(nn.Module):
 
     def forward(self, x):
         return torch.flatten(self.classifier(self.features(x)), 1)
+
+
+def _dropout_head(x, pos, bg, n_pos, hw, hb, keys, seed, samples):
+    """swk_nhwc_head2_dropout_relu_mean on PyTorch's current stream: x (k, c, h, w) channels-last, the live positions `pos` of the last
+    Fire's output; bg (n_pos, c) or None (every position live); keys (k,) int64 tensor holding the uint64 keys.  -> (k, samples, 2)."""
+    from . import _lib
+    lib = _lib.load()
+    k = x.shape[0]
+    if not (x.is_contiguous(memory_format=torch.channels_last) and hw.shape[0] == 2 and keys.shape[0] == k and keys.is_contiguous()):
+        raise RuntimeError("the dropout head needs a channels-last tensor, a two-class head and one key per segment")
+    out = torch.empty((k, samples, 2), dtype=torch.float32, device=x.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    rc = lib.swk_nhwc_head2_dropout_relu_mean(stream, x.data_ptr(), k, x.shape[2] * x.shape[3], x.shape[1], pos.data_ptr(),
+                                              None if bg is None else bg.data_ptr(), n_pos, hw.data_ptr(), hb.data_ptr(), keys.data_ptr(),
+                                              ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), samples, out.data_ptr())
+    if rc:
+        raise RuntimeError("swk_nhwc_head2_dropout_relu_mean failed (%d)" % rc)
+    return out
 
 
 def _affected(lo, hi, k, st, pad, out_size):
@@ -148,6 +171,11 @@ class CroppedSqueezeNet10:
         ring[:, :, lo:hi + 1, lo:hi + 1] = 0
         self.ring_sum = ring.sum(dim=(2, 3))                 # (1, 2): the head's input-independent positions
         self.n_pos = float(size * size)
+        # what the dropout head reads (swk_nhwc_head2_dropout_relu_mean): the last Fire's output for the blank image at every position,
+        # channels-last (its ring is dropped per segment and sample like the live square, so ring_sum cannot stand in for it), and the
+        # position of each live pixel in the full map, raster order
+        self.head_bg = x.permute(0, 2, 3, 1).reshape(size * size, x.shape[1]).contiguous()
+        self.head_pos = torch.tensor([r * size + c for r in range(lo, hi + 1) for c in range(lo, hi + 1)], dtype=torch.int32, device=dev)
         # input-independent squeeze output of every Fire tile (with the map's own zero padding where a tile reaches
         # the edge): the ring of the persistent squeeze buffers
         self.sq_bg = []
@@ -318,12 +346,16 @@ class CroppedSqueezeNet10:
         return w
 
     @torch.no_grad()
-    def __call__(self, tiles, row0=0):
+    def __call__(self, tiles, row0=0, dropout=None):
         """tiles: (B, 3, 40, 40) float32 = rows/cols 92..131 of the normalised 224x224 input.  row0: first row of the persistent
-        per-layer tiles this forward works in (two forwards on disjoint row ranges may run side by side on two streams)."""
+        per-layer tiles this forward works in (two forwards on disjoint row ranges may run side by side on two streams).
+        dropout = (keys, seed, samples): instead of the eval-mode scores, (B, samples, 2) scores under the reference's live Dropout(0.5)
+        (keys: (B,) int64 device tensor of the segments' uint64 keys); the library's HIP kernel only."""
         if self._gpu_path(tiles):
             with torch.cuda.device(tiles.device):            # the glue kernels go to this device's current stream
-                return self._forward_hip_glue(tiles, row0)
+                return self._forward_hip_glue(tiles, row0, dropout)
+        if dropout is not None:
+            raise RuntimeError("dropout sampling runs on the library's HIP head kernel: it needs the GPU path")
         if row0:
             raise ValueError("row0 is a feature of the GPU path")
         m = self.model
@@ -357,7 +389,7 @@ class CroppedSqueezeNet10:
         s = torch.relu(m.classifier[1](x)).sum(dim=(2, 3))
         return (s + self.ring_sum) / self.n_pos
 
-    def _forward_hip_glue(self, tiles, row0=0):
+    def _forward_hip_glue(self, tiles, row0=0, dropout=None):
         """The same forward on the GPU with the convolutions alone left to MIOpen: bias + ReLU + placement into the
         next tile is one HIP kernel per convolution output (swk_nhwc_bias_relu_place), max-pooling another
         (swk_nhwc_maxpool3s2), both on PyTorch's current stream.  Same float32 operations per element as above."""
@@ -490,6 +522,12 @@ class CroppedSqueezeNet10:
         # the 512 -> 2 head (1 x 1 convolution + ReLU + spatial sum) as a plain matrix product over the channels-last pixels: no
         # convolution library on this path, hence no kernel search per batch shape
         head = m.classifier[1]
+        if dropout is not None:
+            if not (self.own_kernels and head.out_channels == 2 and x.shape[1] in (256, 512, 768, 1024)):
+                raise RuntimeError("dropout sampling runs on the library's HIP head kernel (own kernels, a two-class head)")
+            hw, hb, _ = self._head_operand()
+            keys, seed, samples = dropout
+            return _dropout_head(x, self.head_pos, self.head_bg, int(self.n_pos), hw, hb, keys, seed, samples)
         if self.own_kernels and head.out_channels == 2 and x.shape[1] in (256, 512, 768, 1024) and x.is_contiguous(memory_format=cl):
             # the head as one kernel with a fixed summation order (csrc/cnn_aux.hip): scores that do not depend on the batch's row count
             hw, hb, ring = self._head_operand()
@@ -556,7 +594,10 @@ class SegmentClassifier:
         buf.seek(0)
         return cls(buf, **kw)
 
-    def __init__(self, model_path, device=None, batch_size=1024, cropped=True):
+    def __init__(self, model_path, device=None, batch_size=1024, cropped=True, dropout_seed=None):
+        """dropout_seed: None = the eval-mode classifier (the parity definition).  An int: __call__, classify_frames and the device
+        hand-over (predict_last_batch) decide by sample 0 of dropout_scores under that seed -- ONE realisation of a reference run, whose
+        Dropout(0.5) is live; every segment's draw is fixed by its key (data_structures.segment_keys)."""
         if device is None:
             if not torch.cuda.is_available():
                 raise RuntimeError("SegmentClassifier runs on the MI355X (PyTorch-ROCm); pass device='cpu' "
@@ -591,6 +632,8 @@ class SegmentClassifier:
         self._graphs = {}
         self._use_graphs = self.device.type == "cuda" and os.environ.get("SWK_HIP_GRAPHS", "1") == "1"
         self._graph_error = None
+        self.dropout_seed = None if dropout_seed is None else int(dropout_seed)
+        self._full_head = None
 
     def preprocess(self, segment_images, window=False):
         """(:18-24, :31-33) for a list of HxWx3 uint8 crops -> float32 (B, 3, 224, 224) on the device, or with
@@ -638,6 +681,81 @@ class SegmentClassifier:
                 and self.cropped._gpu_path(x)):
             return self._forward_two_streams(x)
         return self.cropped(x) if self.cropped is not None else self.model(x)
+
+    def _full_head_operand(self, n_pos):
+        """What the dropout head reads on the full network: the head's weights and bias, and every position as a live one."""
+        if self._full_head is None or self._full_head[2].shape[0] != n_pos:
+            head = self.model.classifier[1]
+            self._full_head = (head.weight.detach().reshape(head.out_channels, -1).contiguous(), head.bias.detach().contiguous(),
+                               torch.arange(n_pos, dtype=torch.int32, device=self.device))
+        return self._full_head
+
+    @torch.no_grad()
+    def _forward_dropout(self, x, keys, samples, seed):
+        """(k, samples, 2) scores of the network inputs x under the reference's live Dropout(0.5): everything up to the last Fire's
+        output is the eval forward's (SqueezeNet has no batch norm: train mode differs from eval mode in the head alone), then the
+        dropout head.  One chain on the current stream, never captured; every operand it reads was made on this stream before
+        (CroppedSqueezeNet10.__init__ and reserve)."""
+        if self.device.type != "cuda":
+            raise RuntimeError("dropout sampling runs on the library's HIP head kernel: it needs the GPU")
+        samples = int(samples)
+        if not 1 <= samples <= 256:
+            raise ValueError("samples must be 1..256")
+        if self.cropped is not None:
+            if not (self.cropped.own_kernels and self.cropped._gpu_path(x)):
+                raise RuntimeError("dropout sampling runs on the library's own kernels (SWK_OWN_CNN_KERNELS=1, channels-last)")
+            self.cropped.reserve(x.shape[0])
+            return self.cropped(x, dropout=(keys, int(seed), samples))
+        with torch.cuda.device(self.device):
+            with torch.backends.cudnn.flags(enabled=True, benchmark=self._cudnn_benchmark):
+                f = self.model.features(x)
+            f = f.contiguous(memory_format=torch.channels_last)
+            n_pos = f.shape[2] * f.shape[3]
+            hw, hb, pos = self._full_head_operand(n_pos)
+            return _dropout_head(f, pos, None, n_pos, hw, hb, keys, int(seed), samples)
+
+    def _keys_tensor(self, keys, k):
+        if not (isinstance(keys, np.ndarray) and keys.dtype in (np.uint64, np.int64)):
+            # anything else goes through Python ints, two's complement in 64 bits (numpy would round a list that mixes a negative key
+            # with one of 2**63 or more through float64)
+            keys = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in np.asarray(keys, dtype=object).reshape(-1)], dtype=np.uint64)
+        keys = np.ascontiguousarray(keys.reshape(-1)).view(np.int64)
+        if keys.shape[0] != k:
+            raise ValueError("%d keys for %d segments" % (keys.shape[0], k))
+        return torch.from_numpy(keys.copy()).to(self.device)
+
+    def dropout_scores(self, segment_images, keys, samples=32, seed=0):
+        """Scores of every segment under `samples` realisations of the reference's live Dropout(0.5): float32 (k, samples, 2) on the
+        device.  keys: one uint64 per segment (data_structures.segment_keys: (parent frame number << 8) | label); the mask of sample s
+        is a function of (seed, key, s, position, channel) alone (include/swk.h), so a segment's scores do not depend on the batch it is
+        scored in.  Cropped and full network alike; the mask is the library's own, not torch's generator stream."""
+        with self._lock:
+            kt = self._keys_tensor(keys, len(segment_images))
+            out = []
+            for i in range(0, len(segment_images), self.batch_size):
+                chunk = segment_images[i:i + self.batch_size]
+                x = self.preprocess(chunk, window=self.cropped is not None)
+                out.append(self._forward_dropout(x, kt[i:i + len(chunk)], samples, seed))
+            return torch.cat(out) if out else torch.zeros((0, int(samples), 2), device=self.device)
+
+    def keep_probability(self, segments, samples=32, seed=0):
+        """Per segment (Segment objects), the share of `samples` dropout realisations that keep it: score[1] > score[0] (a tie drops
+        the segment, as torch.max picks index 0).  float64 numpy array (k,)."""
+        from .data_structures import segment_keys
+        if not segments:
+            return np.zeros(0, np.float64)
+        keys = segment_keys([s.parent_frame_number for s in segments], [s.label for s in segments])
+        sc = self.dropout_scores([s.segment_image for s in segments], keys, samples, seed)
+        return (sc[:, :, 1] > sc[:, :, 0]).sum(dim=1).cpu().numpy().astype(np.float64) / float(int(samples))
+
+    def _predict_images(self, segments):
+        """Predicted class of each segment from its image: eval mode, or sample 0 under dropout_seed."""
+        images = [s.segment_image for s in segments]
+        if self.dropout_seed is None:
+            return torch.max(self.scores(images), 1)[1].cpu().numpy()
+        from .data_structures import segment_keys
+        keys = segment_keys([s.parent_frame_number for s in segments], [s.label for s in segments])
+        return torch.max(self.dropout_scores(images, keys, 1, self.dropout_seed)[:, 0], 1)[1].cpu().numpy()
 
     def _forward_two_streams(self, x):
         """A large forward as two forwards on disjoint rows of the persistent tiles, the second on a side stream.  The kernels of a
@@ -737,19 +855,20 @@ class SegmentClassifier:
         with self._lock:
             return self._scores_unlocked(segment_images)
 
-    def _scores_device(self, cut):
+    def _scores_device(self, cut, keys=None):
         """_scores_device_unlocked under the classifier's lock: the input slots, their events, the captured graphs and the forward's
         buffers belong to the classifier, and two threads score through one classifier when a reader segments (and scores) ahead
         beside the counting loop (io_frames.PresegmentingReader, pipeline.py windows_per_call): one scoring at a time."""
         with self._lock:
-            return self._scores_device_unlocked(cut)
+            return self._scores_device_unlocked(cut, keys)
 
     @torch.no_grad()
-    def _scores_device_unlocked(self, cut):
+    def _scores_device_unlocked(self, cut, keys=None):
         """Scores of a device-resident batch.  cut(net_ptr, frame_ptr, net_cap, first, pad, channels_last) -> (total, skipped) writes
         the network inputs of segments [first, first + net_cap) (a library call: its own stream, synchronous).  Two input slots: the
         library cuts and resamples chunk i + 1 while PyTorch's stream runs the network on chunk i; a slot is written again only after
-        the forward that read it has finished (its event) -- also across calls, the slots and events belong to the classifier."""
+        the forward that read it has finished (its event) -- also across calls, the slots and events belong to the classifier.
+        keys (one uint64 per segment of the batch, with dropout_seed set): the scores are sample 0 of the dropout head instead."""
         if self.device.type != "cuda":
             raise RuntimeError("device-resident scoring needs the GPU")
         pad = PAD - CroppedSqueezeNet10.IN_LO if self.cropped is not None else PAD
@@ -769,11 +888,15 @@ class SegmentClassifier:
 
         scores, frames_of = [], []
         total = produce(0, 0)
+        kt = self._keys_tensor(keys, total) if keys is not None else None
         first, i = 0, 0
         while first < total:
             slot = i & 1
             k = min(bs, total - first)
-            scores.append(self._run(xb[slot][:self._bucket(k)], k, persistent=True).clone())     # rows past k hold an earlier chunk: scored, dropped
+            if kt is not None:
+                scores.append(self._forward_dropout(xb[slot][:k], kt[first:first + k], 1, self.dropout_seed)[:, 0])
+            else:
+                scores.append(self._run(xb[slot][:self._bucket(k)], k, persistent=True).clone())     # rows past k hold an earlier chunk: scored, dropped
             frames_of.append(fb[slot][:k].clone())
             done[slot] = torch.cuda.Event()
             done[slot].record(torch.cuda.current_stream(self.device))
@@ -796,14 +919,19 @@ class SegmentClassifier:
                                       first=first, pad=pad, min_seg_size=min_seg_size, seg_frame_ptr=frame_ptr, channels_last=nhwc)
         return self._scores_device(cut)
 
-    def predict_last_batch(self, ctx, generation, total, min_seg_size=(24, 24)):
+    def predict_last_batch(self, ctx, generation, total, min_seg_size=(24, 24), keys=None):
         """Predicted class of every segment of the batch `ctx` ran last (FrameQueue.segment_queue's window), in batch order: an int64
         device tensor (total,), not waited for.  The inputs are cut from what that batch left on the device (swk_segment_inputs_last);
-        raises _lib.StaleBatch when the context has moved on."""
+        raises _lib.StaleBatch when the context has moved on.  keys: the segments' dropout keys in batch order, needed (and only
+        read) when the classifier has a dropout_seed."""
+        if self.dropout_seed is not None and keys is None:
+            raise ValueError("a classifier with a dropout_seed needs the segments' keys")
+        if self.dropout_seed is None:
+            keys = None
         def cut(net_ptr, frame_ptr, cap, first, pad, nhwc):
             return ctx.segment_inputs_last(generation, IMAGENET_MEAN, IMAGENET_STD, net_ptr, cap, first=first, pad=pad,
                                            min_seg_size=min_seg_size, seg_frame_ptr=frame_ptr, channels_last=nhwc, known_total=total)
-        scores, _ = self._scores_device(cut)
+        scores, _ = self._scores_device(cut) if keys is None else self._scores_device(cut, keys)
         if scores.shape[0] != total:
             raise RuntimeError("the device holds %d segments, the window has %d" % (scores.shape[0], total))
         return torch.max(scores, 1)[1]                                   # :36-39
@@ -816,7 +944,7 @@ class SegmentClassifier:
             return
         pred = self._window_predictions(segs)                 # segments of one segment_windows / segment_queue call: device-resident
         if pred is None:
-            pred = torch.max(self.scores([s.segment_image for s in segs]), 1)[1].cpu().numpy()
+            pred = self._predict_images(segs)
         i = 0
         for fr in frames:
             kept = []
@@ -851,8 +979,7 @@ class SegmentClassifier:
             return []
         pred = self._window_predictions(segments)
         if pred is None:
-            score = self.scores([s.segment_image for s in segments])
-            pred = torch.max(score, 1)[1].cpu().numpy()
+            pred = self._predict_images(segments)
         kept = [s for s, y in zip(segments, pred) if y == 1]
         for i, s in enumerate(kept):
             s.label = i + 1
