@@ -34,6 +34,7 @@ inline bool place_ok(const Place &p, int h, int w, int c, bool quads, const Crop
 int launch_expand1x1_split_bf16(hipStream_t s, const float *src, int64_t rows, const Crop &cr, int cin, int h, int w, const float *wgt,
                                 const float *bias, int cout, const Place &pl);
 extern int g_expand_split_bf16;          // A/B switch (swk_set_cnn_tuning knob 1): 1 = the split-bf16 kernel for the expand1x1 shapes
+extern int g_wino_bf16s_layout;          // A/B switch (swk_set_cnn_tuning knob 2): workgroup layout of the split-bf16 Winograd expands
 
 // The fused epilogue: register quad g of an accumulator = four consecutive output channels of the lane's pixel; bias, ReLU, one
 // float4 store.  An add, then a max (the library is built without contraction).

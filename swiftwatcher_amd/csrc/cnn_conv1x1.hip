@@ -238,10 +238,13 @@ int32_t swk_nhwc_conv1x1_bias_relu_place(void *stream, const float *src, int32_t
 // Measurement knobs of the classifier kernels (A/B runs).  knob 0: activation ring of the 1x1 kernel (0 = deepest that fits, 1 = one chunk
 // in flight; results do not depend on it).  knob 1: 1 = expand1x1 shapes on the split-bf16 kernel (cnn_expand_bf16.hip: float32-accurate,
 // another summation order than the float32 kernel's, so scores move in the last bits); 0, the default: every 1x1 on the float32 kernel.
+// knob 2: workgroup layout of the split-bf16 Winograd expands (cnn_wino3x3_bf16s.hip; results do not depend on it): 0 = each shape's default,
+// 1 = one column block and two tile groups per wave for every shape, 2 = the shared-filter layout for every shape that has one.
 int32_t swk_set_cnn_tuning(int32_t knob, int32_t value)
 {
     if (knob == 0 && (value == 0 || value == 1)) { swk::g_conv1x1_ring = value; return SWK_OK; }
     if (knob == 1 && (value == 0 || value == 1)) { swk::g_expand_split_bf16 = value; return SWK_OK; }
+    if (knob == 2 && value >= 0 && value <= 2) { swk::g_wino_bf16s_layout = value; return SWK_OK; }
     return SWK_ERR_ARG;
 }
 

@@ -2,7 +2,7 @@
 swk_nhwc_* call of CroppedSqueezeNet10._forward_hip_glue is bracketed by events on PyTorch's stream.  Prints one row per
 call with its multiply-accumulate rate and the activation bytes it has to move, and a JSON summary as the last line.
 
-    python3 tools/bench_convs.py [batch] [reps] [1x1 ring knob] [Winograd one-block-waves knob]
+    python3 tools/bench_convs.py [batch] [reps] [1x1 ring knob] [split-bf16 Winograd layout knob: 0 default, 1 present, 2 shared-filter]
 """
 import json
 import os
@@ -77,8 +77,11 @@ def main():
     batch = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     ring = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+    layout = int(sys.argv[4]) if len(sys.argv) > 4 else 0
     if _lib.load().swk_set_cnn_tuning(0, ring):
         raise SystemExit("swk_set_cnn_tuning refused %d" % ring)
+    if _lib.load().swk_set_cnn_tuning(2, layout):
+        raise SystemExit("swk_set_cnn_tuning refused layout %d" % layout)
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "w.pt")
         torch.save(ref.random_state_dict(0), path)
@@ -128,7 +131,7 @@ def main():
     groups = {}
     for r in rows:
         groups[r["call"][:4].strip()] = round(groups.get(r["call"][:4].strip(), 0.0) + r["us"] / 1e3, 3)
-    print(json.dumps({"batch": batch, "forward_ms": round(whole_ms, 3), "forward_two_chains_ms": round(chains_ms, 3), "own_kernels_ms": round(own, 3), "by_kind_ms": groups, "rows": rows}))
+    print(json.dumps({"batch": batch, "wino_bf16s_layout": layout, "forward_ms": round(whole_ms, 3), "forward_two_chains_ms": round(chains_ms, 3), "own_kernels_ms": round(own, 3), "by_kind_ms": groups, "rows": rows}))
 
 
 if __name__ == "__main__":
