@@ -251,7 +251,9 @@ int32_t swk_classifier_input_window(swk_ctx *ctx, const uint8_t *crops, int64_t 
  * frame_w frame -- intersected with the frame where the reference's unchecked slice would leave it.  Segments
  * [first, first + net_cap) get their (24 + 2 pad)^2 network inputs written to net; seg_frame (optional) receives
  * the frame index of each.  *total = segments in the batch (regions beyond seg_cap per frame do not count);
- * *skipped = boxes that were empty or larger than 512 pixels (their input is the blank image). */
+ * *skipped = boxes that were empty or had a side above 4096 (their input is the blank image).  Boxes with a side of 513..4096
+ * are resampled by a second kernel, launched only when the batch holds one; the result is Pillow's horizontal-pass-first resize,
+ * like every smaller box's. */
 int32_t swk_segment_inputs(swk_ctx *ctx, const swk_input *in, int32_t frame_h, int32_t frame_w,
                            const swk_segment *segs, const int32_t *nseg, int32_t seg_cap, int32_t min_h, int32_t min_w,
                            const float mean[3], const float std_[3], int32_t pad, int32_t channels_last, int32_t first,

@@ -108,6 +108,15 @@ int32_t swk_set_eig_method(swk_ctx *ctx, int32_t method);
 int32_t swk_set_start_refine(swk_ctx *ctx, double tau);
 int32_t swk_prof_refined_windows(swk_ctx *ctx, int64_t *refined, int64_t *unrefined);
 
+/* Diagnostic: the resize tables the classifier-input kernels form on the device (Pillow's antialiased bilinear coefficients for 24 output
+ * samples, 22-bit fixed point) for the input sizes first .. first + count - 1:
+ *   bounds[count][24][2]    first input sample and number of coefficients of each output sample;
+ *   coeffs[count][24][343]  the coefficients, zeros behind each sample's last.
+ * route 1 = as the large-crop kernel of swk_segment_inputs forms them (weights summed in one sweep, formed again in a second; sizes 1..4096),
+ * route 0 = as the kernels of crops up to 512 pixels form them (sizes 1..512).  The tests hold both to the float64 restatement of
+ * Pillow, integer for integer: a fused multiply-add or another summation order in the device code would show here. */
+int32_t swk_debug_resize_table(swk_ctx *ctx, int32_t first, int32_t count, int32_t route, int32_t *bounds, int32_t *coeffs);
+
 /* ---- classifier kernels: A/B switches ---- */
 /* Measurement knobs of the classifier kernels (A/B runs).  knob 0: workgroup layout of the 1 x 1 kernel (0 = 16-wave workgroups, the
  * default; 1 = 8 waves with the deepest activation ring that fits; results do not depend on it).  knob 1: 1 = the Fire modules' expand1x1

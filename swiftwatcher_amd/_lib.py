@@ -97,6 +97,7 @@ _SIGS = {
     "swk_last_integer_start_windows": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "swk_debug_ialm_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double] + [ctypes.c_void_p] * 7),
     "swk_last_host_stage": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
+    "swk_debug_resize_table": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_last_eig_sweeps": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "swk_set_norm_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
     "swk_set_norm_guard": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
@@ -671,6 +672,14 @@ class Context:
                 raise StaleBatch("the context no longer holds that batch")
             self._check(rc)
         return total.value, skipped.value
+
+    def debug_resize_table(self, first, count, route=1):
+        """swk_debug_resize_table: (bounds (count, 24, 2), coeffs (count, 24, 343)) int32, the device's Pillow resize tables of the
+        input sizes first .. first + count - 1 (route 1: the large-crop kernel's, sizes up to 4096; route 0: the <= 512 kernels')."""
+        bounds = np.empty((count, 24, 2), np.int32)
+        coeffs = np.empty((count, 24, 343), np.int32)
+        self._check(self._lib.swk_debug_resize_table(self._h, int(first), int(count), int(route), _ptr(bounds), _ptr(coeffs)))
+        return bounds, coeffs
 
     def regionprops_u8(self, labels, seg_cap=255):
         s, single = self._planes(labels)

@@ -23,7 +23,7 @@ enum Slot {
     SL_ROI = 0, SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8, SL_LAB32, SL_A, SL_Y, SL_E, SL_PN,
     SL_BM, SL_VPREV, SL_GPART, SL_ZZPART, SL_WIN, SL_ACTIVE, SL_PARENT, SL_ROOTBITS, SL_WORDPREFIX,
     SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_TMP_IN, SL_TMP_OUT, SL_TMP_AUX, SL_COLORW, SL_SPACEW,
-    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_COUNT
+    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_SEGLARGE, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int fam; };
@@ -604,16 +604,24 @@ int segment_inputs_impl(swk_ctx *ctx, const uint8_t *frames, int64_t fs, int64_t
     int count = tot - first;
     if (count > net_cap) count = net_cap;
     if (count < 1) return SWK_OK;
+    int32_t *dlarge;          // boxes with a side of 513..4096: [0] = how many, then 6 ints each
+    NEED(ctx, SL_SEGLARGE, ((size_t)count * 6 + 1) * 4, dlarge);
+    HIPCHK(ctx, hipMemsetAsync(dlarge, 0, 4, s));
     if (fr)
-        launch_segment_inputs_groups(s, fr, segs, seg_cap, doffs, F, min_h, min_w, first, count, net, seg_frame, pad, nhwc, mean, std_, dskip);
+        launch_segment_inputs_groups(s, fr, segs, seg_cap, doffs, F, min_h, min_w, first, count, net, seg_frame, pad, nhwc, mean, std_, dskip, dlarge);
     else
         launch_segment_inputs(s, frames, fs, rs, frame_h, frame_w, x0, y0, segs, doffs, F, seg_cap,
-                              min_h, min_w, first, count, net, seg_frame, pad, nhwc, mean, std_, dskip);
-    int32_t sk = 0;
+                              min_h, min_w, first, count, net, seg_frame, pad, nhwc, mean, std_, dskip, dlarge);
+    int32_t sk = 0, nlarge = 0;
     HIPCHK(ctx, hipMemcpyAsync(&sk, dskip, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(&nlarge, dlarge, 4, hipMemcpyDeviceToHost, s));
     int rc = sync(ctx);
     if (rc) return rc;
     if (skipped) *skipped = sk;
+    if (nlarge > 0) {          // rare: the rows of net those boxes own are written by a second kernel
+        launch_segment_inputs_large(s, fr ? nullptr : frames, fs, rs, fr, dlarge, nlarge > count ? count : nlarge, net, pad, nhwc, mean, std_);
+        return sync(ctx);
+    }
     return SWK_OK;
 }
 
@@ -1602,6 +1610,21 @@ int32_t swk_segment_inputs_last(swk_ctx *ctx, int32_t min_h, int32_t min_w, cons
     if (known >= 0 && *total != known) return fail(ctx, SWK_ERR_ARG, "*total does not match the batch");
     return segment_inputs_impl(ctx, lb.frames, lb.fs, lb.rs, lb.nwin * lb.n, lb.x0, lb.y0, lb.frame_h, lb.frame_w, lb.segs, lb.nseg, lb.cap,
                                min_h, min_w, mean, std_, pad, channels_last != 0, first, net_cap, net, seg_frame, total, skipped, known, lb.fr);
+}
+
+int32_t swk_debug_resize_table(swk_ctx *ctx, int32_t first, int32_t count, int32_t route, int32_t *bounds, int32_t *coeffs)
+{
+    if (!ctx || !bounds || !coeffs || first < 1 || count < 1 || (route != 0 && route != 1) ||
+        (int64_t)first + count - 1 > (route == 0 ? 512 : 4096))
+        return fail(ctx, SWK_ERR_ARG, "bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t nb = (size_t)count * 24 * 2, nk = (size_t)count * 24 * 343;
+    int32_t *d;
+    NEED(ctx, SL_TMP_OUT, (nb + nk) * 4, d);
+    launch_resize_table(ctx->stream, first, count, route, d, d + nb);
+    HIPCHK(ctx, hipMemcpyAsync(bounds, d, nb * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(coeffs, d + nb, nk * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
 }
 
 int32_t swk_classifier_input(swk_ctx *ctx, const uint8_t *crops, int64_t crops_bytes, const int64_t *offsets,

@@ -168,7 +168,13 @@ void launch_segment_prefix(hipStream_t s, const int32_t *nseg, int F, int seg_ca
 void launch_segment_inputs(hipStream_t s, const uint8_t *frames, int64_t frame_stride, int64_t row_stride, int frame_h, int frame_w,
                            int x0, int y0, const swk_segment *segs, const int32_t *offsets, int F, int seg_cap, int min_h, int min_w,
                            int first, int count, float *net, int32_t *seg_frame, int pad, bool nhwc, const float *mean, const float *sd,
-                           int32_t *oversize);
+                           int32_t *oversize, int32_t *large);
+// Boxes with a side of 513..4096: launch_segment_inputs / _groups append them to `large` ([0] = how many, then 6 ints each: row of net,
+// frame, r0, c0, h, w; room for `count` boxes) and leave their rows of net alone; this writes those rows.  fr: the groups call's frames.
+void launch_segment_inputs_large(hipStream_t s, const uint8_t *frames, int64_t frame_stride, int64_t row_stride, const struct SegFrame *fr,
+                                 const int32_t *large, int nlarge, float *net, int pad, bool nhwc, const float *mean, const float *sd);
+// diagnostic: Pillow coefficient tables of input sizes first .. first + count - 1; bounds [count][24][2], coeffs [count][24][343]
+void launch_resize_table(hipStream_t s, int first, int count, int route, int32_t *bounds, int32_t *coeffs);
 
 // ccl.hip
 struct CclBuffers {
@@ -226,6 +232,6 @@ void launch_ccl_frame_geom(hipStream_t s, const uint8_t *src, int F, const Frame
 void launch_segment_prefix_groups(hipStream_t s, const int32_t *nseg, const SegFrame *fr, int F, int32_t *offsets);
 void launch_segment_inputs_groups(hipStream_t s, const SegFrame *fr, const swk_segment *segs, int seg_stride, const int32_t *offsets,
                                   int F, int min_h, int min_w, int first, int count, float *net, int32_t *seg_frame, int pad, bool nhwc,
-                                  const float *mean, const float *sd, int32_t *oversize);
+                                  const float *mean, const float *sd, int32_t *oversize, int32_t *large);
 
 }  // namespace swk

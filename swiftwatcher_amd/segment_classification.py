@@ -883,7 +883,7 @@ class SegmentClassifier:
                 done[slot].synchronize()
             total, skipped = cut(xb[slot].data_ptr(), fb[slot].data_ptr(), bs, first, pad, nhwc)
             if skipped:
-                raise RuntimeError("%d segment boxes were empty or larger than 512 pixels" % skipped)
+                raise RuntimeError("%d segment boxes were empty or had a side above 4096 pixels" % skipped)
             return total
 
         scores, frames_of = [], []
