@@ -184,6 +184,42 @@ int32_t swk_batch_run(swk_ctx *ctx, const swk_input *in, const swk_params *p, sw
  * frame order. */
 int32_t swk_batch_run_groups(swk_ctx *ctx, const swk_input *groups, int32_t ngroups, const swk_params *p, swk_output *outs);
 
+/* ---- decoder hand-over: 8-bit 4:2:0 YUV -> BGR ------------------------------------------------------------
+ * The reference reads BGR frames from cv2.VideoCapture (io_video.py:85-125); every decoder delivers 4:2:0 YUV.  This is
+ * the conversion a reference user would have applied to raw YUV, cv2.cvtColor(yuv, COLOR_YUV2BGR_I420 / _NV12) of OpenCV
+ * 4.1.0 (requirements.txt:8), restated.  PARITY UNPINNED (ITU-R BT.601, limited range, 20-bit fixed point, all in int32,
+ * arithmetic shift, sat8 = clamp to 0..255):
+ *   y = max(0, Y - 16) * 1220542;  uu = U - 128;  vv = V - 128;  h = 1 << 19
+ *   R = sat8((y + h + 1673527 * vv) >> 20)
+ *   G = sat8((y + h - 852492 * vv - 409993 * uu) >> 20)
+ *   B = sat8((y + h + 2116026 * uu) >> 20)
+ * Chroma is not interpolated: pixel (r, c) uses chroma sample (r >> 1, c >> 1); the chroma planes hold ceil(H / 2) x
+ * ceil(W / 2) samples, so an odd last row or column has a sample of its own. */
+enum { SWK_YUV_I420 = 0,   /* three planes: Y, then U and V of ceil(H/2) x ceil(W/2) bytes each */
+       SWK_YUV_NV12 = 1 }; /* two planes: Y, then ceil(H/2) rows of ceil(W/2) interleaved (U, V) byte pairs */
+
+/* `count` frames of H x W pixels.  Pixel (r, c) of frame f has its luma at y + f * y_frame_stride + r * y_row_stride + c and
+ * its chroma at u (and v) + f * c_frame_stride + (r >> 1) * c_row_stride + (c >> 1) for I420, at u + f * c_frame_stride +
+ * (r >> 1) * c_row_stride + 2 * (c >> 1) (U) and + 1 (V) for NV12 (v is not read).  Strides are bytes; row strides may exceed
+ * the width (decoder surfaces), luma and chroma frame strides are independent (planes of a frame need not be adjacent). */
+typedef struct swk_yuv420 {
+    const uint8_t *y, *u, *v;
+    int32_t mem;            /* SWK_MEM_HOST / SWK_MEM_DEVICE: where all planes live */
+    int32_t layout;         /* SWK_YUV_I420 / SWK_YUV_NV12 */
+    int32_t H, W;           /* frame size in pixels (each 1..32768, odd sizes allowed) */
+    int64_t y_row_stride, y_frame_stride;
+    int64_t c_row_stride, c_frame_stride;
+} swk_yuv420;
+
+/* The rectangle [y0, y0 + Hr) x [x0, x0 + Wr) of every frame, converted to dense BGR: bgr [count][Hr][Wr][3] in host
+ * (bgr_mem = SWK_MEM_HOST) or device memory.  Any origin parity and odd Hr / Wr are fine (a chroma sample is then shared
+ * across the rectangle's edge).  Of a host source only the chroma samples that cover the rectangle and their luma pixels are copied to the
+ * device.  The device result is what swk_input.frames takes (channels = 3, SWK_MEM_DEVICE): the hook for a hardware decoder
+ * whose NV12 surfaces are in device memory already.  SWK_ERR_ARG: a null plane, a rectangle outside the frame, an unknown
+ * layout, count < 1, a row stride below the row's bytes. */
+int32_t swk_yuv420_to_bgr(swk_ctx *ctx, const swk_yuv420 *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
+                          uint8_t *bgr, int32_t bgr_mem);
+
 /* ---- stage-level entry points (host buffers; used by the parity tests and by the
  *      image_filtering.* drop-in functions) ------------------------------------- */
 /* convert_grayscale (image_filtering.py:188-196): [count][H][W][3] -> [count][H][W] */

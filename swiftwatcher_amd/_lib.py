@@ -17,6 +17,7 @@ STAGE_DENSE, STAGE_WHOLE, STAGE_ROWS, STAGE_2D, STAGE_DEVICE = 0, 1, 2, 3, -1   
 STAGES = ("gray", "rpca", "bilateral", "thresh", "opened", "labels")
 ORDER_RASTER, ORDER_BLOCK2X2 = 0, 1
 GRAY_Q14, GRAY_Q15 = 0, 1
+YUV_I420, YUV_NV12 = 0, 1
 K_GRAY, K_IALM_STATS, K_IALM_PASS, K_IALM_SMALL, K_FILTER, K_CCL, K_PROPS, K_COPY = range(8)
 KERNEL_FAMILIES = ["gray", "ialm_stats", "ialm_pass", "ialm_small", "filter", "ccl", "props", "copy"]
 
@@ -69,6 +70,13 @@ class Output(ctypes.Structure):
                 ("planes_on_device", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
 
 
+class Yuv420(ctypes.Structure):
+    _fields_ = [("y", ctypes.c_void_p), ("u", ctypes.c_void_p), ("v", ctypes.c_void_p), ("mem", ctypes.c_int32),
+                ("layout", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("y_row_stride", ctypes.c_int64), ("y_frame_stride", ctypes.c_int64),
+                ("c_row_stride", ctypes.c_int64), ("c_frame_stride", ctypes.c_int64)]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -81,6 +89,7 @@ _SIGS = {
     "swk_ctx_device_bytes": (ctypes.c_int64, [ctypes.c_void_p]),
     "swk_batch_run": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Params), ctypes.POINTER(Output)]),
     "swk_batch_run_groups": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.c_int32, ctypes.POINTER(Params), ctypes.POINTER(Output)]),
+    "swk_yuv420_to_bgr": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv420)] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int32]),
     "swk_bgr2gray": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "swk_ialm": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_rpca_epilogue": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -537,6 +546,61 @@ class Context:
             res["generation"] = generation
         return results
 
+    # ---- decoder hand-over ----
+    def yuv420_to_bgr(self, y, u, v=None, rect=None, device_out=False):
+        """swk_yuv420_to_bgr: 8-bit 4:2:0 frames -> BGR (cv2.cvtColor COLOR_YUV2BGR_I420 / _NV12 of OpenCV 4.1.0 restated, include/swk.h).
+        y: uint8 (count, H, W) or (H, W).  I420: u, v uint8 (count, ceil(H/2), ceil(W/2)).  NV12: v=None and u the interleaved plane,
+        (count, ceil(H/2), ceil(W/2), 2) or (count, ceil(H/2), 2 ceil(W/2)).  All numpy arrays, or all torch tensors on this
+        context's GPU (read in place); contiguous along a row, any row pitch and frame stride (views are fine).
+        rect: (x0, y0, Wr, Hr) inside the frame, None = the whole frame.  Returns BGR (count, Hr, Wr, 3) (no count axis for a 2-D y):
+        a numpy array, or with device_out=True a torch uint8 tensor on the GPU -- what batch_run / batch_run_groups take as frames."""
+        on_device = hasattr(y, "data_ptr") and getattr(y, "is_cuda", False)
+        planes = [y, u] + ([v] if v is not None else [])
+        want = "torch.uint8" if on_device else "uint8"
+        if not on_device:
+            planes = [p if isinstance(p, np.ndarray) and p.dtype == np.uint8 and p.ndim and p.strides[-1] == 1 else np.ascontiguousarray(p, np.uint8)
+                      for p in planes]
+        if any((hasattr(p, "data_ptr") and getattr(p, "is_cuda", False)) != on_device or str(p.dtype) != want for p in planes):
+            raise ValueError("the planes must be uint8, all numpy arrays or all tensors on the context's GPU")
+        single = len(planes[0].shape) == 2
+        if single:
+            planes = [p[None] for p in planes]
+
+        def geometry(p):
+            if on_device:
+                return tuple(p.shape), tuple(int(x) for x in p.stride()), p.data_ptr()
+            return p.shape, p.strides, p.ctypes.data
+        (yshape, ystr, yptr), (cshape, cstr, uptr) = geometry(planes[0]), geometry(planes[1])
+        if len(yshape) != 3 or ystr[2] != 1:
+            raise ValueError("y must be (count, H, W), contiguous along a row")
+        count, H, W = yshape
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        if v is not None:
+            vshape, vstr, vptr = geometry(planes[2])
+            if tuple(cshape) != (count, ch, cw) or tuple(vshape) != (count, ch, cw) or cstr[2] != 1 or tuple(vstr) != tuple(cstr):
+                raise ValueError("u and v must be (count, ceil(H/2), ceil(W/2)) with equal strides, contiguous along a row")
+            layout = YUV_I420
+        else:
+            vptr = None
+            ok = (len(cshape) == 4 and tuple(cshape) == (count, ch, cw, 2) and cstr[3] == 1 and cstr[2] == 2) or \
+                 (len(cshape) == 3 and tuple(cshape) == (count, ch, 2 * cw) and cstr[2] == 1)
+            if not ok:
+                raise ValueError("the NV12 chroma plane must be (count, ceil(H/2), ceil(W/2), 2) or (count, ceil(H/2), 2 ceil(W/2))")
+            layout = YUV_NV12
+        x0, y0, Wr, Hr = rect if rect is not None else (0, 0, W, H)
+        src = Yuv420(y=yptr, u=uptr, v=vptr, mem=MEM_DEVICE if on_device else MEM_HOST, layout=layout, H=H, W=W,
+                     y_row_stride=ystr[1], y_frame_stride=ystr[0], c_row_stride=cstr[1], c_frame_stride=cstr[0])
+        shape = (count, int(Hr), int(Wr), 3) if Hr > 0 and Wr > 0 and count > 0 else (1, 1, 1, 3)          # (the library refuses those)
+        if device_out:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device="cuda:%d" % self.device)
+            optr, omem = ctypes.c_void_p(out.data_ptr()), MEM_DEVICE
+        else:
+            out = np.empty(shape, np.uint8)
+            optr, omem = _ptr(out), MEM_HOST
+        self._check(self._lib.swk_yuv420_to_bgr(self._h, ctypes.byref(src), count, int(x0), int(y0), int(Hr), int(Wr), optr, omem))
+        return out[0] if single else out
+
     # ---- stage-level entry points ----
     def bgr2gray(self, bgr, gray_mode=GRAY_Q14):
         bgr = np.ascontiguousarray(bgr, np.uint8)
@@ -869,6 +933,8 @@ def roi_mask(frame, corners):
     chimney corners ((x1, y1), (x2, y2))."""
     if hasattr(frame, "as_full_frame"):          # a ROI-stream frame (io_roi_stream.RoiFrame): the stored rectangle pasted into a blank frame
         frame = frame.as_full_frame()
+    if not isinstance(frame, np.ndarray):        # a frame that converts itself (io_y4m.Yuv420Frame): the BGR frame it stands for
+        frame = np.asarray(frame)
     if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3 or frame.strides[2] != 1 or frame.strides[1] != 3:
         frame = np.ascontiguousarray(frame, np.uint8)
     c = np.array([corners[0][0], corners[0][1], corners[1][0], corners[1][1]], np.int32)

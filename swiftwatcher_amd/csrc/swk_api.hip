@@ -1310,6 +1310,77 @@ int32_t swk_bgr2gray(swk_ctx *ctx, const uint8_t *bgr, int32_t count, int32_t H,
     return sync(ctx);
 }
 
+// rows x width bytes of each of `count` host frames (first byte src, rows rs apart, frames fs apart) densely to the device
+static int upload_rects(swk_ctx *ctx, uint8_t *dst, const uint8_t *src, int64_t rs, int64_t fs, size_t width, size_t rows, int count)
+{
+    const size_t per = width * rows;
+    if ((size_t)rs == width && rs > 0 && (count == 1 || fs == (int64_t)per)) {
+        HIPCHK(ctx, hipMemcpyAsync(dst, src, per * count, hipMemcpyHostToDevice, ctx->stream));
+        return SWK_OK;
+    }
+    for (int f = 0; f < count; ++f) {
+        const uint8_t *s = src + (int64_t)f * fs;
+        if ((size_t)rs == width) HIPCHK(ctx, hipMemcpyAsync(dst + (size_t)f * per, s, per, hipMemcpyHostToDevice, ctx->stream));
+        else HIPCHK(ctx, hipMemcpy2DAsync(dst + (size_t)f * per, width, s, (size_t)rs, width, rows, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return SWK_OK;
+}
+
+int32_t swk_yuv420_to_bgr(swk_ctx *ctx, const swk_yuv420 *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
+                          uint8_t *bgr, int32_t bgr_mem)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!src || !bgr) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (src->layout != SWK_YUV_I420 && src->layout != SWK_YUV_NV12) return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_I420 or SWK_YUV_NV12)");
+    const bool nv12 = src->layout == SWK_YUV_NV12;
+    if (!src->y || !src->u || (!nv12 && !src->v)) return fail(ctx, SWK_ERR_ARG, "null YUV plane");
+    if (count < 1 || count > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "count must be in 1..2^24");
+    if ((src->mem != SWK_MEM_HOST && src->mem != SWK_MEM_DEVICE) || (bgr_mem != SWK_MEM_HOST && bgr_mem != SWK_MEM_DEVICE))
+        return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
+    const int H = src->H, W = src->W;
+    if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(ctx, SWK_ERR_ARG, "frame size must be 1..32768 on each side");
+    if (x0 < 0 || y0 < 0 || Hr < 1 || Wr < 1 || (int64_t)x0 + Wr > W || (int64_t)y0 + Hr > H)
+        return fail(ctx, SWK_ERR_ARG, "rectangle outside the frame");
+    const int cbytes = nv12 ? 2 : 1;                                  // bytes per chroma sample position in a chroma row
+    if (src->y_row_stride < W || src->c_row_stride < (int64_t)((W + 1) / 2) * cbytes)
+        return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t out_b = (size_t)count * Hr * Wr * 3;
+    const uint8_t *dy = src->y, *du = src->u, *dv = src->v;
+    int64_t y_rs = src->y_row_stride, y_fs = src->y_frame_stride, c_rs = src->c_row_stride, c_fs = src->c_frame_stride;
+    int kx0 = x0, ky0 = y0;
+    if (src->mem == SWK_MEM_HOST) {
+        // only the chroma cells that cover the rectangle, and the luma pixels of those cells (the rectangle grown to even
+        // origins: at most one more row and column), go to the device, densely; the kernel then sees a frame whose origin is
+        // the rectangle's first chroma cell, and the rectangle starts at its origin's parity
+        const int cy0 = y0 >> 1, ch = ((y0 + Hr - 1) >> 1) - cy0 + 1, cx0 = x0 >> 1, cw = ((x0 + Wr - 1) >> 1) - cx0 + 1;
+        const int lh = y0 + Hr - 2 * cy0, lw = x0 + Wr - 2 * cx0;
+        const size_t yb = ((size_t)count * lh * lw + 15) & ~(size_t)15, cb = ((size_t)count * ch * cw * cbytes + 15) & ~(size_t)15;
+        uint8_t *din;
+        NEED(ctx, SL_TMP_IN, yb + cb * (nv12 ? 1 : 2), din);
+        int rc = upload_rects(ctx, din, src->y + (int64_t)2 * cy0 * y_rs + 2 * cx0, y_rs, y_fs, (size_t)lw, (size_t)lh, count);
+        if (rc) return rc;
+        const int64_t coff = (int64_t)cy0 * c_rs + (int64_t)cx0 * cbytes;
+        rc = upload_rects(ctx, din + yb, src->u + coff, c_rs, c_fs, (size_t)cw * cbytes, (size_t)ch, count);
+        if (rc) return rc;
+        if (!nv12) {
+            rc = upload_rects(ctx, din + yb + cb, src->v + coff, c_rs, c_fs, (size_t)cw, (size_t)ch, count);
+            if (rc) return rc;
+        }
+        dy = din; du = din + yb; dv = nv12 ? nullptr : din + yb + cb;
+        y_rs = lw; y_fs = (int64_t)lh * lw; c_rs = (int64_t)cw * cbytes; c_fs = (int64_t)ch * c_rs;
+        kx0 = x0 & 1; ky0 = y0 & 1;
+    }
+    uint8_t *dout = bgr;
+    if (bgr_mem == SWK_MEM_HOST) NEED(ctx, SL_TMP_OUT, out_b, dout);
+    {
+        Timed t(ctx, SWK_K_GRAY);
+        launch_yuv420_to_bgr(ctx->stream, src->layout, dy, du, dv, y_fs, y_rs, c_fs, c_rs, kx0, ky0, count, Hr, Wr, dout);
+    }
+    if (bgr_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(bgr, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
 int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, double lmbda, double tol, int32_t maxiter,
                  double *A, double *E, int32_t *iters)
 {

@@ -160,6 +160,11 @@ void launch_resize_linear(hipStream_t s, const uint8_t *src, int F, int H, int W
 void launch_filter_fused(hipStream_t s, const uint8_t *src, int F, int H, int W, const BilateralTables &t,
                          int use_fma, int thresh, uint8_t *bil_out, uint8_t *thr_out, uint8_t *open_out);
 
+// yuv.hip: the rectangle [y0, y0 + Hr) x [x0, x0 + Wr) of F 4:2:0 frames (layout SWK_YUV_I420 / SWK_YUV_NV12; strides in bytes)
+// -> dense BGR [F][Hr][Wr][3]
+void launch_yuv420_to_bgr(hipStream_t s, int layout, const uint8_t *y, const uint8_t *u, const uint8_t *v, int64_t y_fs, int64_t y_rs,
+                          int64_t c_fs, int64_t c_rs, int x0, int y0, int F, int Hr, int Wr, uint8_t *out);
+
 // classify_input.hip
 void launch_classifier_input(hipStream_t s, const uint8_t *crops, const int64_t *offsets, const int32_t *hw, int nseg,
                              uint8_t *patches, float *net, int pad, bool nhwc, const float *mean, const float *sd);

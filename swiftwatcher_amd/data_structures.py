@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib
 from . import image_filtering as img
+from .io_y4m import Yuv420Frame
 
 STAGE_KEYS = OrderedDict([("gray", "grayscale"), ("rpca", "RPCA"), ("bilateral", "bilateral"),
                           ("thresh", "thresh_15"), ("opened", "opened"), ("labels", "cc_labeling")])
@@ -266,8 +267,18 @@ class WindowBatch:
     (_batch, _index = k); SegmentClassifier asks predictions(classifier) for the whole table once per window.  Returns None
     when the context has moved on (the caller then classifies from the segments' images, as before)."""
 
-    def __init__(self, ctx, generation, total, min_seg_size, queue=None, keys=None):
+    def __init__(self, ctx, generation, total, min_seg_size, queue=None, keys=None, hold=None):
         self.ctx, self.generation, self.total, self.min_seg_size = ctx, generation, total, tuple(min_seg_size)
+        # device frames the batch ran on that nobody else keeps alive (stack_frames' BGR conversion of 4:2:0 frames): the context
+        # reads them again when the classifier's inputs are cut (swk_segment_inputs_last keeps the caller's pointer).  Segments
+        # outlive their window (events): the buffer is let go when the context's next window batch is made -- the context has
+        # moved on by then and serves this batch no more
+        self.hold = hold
+        with ctx._lock:
+            prev = ctx.__dict__.get("_holding_batch")
+            if prev is not None:
+                prev.hold = None
+            ctx.__dict__["_holding_batch"] = self if hold is not None else None
         # the segments' dropout keys in batch order (batch_keys), or a zero-argument callable that makes them: only a classifier with a
         # dropout_seed asks for them
         self.keys = keys
@@ -408,7 +419,7 @@ class FrameQueue(deque):
             if self._staging is None or self._staging.shape != shape:
                 self._staging = _lib.pinned_empty(shape, np.uint8, device=self.device)  # page-locked: the upload is one DMA
             return self._staging
-        return stack_frames(frames, crop_region, min_seg_size, buffer)
+        return stack_frames(frames, crop_region, min_seg_size, buffer, self.device)
 
     def segment_queue(self, min_seg_size, crop_region):
         """:187-217: RPCA -> bilateral -> threshold -> opening -> CCL -> region properties ->
@@ -435,7 +446,8 @@ class FrameQueue(deque):
             self._classifier_hint = None
         # (the closure binds the records, not res: res holds the window's stage planes)
         batch = WindowBatch(ctx, generation, int(nseg.sum()), min_seg_size, queue=self,
-                            keys=lambda r=res["segs"], s=nseg, m=tuple(slot.frame_number for slot in self): batch_keys(r, s, m)) if stack.ndim == 4 else None
+                            keys=lambda r=res["segs"], s=nseg, m=tuple(slot.frame_number for slot in self): batch_keys(r, s, m),
+                            hold=_device_stack(stack)) if stack.ndim == 4 else None
         self._last_batch = batch
         hint = self._classifier_hint() if self._classifier_hint is not None else None
         if hint is not None and batch is not None:
@@ -456,7 +468,7 @@ def _stages_on_request(frames, crop_region, min_seg_size, params, device):
     def read(key, pos):
         if "planes" not in state:
             ctx = _lib.default_context(device)
-            stack, (rx, ry), (Hc, Wc), backwards = stack_frames(frames, crop_region, min_seg_size, ctx.staging)
+            stack, (rx, ry), (Hc, Wc), backwards = stack_frames(frames, crop_region, min_seg_size, ctx.staging, device)
             res = ctx.batch_run(stack, 1, len(frames), crop=(rx, ry, Wc, Hc), params=params, stages=tuple(STAGE_KEYS), device_stages=True,
                                 reverse_frames=backwards)
             state["planes"] = res["planes"]
@@ -464,13 +476,16 @@ def _stages_on_request(frames, crop_region, min_seg_size, params, device):
     return read
 
 
-def stack_frames(frames, crop_region, min_seg_size, buffer):
+def stack_frames(frames, crop_region, min_seg_size, buffer, device=0):
     """frames (in the batch's frame order) -> (stack (F, Hm, Wm[, C]) uint8 in page-locked memory, (x, y) of the ROI inside a stacked
     frame, ROI (Hc, Wc), reversed: the stack holds the frames in the opposite order).  Full decoded frames are cropped to the ROI plus its margin into buffer(shape) (swk_stage_frames).
     RoiFrames of a ROI-stream reader (io_roi_stream.py) already ARE that rectangle: when they sit, in this order, in one of the
-    reader's page-locked blocks, the block itself is the stack -- no copy at all."""
+    reader's page-locked blocks, the block itself is the stack -- no copy at all.
+    4:2:0 frames (io_y4m.Yuv420Frame) are staged as they are and converted to BGR on GPU `device`: the stack is then a device tensor."""
     first = frames[0]
     (ya, yb, xa, xb), (x0, y0, x1, y1) = _margin_rect(first.shape, crop_region, min_seg_size)
+    if isinstance(first, Yuv420Frame):
+        return _stack_yuv420(frames, (ya, yb, xa, xb), buffer, device), (x0 - xa, y0 - ya), (y1 - y0, x1 - x0), False
     if hasattr(first, "roi"):
         oy, ox = first.origin
         h, w = first.roi.shape[:2]
@@ -490,6 +505,33 @@ def stack_frames(frames, crop_region, min_seg_size, buffer):
     stack = buffer((len(frames), yb - ya, xb - xa) + first.shape[2:])
     _lib.stage_frames(frames, ya, yb, xa, xb, stack)
     return stack, (x0 - xa, y0 - ya), (y1 - y0, x1 - x0), False
+
+
+def _device_stack(stack):
+    """The stack if it lives on the GPU (a tensor), else None."""
+    return None if isinstance(stack, np.ndarray) else stack
+
+
+def _stack_yuv420(frames, rect, buffer, device):
+    """The rectangle (ya, yb, xa, xb) of 4:2:0 frames (io_y4m.Yuv420Frame) as a BGR stack (F, yb - ya, xb - xa, 3) ON THE GPU (a
+    torch uint8 tensor; batch_run reads it in place): the chroma samples that cover the rectangle and their luma pixels (the
+    rectangle grown to even origins) are staged in page-locked memory -- 1.5 bytes per pixel instead of 3 --, uploaded once for the
+    whole batch and converted there (swk_yuv420_to_bgr).  The same pixels as np.asarray(frame)[ya:yb, xa:xb], bit for bit."""
+    ya, yb, xa, xb = rect
+    if not all(isinstance(f, Yuv420Frame) and f.shape == frames[0].shape for f in frames):
+        raise ValueError("a window mixes 4:2:0 frames with other frames")
+    F = len(frames)
+    cy0, cy1, cx0, cx1 = ya >> 1, ((yb - 1) >> 1) + 1, xa >> 1, ((xb - 1) >> 1) + 1
+    lh, lw, ch, cw = yb - 2 * cy0, xb - 2 * cx0, cy1 - cy0, cx1 - cx0
+    luma, chroma = F * lh * lw, F * ch * cw
+    staged = buffer((luma + 2 * chroma,))
+    Y = staged[:luma].reshape(F, lh, lw)
+    U = staged[luma:luma + chroma].reshape(F, ch, cw)
+    V = staged[luma + chroma:].reshape(F, ch, cw)
+    _lib.stage_frames([f.y for f in frames], 2 * cy0, yb, 2 * cx0, xb, Y)
+    _lib.stage_frames([f.u for f in frames], cy0, cy1, cx0, cx1, U)
+    _lib.stage_frames([f.v for f in frames], cy0, cy1, cx0, cx1, V)
+    return _lib.default_context(device).yuv420_to_bgr(Y, U, V, rect=(xa - 2 * cx0, ya - 2 * cy0, xb - xa, yb - ya), device_out=True)
 
 
 def _margin_rect(frame_shape, crop_region, min_seg_size):
@@ -530,7 +572,7 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
     ordered = []
     for w in order:
         ordered.extend(windows[w][0][::-1])                  # queue index 0 = newest = last frame read (:134)
-    stack, (rx, ry), (Hc, Wc), backwards = stack_frames(ordered, crop_region, min_seg_size, ctx.staging)
+    stack, (rx, ry), (Hc, Wc), backwards = stack_frames(ordered, crop_region, min_seg_size, ctx.staging, device)
     res = ctx.batch_run(stack, len(windows), n, crop=(rx, ry, Wc, Hc), params=params, stages=(), reverse_frames=backwards)
     nseg = res["nseg"]
     if np.any(nseg > res["segs"].shape[1]):
@@ -539,7 +581,7 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
     # (bound as default arguments: the loop below reuses the name `numbers`, and the keys may be made long after it)
     batch_numbers = tuple(k for w in order for k in list(windows[w][1])[::-1])
     batch = WindowBatch(ctx, res["generation"], int(nseg.sum()), min_seg_size, queue=owner,
-                        keys=lambda r=res["segs"], s=nseg, m=batch_numbers: batch_keys(r, s, m)) if stack.ndim == 4 else None
+                        keys=lambda r=res["segs"], s=nseg, m=batch_numbers: batch_keys(r, s, m), hold=_device_stack(stack)) if stack.ndim == 4 else None
     if batch is not None and classifier is not None:
         batch.launch(classifier)
     if info is not None:
@@ -588,7 +630,7 @@ def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, 
                 raise ValueError("every window of every group needs the same number of frames")
         ordered = [fr for frames, _, _ in windows for fr in frames[::-1]]          # queue index 0 = newest (:134)
         stack, (rx, ry), (Hc, Wc), backwards = stack_frames(ordered, crop_region, min_seg_size,
-                                                            lambda shape, s=slot: _group_staging(ctx, s, shape))
+                                                            lambda shape, s=slot: _group_staging(ctx, s, shape), device)
         specs.append(dict(frames=stack, nwin=len(windows), n=n, crop=(rx, ry, Wc, Hc), reverse_frames=backwards))
     results = ctx.batch_run_groups(specs, params=params, stages=())
     for r in results:
@@ -601,7 +643,8 @@ def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, 
     def keys(records=tuple(records)):
         return np.concatenate([batch_keys(*rec) for rec in records])
 
-    batch = WindowBatch(ctx, results[0]["generation"], total, min_seg_size, keys=keys) if bgr else None
+    batch = WindowBatch(ctx, results[0]["generation"], total, min_seg_size, keys=keys,
+                        hold=[_device_stack(spec["frames"]) for spec in specs]) if bgr else None
     if batch is not None and classifier is not None:
         batch.launch(classifier)
     out = [[] for _ in groups]

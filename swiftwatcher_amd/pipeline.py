@@ -88,9 +88,14 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
 
 
 def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, **kw):
-    """Decoded frames (oldest first) -> (swift count, events).  Regions either explicit or from corners=...; params as in
+    """Decoded frames (oldest first) -> (swift count, events).  frames may also be a reader (get_n_frames / read_frame / total_frames,
+    e.g. io_y4m.Y4MReader: its fps holds) or the path of a .y4m file.  Regions either explicit or from corners=...; params as in
     swift_counting_algorithm."""
-    events = swift_counting_algorithm(ArrayReader(frames, fps=fps), crop_region, roi_mask, params=params, **kw)
+    if isinstance(frames, (str, bytes)) or hasattr(frames, "__fspath__"):
+        from .io_y4m import Y4MReader
+        frames = Y4MReader(frames)
+    reader = frames if hasattr(frames, "get_n_frames") else ArrayReader(frames, fps=fps)
+    events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, **kw)
     return ec.count_swifts(events), events
 
 
