@@ -80,6 +80,22 @@ int32_t swk_last_integer_start_windows(swk_ctx *ctx, int32_t *windows);
  * Every output but G may be NULL.  No IALM iteration runs; the counters of the context do not move. */
 int32_t swk_debug_ialm_start(swk_ctx *ctx, const uint8_t *X, int32_t nwin, int32_t n, int32_t P, double lmbda, double *G,
                              uint64_t *sumsq, uint32_t *maxv, int32_t *int_gram, double *scal, int32_t *nblk_out, int32_t *gram8_ran);
+/* Diagnostic: the start and the first step of the IALM alone, on nwin host windows X[nwin][n][P] (u8), staged and checked like
+ * swk_debug_ialm_start's and run with the context's current switches (swk_set_ialm_variant, swk_set_integer_start, swk_set_eig_method,
+ * swk_set_start_refine): the start, then what the chain runs next through the same helper -- the chip-wide slab sum when a window has
+ * more than 4 slabs, the small-matrix step of k = 0 (k_ialm_small, or k_ialm_small_wide above 64 frames and under variant 6) and, with
+ * the refinement on, the accurate first iteration of the windows that step flagged (csrc/ialm_refine.hip).  Per window:
+ *   B_fin[nwin][n][n]  B_1 = I - W / mu_0 as iteration 1's pass reads it: A_1 = M_1 B_1 with M_1 pixels x frames, B_1 row-major (NOT
+ *                      symmetric where the window was refined);
+ *   B_std[nwin][n][n]  the same matrix as the small-matrix step left it, copied before the refinement is launched;
+ *   refine             0 = not asked for, 2 = refined, 3 = given up (rank deficient or not converged), 4 = over the work cap of the
+ *                      double-double Gram matrix from the pixels;
+ *   cond_sum           the step's estimate ||G_1||_F sum_i 1 / lambda_i (0 from k_ialm_small_wide, which makes none);
+ *   sweeps             solver steps of k = 0: Newton-Schulz iterations, or 100 + Jacobi sweeps;
+ *   int_gram, scal[nwin][4]   as swk_debug_ialm_start returns them.
+ * Every output but B_fin may be NULL.  No pass of an iteration runs; the counters of the context do not move. */
+int32_t swk_debug_ialm_first_step(swk_ctx *ctx, const uint8_t *X, int32_t nwin, int32_t n, int32_t P, double lmbda, double *B_fin,
+                                  double *B_std, int32_t *refine, double *cond_sum, int32_t *sweeps, int32_t *int_gram, double *scal);
 /* Diagnostic: how each group of the last swk_batch_run / swk_batch_run_groups reached the device, one value per group (up to cap):
  * 0 = one copy of a packed ROI, 1 = the whole buffer as it lies, read at (x0, y0) with the caller's strides, 2 = one copy per frame
  * (full-width rows), 3 = one 2-D copy per frame; -1 = a device group, read in place.  Returns the number of groups of that call (0 before

@@ -105,6 +105,7 @@ _SIGS = {
     "swk_set_integer_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
     "swk_last_integer_start_windows": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "swk_debug_ialm_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double] + [ctypes.c_void_p] * 7),
+    "swk_debug_ialm_first_step": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double] + [ctypes.c_void_p] * 7),
     "swk_last_host_stage": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "swk_debug_resize_table": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_last_eig_sweeps": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
@@ -419,6 +420,21 @@ class Context:
                                                    _ptr(int_gram), _ptr(scal), _ptr(nblk), _ptr(ran)))
         return dict(G=G, sumsq=sumsq, maxv=maxv, int_gram=int_gram, dual_norm=scal[:, 0], mu_0=scal[:, 1], thr_0=scal[:, 2],
                     dnorm=scal[:, 3], nblk=int(nblk[0]), gram8_ran=int(ran[0]))
+
+    def debug_ialm_first_step(self, windows, lmbda=0.01):
+        """The start and the first step of the IALM alone on uint8 windows [nwin][n][P] (swk_debug_ialm_first_step), with the
+        context's current pass variant, integer-start switch, solver and refinement threshold: dict of B_fin, B_std [nwin][n][n]
+        (B_1 as iteration 1's pass would read it -- A_1 = M_1 B_1, M_1 pixels x frames -- and as the small-matrix step left it),
+        refine, cond_sum, sweeps, int_gram, dual_norm, mu_0, thr_0, dnorm per window."""
+        x = np.ascontiguousarray(windows, np.uint8)
+        nwin, n, P = x.shape
+        B_fin, B_std = np.zeros((nwin, n, n), np.float64), np.zeros((nwin, n, n), np.float64)
+        refine, sweeps, int_gram = np.zeros(nwin, np.int32), np.zeros(nwin, np.int32), np.zeros(nwin, np.int32)
+        cond_sum, scal = np.zeros(nwin, np.float64), np.zeros((nwin, 4), np.float64)
+        self._check(self._lib.swk_debug_ialm_first_step(self._h, _ptr(x), nwin, n, P, float(lmbda), _ptr(B_fin), _ptr(B_std),
+                                                        _ptr(refine), _ptr(cond_sum), _ptr(sweeps), _ptr(int_gram), _ptr(scal)))
+        return dict(B_fin=B_fin, B_std=B_std, refine=refine, cond_sum=cond_sum, sweeps=sweeps, int_gram=int_gram,
+                    dual_norm=scal[:, 0], mu_0=scal[:, 1], thr_0=scal[:, 2], dnorm=scal[:, 3])
 
     def last_host_stage(self, cap=256):
         """How each group of the last batch call reached the device (swk_last_host_stage): a list of STAGE_DENSE / STAGE_WHOLE /

@@ -422,9 +422,34 @@ int ialm_start(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want
     return SWK_OK;
 }
 
-// One chain over the job's windows on the context's stream: start, then per iteration pass -> (slab sum) -> small-matrix step, until
-// every window has stopped.  speculate: the M-state pass may guess (sparse-image stores and stopping norms skipped far from the
-// tolerance).  *bp describes the buffers the chain worked in.
+// The small-matrix step of iteration k over the chain's windows: the chip-wide slab sum where a window has more than 4 slabs, then the
+// step's kernel (k_ialm_small_wide above 64 frames or under pass variant 6, k_ialm_small under the context's solver otherwise).
+void ialm_small_step(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, const IalmBuffers &b, int k, double *wide_work)
+{
+    hipStream_t s = ctx->stream;
+    Timed t(ctx, SWK_K_IALM_SMALL);
+    if (b.nblk > 4) launch_gram_reduce(s, b);
+    if (plan.small_wide) launch_ialm_small_wide(s, b, k, job.lmbda, job.tol, job.maxiter, wide_work);
+    else launch_ialm_small(s, b, k, job.lmbda, job.tol, job.maxiter, ctx->eig_method);
+}
+
+// The first step after the start (ialm_chain, and swk_debug_ialm_first_step, which stops after it): the small-matrix step of k = 0,
+// then the windows that step found ill-conditioned get their first iteration's matrix B_1 again, from a double-double Cholesky factor
+// of the exact integer X^T X -- of a double-double M_1^T M_1 where the window had no integer start -- (one workgroup per flagged
+// window; the others leave at the first branch).  B_std (optional, host, [nwin][n][n]): the step's own B_1, copied out in stream
+// order before the refinement is launched.
+int ialm_first_step(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, const IalmBuffers &b, double *wide_work, double *B_std)
+{
+    hipStream_t s = ctx->stream;
+    ialm_small_step(ctx, job, plan, b, 0, wide_work);
+    if (B_std) HIPCHK(ctx, hipMemcpyAsync(B_std, b.Bm, (size_t)b.nwin * b.n * b.n * 8, hipMemcpyDeviceToHost, s));
+    if (b.refine > 0.0) { Timed t(ctx, SWK_K_IALM_SMALL); launch_ialm_refine_start(s, b); }
+    return SWK_OK;
+}
+
+// One chain over the job's windows on the context's stream: start, first step, then per iteration pass -> (slab sum) -> small-matrix
+// step, until every window has stopped.  speculate: the M-state pass may guess (sparse-image stores and stopping norms skipped far
+// from the tolerance).  *bp describes the buffers the chain worked in.
 int ialm_chain(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want_A, bool want_E, bool speculate, IalmBuffers *bp)
 {
     int rc = ensure_poll_events(ctx);
@@ -434,19 +459,8 @@ int ialm_chain(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want
     IalmBuffers &b = *bp;
     hipStream_t s = ctx->stream;
     const int check_from = 6;     // no window converges earlier (mu grows 1.5x per iteration)
-    const double lmbda = job.lmbda, tol = job.tol;
     const int maxiter = job.maxiter;
-    auto small_step = [&](int k) {
-        Timed t(ctx, SWK_K_IALM_SMALL);
-        if (b.nblk > 4) launch_gram_reduce(s, b);
-        if (plan.small_wide) launch_ialm_small_wide(s, b, k, lmbda, tol, maxiter, wide_work);
-        else launch_ialm_small(s, b, k, lmbda, tol, maxiter, ctx->eig_method);
-    };
-    small_step(0);
-    // windows that step found ill-conditioned get their first iteration's matrix B_1 again, from a double-double Cholesky factor
-    // of the exact integer X^T X -- of a double-double M_1^T M_1 where the window had no integer start -- (one workgroup per flagged
-    // window; the others leave at the first branch)
-    if (b.refine > 0.0) { Timed t(ctx, SWK_K_IALM_SMALL); launch_ialm_refine_start(s, b); }
+    if ((rc = ialm_first_step(ctx, job, plan, b, wide_work, nullptr))) return rc;
     for (int k = 1; k <= maxiter + 2; ++k) {
         // convergence is polled two iterations late so the host never stalls the queue; the launches made
         // meanwhile for an already finished batch return at their first branch
@@ -457,7 +471,7 @@ int ialm_chain(swk_ctx *ctx, const IalmJob &job, const IalmPlan &plan, bool want
         }
         if (k > maxiter) break;
         { Timed t(ctx, SWK_K_IALM_PASS); launch_ialm_pass(s, b, k == 1 ? 1 : 2, plan.variant, k, ctx->pass_tune); }
-        small_step(k);
+        ialm_small_step(ctx, job, plan, b, k, wide_work);
         if (k >= check_from) {
             HIPCHK(ctx, hipMemcpyAsync(&ctx->h_active[k & 1], b.active, sizeof(int), hipMemcpyDeviceToHost, s));
             HIPCHK(ctx, hipEventRecord(ctx->ev_poll[k & 1], s));
@@ -1412,25 +1426,36 @@ int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, doub
     return SWK_OK;
 }
 
-// Diagnostic (swk_debug.h): the start of ialm_chain on host windows, and what it left for the first small-matrix step.
-int32_t swk_debug_ialm_start(swk_ctx *ctx, const uint8_t *X, int32_t nwin, int32_t n, int32_t P, double lmbda, double *G,
-                             uint64_t *sumsq, uint32_t *maxv, int32_t *int_gram, double *scal, int32_t *nblk_out, int32_t *gram8_ran)
+// The diagnostics below stage nwin host windows X[nwin][n][P] like swk_ialm's window -- the library's own allocation, padded to whole
+// dwords past the last pixel (k_gram_u8) -- and run the chain's start on them under the context's switches.
+static int debug_stage_and_start(swk_ctx *ctx, const uint8_t *X, int nwin, int n, int P, double lmbda, IalmJob *job, IalmPlan *plan,
+                                 IalmBuffers *b, double **wide_work)
 {
-    if (!ctx || !X || !G || nwin < 1 || n < 1 || n > kMaxNWide || P < 1 || !(lmbda > 0.0)) return fail(ctx, SWK_ERR_ARG, "bad argument");
+    if (!ctx || !X || nwin < 1 || n < 1 || n > kMaxNWide || P < 1 || !(lmbda > 0.0)) return fail(ctx, SWK_ERR_ARG, "bad argument");
     if ((int64_t)nwin * n * P >= (1ll << 31)) return fail(ctx, SWK_ERR_ARG, "too many pixels in one call");
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    // staged like swk_ialm's window: the library's own allocation, padded to whole dwords past the last pixel (k_gram_u8)
     const size_t elems = (size_t)nwin * n * P;
     uint8_t *dX, *dS;
     NEED(ctx, SL_X, elems + 4, dX);
     NEED(ctx, SL_S, elems, dS);
-    HIPCHK(ctx, hipMemcpyAsync(dX, X, elems, hipMemcpyHostToDevice, s));
-    const IalmPlan plan = plan_ialm(ctx, n, P, nwin, false, 0);
+    HIPCHK(ctx, hipMemcpyAsync(dX, X, elems, hipMemcpyHostToDevice, ctx->stream));
+    *plan = plan_ialm(ctx, n, P, nwin, false, 0);
+    *job = IalmJob{dX, dS, nwin, n, P, nullptr, lmbda, 1e-3, 100};
+    return ialm_start(ctx, *job, *plan, false, false, b, wide_work);
+}
+
+// Diagnostic (swk_debug.h): the start of ialm_chain on host windows, and what it left for the first small-matrix step.
+int32_t swk_debug_ialm_start(swk_ctx *ctx, const uint8_t *X, int32_t nwin, int32_t n, int32_t P, double lmbda, double *G,
+                             uint64_t *sumsq, uint32_t *maxv, int32_t *int_gram, double *scal, int32_t *nblk_out, int32_t *gram8_ran)
+{
+    if (!G) return fail(ctx, SWK_ERR_ARG, "bad argument");
+    IalmJob job;
+    IalmPlan plan;
     IalmBuffers b;
     double *wide_work = nullptr;
-    int rc = ialm_start(ctx, IalmJob{dX, dS, nwin, n, P, nullptr, lmbda, 1e-3, 100}, plan, false, false, &b, &wide_work);
+    int rc = debug_stage_and_start(ctx, X, nwin, n, P, lmbda, &job, &plan, &b, &wide_work);
     if (rc) return rc;
+    hipStream_t s = ctx->stream;
     if (b.nblk > 4) launch_gram_reduce(s, b);          // as the first small-matrix step does (ialm_chain)
     // the slabs that step would sum: the first nred of every window
     const size_t nn = (size_t)n * n;
@@ -1458,6 +1483,34 @@ int32_t swk_debug_ialm_start(swk_ctx *ctx, const uint8_t *X, int32_t nwin, int32
     }
     if (nblk_out) *nblk_out = b.nblk;
     if (gram8_ran) *gram8_ran = b.use_gram8;
+    return SWK_OK;
+}
+
+// Diagnostic (swk_debug.h): the start and the first step of ialm_chain on host windows, and the matrix B_1 they leave for iteration 1's pass.
+int32_t swk_debug_ialm_first_step(swk_ctx *ctx, const uint8_t *X, int32_t nwin, int32_t n, int32_t P, double lmbda, double *B_fin,
+                                  double *B_std, int32_t *refine, double *cond_sum, int32_t *sweeps, int32_t *int_gram, double *scal)
+{
+    if (!B_fin) return fail(ctx, SWK_ERR_ARG, "bad argument");
+    IalmJob job;
+    IalmPlan plan;
+    IalmBuffers b;
+    double *wide_work = nullptr;
+    int rc = debug_stage_and_start(ctx, X, nwin, n, P, lmbda, &job, &plan, &b, &wide_work);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    if ((rc = ialm_first_step(ctx, job, plan, b, wide_work, B_std))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(B_fin, b.Bm, (size_t)nwin * n * n * 8, hipMemcpyDeviceToHost, s));
+    std::vector<IalmWin> hw(nwin);
+    HIPCHK(ctx, hipMemcpyAsync(hw.data(), b.win, (size_t)nwin * sizeof(IalmWin), hipMemcpyDeviceToHost, s));
+    if ((rc = sync(ctx))) return rc;
+    for (int w = 0; w < nwin; ++w) {
+        const IalmWin &st = hw[w];
+        if (refine) refine[w] = st.refine;
+        if (cond_sum) cond_sum[w] = st.cond_sum;
+        if (sweeps) sweeps[w] = st.sweeps;
+        if (int_gram) int_gram[w] = st.int_gram;
+        if (scal) { scal[4 * w] = st.dual_norm; scal[4 * w + 1] = st.cur.mu; scal[4 * w + 2] = st.cur.thr; scal[4 * w + 3] = st.dnorm; }
+    }
     return SWK_OK;
 }
 
