@@ -18,548 +18,14 @@ keep_probability score a segment under many dropout masks in one launch (swk_nhw
 SegmentClassifier(dropout_seed=...) decides by one such realisation.  The mask is the library's own counter-based one (include/swk.h),
 not torch's generator stream: the distribution of the reference's decision is reproduced, not a single run of it.
 """
-import ctypes
 import os
 import threading
 
 import numpy as np
 import torch
-from torch import nn
 
-IMAGENET_MEAN = (0.485, 0.456, 0.406)      # segment_classification.py:23
-IMAGENET_STD = (0.229, 0.224, 0.225)
-RESIZE = 24                                  # :20
-PAD = (224 - 24) // 2                        # :21
-
-
-class Fire(nn.Module):
-    """torchvision.models.squeezenet.Fire: 1x1 squeeze, then 1x1 and 3x3 expands concatenated."""
-
-    def __init__(self, inplanes, squeeze_planes, expand1x1_planes, expand3x3_planes):
-        super().__init__()
-        self.squeeze = nn.Conv2d(inplanes, squeeze_planes, kernel_size=1)
-        self.squeeze_activation = nn.ReLU(inplace=True)
-        self.expand1x1 = nn.Conv2d(squeeze_planes, expand1x1_planes, kernel_size=1)
-        self.expand1x1_activation = nn.ReLU(inplace=True)
-        self.expand3x3 = nn.Conv2d(squeeze_planes, expand3x3_planes, kernel_size=3, padding=1)
-        self.expand3x3_activation = nn.ReLU(inplace=True)
-
-    def forward(self, x):
-        x = self.squeeze_activation(self.squeeze(x))
-        return torch.cat([self.expand1x1_activation(self.expand1x1(x)),
-                          self.expand3x3_activation(self.expand3x3(x))], 1)
-
-
-class SqueezeNet10(nn.Module):
-    """SqueezeNet 1.0 with the module names of torchvision's, so model.pt's state_dict
-    (features.{0,3,4,5,7,8,9,10,12}.*, classifier.1.*) loads with strict=True."""
-
-    def __init__(self, num_classes=2):
-        super().__init__()
-        self.num_classes = num_classes
-        self.features = nn.Sequential(
-            nn.Conv2d(3, 96, kernel_size=7, stride=2), nn.ReLU(inplace=True),
-            nn.MaxPool2d(kernel_size=3, stride=2, ceil_mode=True),
-            Fire(96, 16, 64, 64), Fire(128, 16, 64, 64), Fire(128, 32, 128, 128),
-            nn.MaxPool2d(kernel_size=3, stride=2, ceil_mode=True),
-            Fire(256, 32, 128, 128), Fire(256, 48, 192, 192), Fire(384, 48, 192, 192), Fire(384, 64, 256, 256),
-            nn.MaxPool2d(kernel_size=3, stride=2, ceil_mode=True),
-            Fire(512, 64, 256, 256))
-        self.classifier = nn.Sequential(nn.Dropout(p=0.5), nn.Conv2d(512, num_classes, kernel_size=1),
-                                        nn.ReLU(inplace=True), nn.AdaptiveAvgPool2d((1, 1)))
-
-    def forward(self, x):
-        return torch.flatten(self.classifier(self.features(x)), 1)
-
-
-def _dropout_head(x, pos, bg, n_pos, hw, hb, keys, seed, samples):
-    """swk_nhwc_head2_dropout_relu_mean on PyTorch's current stream: x (k, c, h, w) channels-last, the live positions `pos` of the last
-    Fire's output; bg (n_pos, c) or None (every position live); keys (k,) int64 tensor holding the uint64 keys.  -> (k, samples, 2)."""
-    from . import _lib
-    lib = _lib.load()
-    k = x.shape[0]
-    if not (x.is_contiguous(memory_format=torch.channels_last) and hw.shape[0] == 2 and keys.shape[0] == k and keys.is_contiguous()):
-        raise RuntimeError("the dropout head needs a channels-last tensor, a two-class head and one key per segment")
-    out = torch.empty((k, samples, 2), dtype=torch.float32, device=x.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-    rc = lib.swk_nhwc_head2_dropout_relu_mean(stream, x.data_ptr(), k, x.shape[2] * x.shape[3], x.shape[1], pos.data_ptr(),
-                                              None if bg is None else bg.data_ptr(), n_pos, hw.data_ptr(), hb.data_ptr(), keys.data_ptr(),
-                                              ctypes.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), samples, out.data_ptr())
-    if rc:
-        raise RuntimeError("swk_nhwc_head2_dropout_relu_mean failed (%d)" % rc)
-    return out
-
-
-def _affected(lo, hi, k, st, pad, out_size):
-    """Outputs of a (k, stride, pad) window layer that see any input index in [lo, hi]."""
-    a = -((-(lo + pad - k + 1)) // st)          # ceil
-    b = (hi + pad) // st
-    return max(a, 0), min(b, out_size - 1)
-
-
-class CroppedSqueezeNet10:
-    """Receptive-field cropped evaluation of SqueezeNet10 for this classifier's inputs.
-
-    Every input is a 24x24 patch in the middle of a 224x224 image whose other 89 % is ONE constant (Pad(100) then
-    Normalize, segment_classification.py:21-23).  Outside the patch's receptive field every activation is therefore
-    the same for every segment: it is computed once, from a blank image, when the model is loaded.  Per batch only
-    the affected square of each feature map is evaluated -- on a tile cut from that background map (which supplies
-    the halo a 3x3 window needs) with the live values pasted in its middle and the layer run without padding:
-
-        input 40x40 (rows 92..131) -> conv1 17x17 (46..62 of 109) -> pool 8x8 (23..30 of 54)
-        -> fire2..4: 10, 12, 14 -> pool 8x8 (9..16 of 27) -> fire5..8: 10, 12, 14, 16 -> pool 9x9 (2..10 of 13)
-        -> fire9 11x11 -> 1x1 head + ReLU on 11x11, plus the head's constant ring, / 169.
-
-    Same arithmetic per output as the full network (0.128 instead of 0.733 GMAC per segment); results differ from
-    it only by float32 summation order inside the convolution kernels and in the final average."""
-
-    IN_LO, IN_HI = 92, 131            # rows/cols of the 224-pixel input the tile covers (patch at 100..123)
-
-    def __init__(self, model, border):
-        """model: SqueezeNet10 in eval mode on its device; border: (3,) tensor, the normalised pad value."""
-        self.model = model
-        dev = next(model.parameters()).device
-        feats = list(model.features)
-        with torch.no_grad():
-            x = border.to(dev, torch.float32).view(1, 3, 1, 1).expand(1, 3, 224, 224).contiguous()
-            maps = []                  # maps[i] = input of features[i] for the blank image
-            for layer in feats:
-                maps.append(x)
-                x = layer(x)
-            head = torch.relu(model.classifier[1](x))                 # (1, 2, 13, 13)
-        lo, hi = PAD, PAD + RESIZE - 1
-        size = 224
-        self.plan = []                 # per features[i] from the first Fire on: (kind, tile, paste offset, paste size)
-        # conv1 + ReLU + pool are run on the input tile directly
-        assert isinstance(feats[0], nn.Conv2d) and feats[0].padding == (0, 0)
-        out_size = maps[1].shape[-1]
-        lo, hi = _affected(lo, hi, 7, 2, 0, out_size)
-        need = (2 * lo, 2 * hi + 6)
-        assert need[0] >= self.IN_LO and need[1] <= self.IN_HI
-        assert (2 * lo - self.IN_LO) % 2 == 0
-        self.conv_skip = (2 * lo - self.IN_LO) // 2          # conv outputs the tile yields before the first affected one
-        conv_lo = lo - self.conv_skip
-        conv_hi = conv_lo + (self.IN_HI - self.IN_LO + 1 - 7) // 2
-        size = out_size
-        # the first pool works on conv rows [conv_lo, conv_hi] (all computed from the tile, background included)
-        out_size = maps[3].shape[-1]
-        plo, phi = _affected(lo, hi, 3, 2, 0, out_size)
-        assert 2 * plo >= conv_lo and 2 * phi + 2 <= conv_hi
-        self.pool1_slice = (2 * plo - conv_lo, 2 * phi + 2 - conv_lo + 1)
-        lo, hi, size = plo, phi, out_size
-        for i in range(3, len(feats)):
-            layer = feats[i]
-            in_map = maps[i]
-            if isinstance(layer, Fire):
-                a, b = max(lo - 1, 0), min(hi + 1, size - 1)
-                n0, n1 = a - 1, b + 1                       # inputs the 3x3 expand needs; may leave the map by one
-                c0, c1 = max(n0, 0), min(n1, size - 1)
-                tile = in_map[:, :, c0:c1 + 1, c0:c1 + 1].contiguous()
-                self.plan.append(("fire", layer, tile, lo - c0, hi - lo + 1, (c0 - n0, n1 - c1), (a - c0, b - a + 1)))
-                lo, hi = a, b
-            else:                                            # MaxPool2d(3, 2, ceil_mode=True)
-                out_size = maps[i + 1].shape[-1] if i + 1 < len(feats) else x.shape[-1]
-                a, b = _affected(lo, hi, 3, 2, 0, out_size)
-                n0, n1 = 2 * a, 2 * b + 2
-                assert n0 >= 0 and n1 <= size - 1            # no clipped window among the affected ones
-                tile = in_map[:, :, n0:n1 + 1, n0:n1 + 1].contiguous()
-                self.plan.append(("pool", layer, tile, lo - n0, hi - lo + 1, None, None))
-                lo, hi, size = a, b, out_size
-        self.final = (lo, hi, size)
-        self.final_bg = x[:, :, lo:hi + 1, lo:hi + 1].contiguous()          # the last Fire's output for the blank image, live square
-        ring = head.clone()
-        ring[:, :, lo:hi + 1, lo:hi + 1] = 0
-        self.ring_sum = ring.sum(dim=(2, 3))                 # (1, 2): the head's input-independent positions
-        self.n_pos = float(size * size)
-        # what the dropout head reads (swk_nhwc_head2_dropout_relu_mean): the last Fire's output for the blank image at every position,
-        # channels-last (its ring is dropped per segment and sample like the live square, so ring_sum cannot stand in for it), and the
-        # position of each live pixel in the full map, raster order
-        self.head_bg = x.permute(0, 2, 3, 1).reshape(size * size, x.shape[1]).contiguous()
-        self.head_pos = torch.tensor([r * size + c for r in range(lo, hi + 1) for c in range(lo, hi + 1)], dtype=torch.int32, device=dev)
-        # input-independent squeeze output of every Fire tile (with the map's own zero padding where a tile reaches
-        # the edge): the ring of the persistent squeeze buffers
-        self.sq_bg = []
-        with torch.no_grad():
-            for kind, layer, tile, off, n, pad, crop in self.plan:
-                if kind != "fire":
-                    self.sq_bg.append(None)
-                    continue
-                sq = layer.squeeze_activation(layer.squeeze(tile))
-                if pad[0] or pad[1]:
-                    sq = torch.nn.functional.pad(sq, (pad[0], pad[1], pad[0], pad[1]))
-                self.sq_bg.append(sq.contiguous())
-        self._cap = 0
-        self._buf = None
-        # channels-last on the GPU: what the library's convolution kernels read and write
-        self.memory_format = torch.channels_last if dev.type == "cuda" else torch.contiguous_format
-        if self.memory_format == torch.channels_last:
-            model.to(memory_format=torch.channels_last)
-        # The two cross-checks the tests keep: own_kernels = False routes every convolution through MIOpen (+ the placement kernel),
-        # winograd = False runs the 3x3 expands on the direct kernel (csrc/cnn_conv3x3.hip) instead of F(2x2, 3x3).
-        self.own_kernels = os.environ.get("SWK_OWN_CNN_KERNELS", "1") == "1"
-        self._head = None
-        self.winograd = True
-        # the Winograd expands with float32 products as six bf16 matrix-core products of split operands (csrc/cnn_wino3x3_bf16s.hip);
-        # False (or SWK_WINO_SPLIT_BF16=0) keeps them on the f32 matrix cores (csrc/cnn_wino3x3.hip)
-        self.wino_split_bf16 = os.environ.get("SWK_WINO_SPLIT_BF16", "1") == "1"
-        # max-pool + the squeeze behind it as one kernel (csrc/cnn_poolsq.hip): the pooled tensor never goes to memory
-        self.fuse_pool = os.environ.get("SWK_FUSE_POOL", "1") == "1"
-        self._w1 = None
-        self._wt3 = {}
-        self._ww3 = {}
-        self._ws3 = {}
-
-    def macs_per_segment(self):
-        """Multiply-accumulates of one forward per segment: (executed, useful).  "useful" prices every convolution output the next
-        layer reads as a direct convolution (the figure to compare networks and hardware with); "executed" is what the kernels
-        really multiply: the Winograd F(2x2, 3x3) kernel does 16 instead of 36 per 2 x 2 outputs (tiles padded to even sizes), the
-        MIOpen path (fused kernels off) runs the 1x1 expands over the whole squeeze tile.  The full 224 x 224 network does 0.7326 G."""
-        m = self.model
-        c1 = m.features[0]
-        side = (self.IN_HI - self.IN_LO + 1 - 7) // 2 + 1
-        executed = useful = side * side * c1.out_channels * c1.in_channels * 49
-        last_n = None
-        on_gpu = self.ring_sum.is_cuda and self.memory_format == torch.channels_last and self.own_kernels
-        for kind, layer, tile, off, n, pad, crop in self.plan:
-            if kind != "fire":
-                continue
-            t = tile.shape[2] + pad[0] + pad[1]
-            sq, e1, e3 = layer.squeeze, layer.expand1x1, layer.expand3x3
-            executed += n * n * sq.out_channels * sq.in_channels
-            e1_side = n if on_gpu else t      # the fused kernel only computes the outputs that depend on the segment
-            executed += e1_side * e1_side * e1.out_channels * e1.in_channels
-            wino = on_gpu and self.winograd and e3.out_channels == 4 * e3.in_channels and e3.in_channels in (16, 32, 48, 64)
-            if wino:
-                tiles = ((t - 2 + 1) // 2) ** 2
-                executed += tiles * 16 * e3.out_channels * e3.in_channels
-            else:
-                executed += (t - 2) ** 2 * e3.out_channels * e3.in_channels * 9
-            useful += n * n * sq.out_channels * sq.in_channels
-            useful += crop[1] ** 2 * (e1.out_channels * e1.in_channels + e3.out_channels * e3.in_channels * 9)
-            last_n = crop[1]
-        head = m.classifier[1]
-        executed += last_n * last_n * head.out_channels * head.in_channels
-        useful += last_n * last_n * head.out_channels * head.in_channels
-        return int(executed), int(useful)
-
-    def _buffers(self, batch):
-        """Persistent per-layer tiles for up to `batch` segments.  Their rings hold the background values and are
-        written once; a forward pass only overwrites the live centres."""
-        if batch <= self._cap:
-            return self._buf
-        bufs = []
-        for (kind, layer, tile, off, n, pad, crop), sq in zip(self.plan, self.sq_bg):
-            if kind == "fire":
-                bufs.append(sq.expand(batch, -1, -1, -1).contiguous(memory_format=self.memory_format))
-            else:
-                bufs.append(tile.expand(batch, -1, -1, -1).contiguous(memory_format=self.memory_format))
-        # live (ring-free) inputs of the Fires that follow a Fire, and of the head
-        live = []
-        for j, (kind, layer, tile, off, n, pad, crop) in enumerate(self.plan):
-            nxt = self.plan[j + 1][0] if j + 1 < len(self.plan) else "head"
-            if kind == "fire" and nxt != "pool":
-                # initialised with the blank image's values: the expand1x1 outputs on the ring of the square (squeeze values that do
-                # not depend on the segment) are never recomputed, a forward writes the expand1x1 centre and all of expand3x3
-                if nxt == "fire":
-                    _, _, ntile, noff, nn, _, _ = self.plan[j + 1]
-                    bg = ntile[:, :, noff:noff + nn, noff:noff + nn]
-                else:
-                    bg = self.final_bg
-                assert bg.shape[2] == crop[1] and bg.shape[1] == layer.expand1x1.out_channels + layer.expand3x3.out_channels
-                live.append(bg.expand(batch, -1, -1, -1).contiguous(memory_format=self.memory_format))
-            else:
-                live.append(None)
-        self._buf, self._cap = (bufs, live), batch
-        self.version = getattr(self, "version", 0) + 1          # new addresses: captured graphs of the old ones are void
-        return self._buf
-
-    def _gpu_path(self, tiles):
-        return tiles.is_cuda and self.memory_format == torch.channels_last and all(
-            kind != "fire" or not (pad[0] or pad[1]) for kind, _, _, _, _, pad, _ in self.plan)
-
-    def reserve(self, batch):
-        """Persistent tiles for `batch` segments and every per-layer operand tensor, made now (on the current stream)."""
-        self._buffers(batch)
-        if self.ring_sum.is_cuda:
-            self._aux_buffers(batch)
-            self._prepare_operands()
-
-    def _prepare_operands(self):
-        """The operand tensors the own kernels read (conv1's weights, the 3x3 expands' in the layout of the kernel each one runs on, the
-        head's), made on the current stream.  Made lazily by the first forward that needs one, they would be enqueued on whichever stream
-        that forward runs on: in a two-chain forward (SegmentClassifier._forward_two_streams) the side stream, whose copy the other chain
-        then may read before it has landed -- so reserve() makes them all before the chains fork."""
-        if not (self.own_kernels and self.ring_sum.is_cuda and self.memory_format == torch.channels_last):
-            return
-        self._conv1_operand()
-        for j, (kind, layer, tile, off, n, pad, crop) in enumerate(self.plan):
-            if kind == "fire":
-                self._w3_operand(j, layer.expand3x3)
-        self._head_operand()
-
-    def _conv1_operand(self):
-        if self._w1 is None:
-            self._w1 = self.model.features[0].weight.detach().contiguous(memory_format=torch.contiguous_format).clone()
-        return self._w1
-
-    def _head_operand(self):
-        if self._head is None:
-            head = self.model.classifier[1]
-            self._head = (head.weight.detach().reshape(head.out_channels, -1).contiguous(), head.bias.detach().contiguous(),
-                          self.ring_sum.reshape(-1).contiguous())
-        return self._head
-
-    def _w3_kind(self, conv):
-        """The kernel a 3x3 expand runs on: "bf16s" / "f32" (Winograd F(2x2, 3x3), split-bf16 or f32 products) or "direct"."""
-        cin, cout = conv.in_channels, conv.out_channels
-        if self.winograd and cout == 4 * cin and cin in (16, 32, 48, 64):
-            # (16 -> 64 measured slower on the split kernel, 77 / 101 against 73 / 93 us per 4,096 rows: it stays on the f32 one)
-            return "bf16s" if self.wino_split_bf16 and cin != 16 else "f32"
-        return "direct"
-
-    def _w3_operand(self, j, conv, kind=None):
-        """The weights of the 3x3 expand of plan entry j in the layout of the kernel `kind` runs on, made once per layer."""
-        from . import _lib
-        kind = kind or self._w3_kind(conv)
-        cache = {"bf16s": self._ws3, "f32": self._ww3, "direct": self._wt3}[kind]
-        w = cache.get(j)
-        if w is not None:
-            return w
-        cin, cout = conv.in_channels, conv.out_channels
-        dev = conv.weight.device
-        if kind == "direct":          # [co][ci][3][3] -> [tap][ci][co]
-            w = conv.weight.detach().permute(2, 3, 1, 0).contiguous(memory_format=torch.contiguous_format)
-        else:                         # G g G^T in the kernel's operand layout (host code of the library)
-            lib = _lib.load()
-            wc = conv.weight.detach().to("cpu", torch.float32).contiguous()
-            ncol = 32 * (-(-cout // 32))
-            if kind == "bf16s":
-                out = torch.empty(3 * 16 * cin * ncol, dtype=torch.int16)          # bf16 bit patterns
-                if lib.swk_winograd_f2x2_3x3_weights_bf16s(wc.data_ptr(), cout, cin, out.data_ptr()):
-                    raise RuntimeError("swk_winograd_f2x2_3x3_weights_bf16s failed")
-            else:
-                out = torch.empty(16 * cin * ncol, dtype=torch.float32)
-                if lib.swk_winograd_f2x2_3x3_weights(wc.data_ptr(), cout, cin, out.data_ptr()):
-                    raise RuntimeError("swk_winograd_f2x2_3x3_weights failed")
-            w = out.to(dev)
-        cache[j] = w
-        return w
-
-    @torch.no_grad()
-    def __call__(self, tiles, row0=0, dropout=None):
-        """tiles: (B, 3, 40, 40) float32 = rows/cols 92..131 of the normalised 224x224 input.  row0: first row of the persistent
-        per-layer tiles this forward works in (two forwards on disjoint row ranges may run side by side on two streams).
-        dropout = (keys, seed, samples): instead of the eval-mode scores, (B, samples, 2) scores under the reference's live Dropout(0.5)
-        (keys: (B,) int64 device tensor of the segments' uint64 keys); the library's HIP kernel only."""
-        if self._gpu_path(tiles):
-            with torch.cuda.device(tiles.device):            # the glue kernels go to this device's current stream
-                return self._forward_hip_glue(tiles, row0, dropout)
-        if dropout is not None:
-            raise RuntimeError("dropout sampling runs on the library's HIP head kernel: it needs the GPU path")
-        if row0:
-            raise ValueError("row0 is a feature of the GPU path")
-        m = self.model
-        conv2d = torch.nn.functional.conv2d
-        k = tiles.shape[0]
-        bufs, live = self._buffers(k)
-        x = torch.relu(m.features[0](tiles.contiguous(memory_format=self.memory_format)))
-        a, b = self.pool1_slice
-        x = m.features[2](x[:, :, a:b, a:b])
-        for j, (kind, layer, tile, off, n, pad, crop) in enumerate(self.plan):
-            if kind == "pool":
-                x = layer(bufs[j][:k])                       # centre written by the Fire before it
-                continue
-            sq = bufs[j][:k]
-            o = off + pad[0]
-            torch.clamp_min(layer.squeeze(x), 0, out=sq[:, :, o:o + n, o:o + n])
-            e3 = conv2d(sq, layer.expand3x3.weight, layer.expand3x3.bias)            # valid: the halo is in the tile
-            e1 = conv2d(sq, layer.expand1x1.weight, layer.expand1x1.bias)
-            c, cn = crop
-            c1 = layer.expand1x1.out_channels
-            if live[j] is not None:
-                dest = live[j][:k]
-            else:                                            # straight into the centre of the pool tile
-                _, _, _, poff, pn, _, _ = self.plan[j + 1]
-                assert pn == cn
-                dest = bufs[j + 1][:k, :, poff:poff + pn, poff:poff + pn]
-            cp = c + pad[0]
-            torch.clamp_min(e1[:, :, cp:cp + cn, cp:cp + cn], 0, out=dest[:, :c1])
-            torch.clamp_min(e3, 0, out=dest[:, c1:])
-            x = dest
-        s = torch.relu(m.classifier[1](x)).sum(dim=(2, 3))
-        return (s + self.ring_sum) / self.n_pos
-
-    def _forward_hip_glue(self, tiles, row0=0, dropout=None):
-        """The same forward on the GPU with the convolutions alone left to MIOpen: bias + ReLU + placement into the
-        next tile is one HIP kernel per convolution output (swk_nhwc_bias_relu_place), max-pooling another
-        (swk_nhwc_maxpool3s2), both on PyTorch's current stream.  Same float32 operations per element as above."""
-        from . import _lib
-        lib = _lib.load()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(tiles.device).cuda_stream)
-        m = self.model
-        conv2d = torch.nn.functional.conv2d
-        k = tiles.shape[0]
-        bufs, live = self._buffers(row0 + k)
-        rows = slice(row0, row0 + k)
-        cl = torch.channels_last
-
-        def nhwc(t):
-            return t if t.is_contiguous(memory_format=cl) else t.contiguous(memory_format=cl)
-
-        def place(e, bias, dest, crop, size, off, c_off):
-            e = nhwc(e)
-            rc = lib.swk_nhwc_bias_relu_place(stream, e.data_ptr(), k, e.shape[2], e.shape[3], e.shape[1], crop, crop, size, size,
-                                              bias.data_ptr(), dest.data_ptr(), dest.shape[2], dest.shape[3], dest.shape[1],
-                                              off, off, c_off)
-            if rc:
-                raise RuntimeError("swk_nhwc_bias_relu_place failed (%d)" % rc)
-
-        def conv1x1(src, crop, size, conv, dest, off, c_off):
-            src = nhwc(src)
-            wgt = conv.weight.reshape(conv.out_channels, conv.in_channels)       # 1 x 1 kernel: same memory in both layouts
-            rc = lib.swk_nhwc_conv1x1_bias_relu_place(stream, src.data_ptr(), k, src.shape[2], src.shape[3], src.shape[1], crop, crop,
-                                                      size, size, wgt.data_ptr(), conv.bias.data_ptr(), conv.out_channels,
-                                                      dest.data_ptr(), dest.shape[2], dest.shape[3], dest.shape[1], off, off, c_off)
-            if rc:
-                raise RuntimeError("swk_nhwc_conv1x1_bias_relu_place failed (%d)" % rc)
-
-        def conv3x3(src, j, conv, dest, off, c_off):
-            src = nhwc(src)
-            cin, cout = conv.in_channels, conv.out_channels
-            kind = self._w3_kind(conv)
-            if kind != "direct" and k * src.shape[2] * src.shape[2] * cin * 4 < (1 << 32):
-                ww = self._w3_operand(j, conv, kind)
-                fn = "swk_nhwc_conv3x3_winograd_bf16s_bias_relu_place" if kind == "bf16s" else "swk_nhwc_conv3x3_winograd_bias_relu_place"
-                rc = getattr(lib, fn)(stream, src.data_ptr(), k, src.shape[2], cin, ww.data_ptr(), conv.bias.data_ptr(), cout,
-                                      dest.data_ptr(), dest.shape[2], dest.shape[3], dest.shape[1], off, off, c_off)
-                if rc:
-                    raise RuntimeError("%s failed (%d)" % (fn, rc))
-                return
-            wt = self._w3_operand(j, conv, "direct")
-            assert src.shape[2] == src.shape[3]
-            rc = lib.swk_nhwc_conv3x3_bias_relu_place(stream, src.data_ptr(), k, src.shape[2], src.shape[1], wt.data_ptr(),
-                                                      conv.bias.data_ptr(), conv.out_channels, dest.data_ptr(), dest.shape[2],
-                                                      dest.shape[3], dest.shape[1], off, off, c_off)
-            if rc:
-                raise RuntimeError("swk_nhwc_conv3x3_bias_relu_place failed (%d)" % rc)
-
-        def pool(src, dst):
-            rc = lib.swk_nhwc_maxpool3s2(stream, src.data_ptr(), k, src.shape[2], src.shape[3], src.shape[1], dst.data_ptr())
-            if rc:
-                raise RuntimeError("swk_nhwc_maxpool3s2 failed (%d)" % rc)
-
-        def pool_squeeze(src, conv, dest, off, ring=None, live=(0, 0)):
-            # ring: the tile whose ring every tile of src shares (written once, _buffers): only the live square is read per segment
-            wgt = conv.weight.reshape(conv.out_channels, conv.in_channels)
-            rc = lib.swk_nhwc_maxpool3s2_conv1x1_bias_relu_place(stream, src.data_ptr(), k, src.shape[2], src.shape[1], wgt.data_ptr(),
-                                                                 conv.bias.data_ptr(), conv.out_channels, dest.data_ptr(), dest.shape[2],
-                                                                 dest.shape[3], dest.shape[1], off, off,
-                                                                 None if ring is None else ring.data_ptr(), live[0], live[1])
-            if rc:
-                raise RuntimeError("swk_nhwc_maxpool3s2_conv1x1_bias_relu_place failed (%d)" % rc)
-
-        aux = self._aux_buffers(row0 + k)
-        conv1 = m.features[0]
-        a, b = self.pool1_slice
-        c1buf = aux["conv1"][rows]
-        side = tiles.shape[2]
-        if self.own_kernels and conv1.out_channels == 96 and side % 2 == 0 and 2 * (b - 1) + 8 <= side:
-            # conv1 + bias + ReLU on the rows the first pool reads, one kernel (csrc/cnn_conv1.hip)
-            w1 = self._conv1_operand()
-            xin = nhwc(tiles)
-            rc = lib.swk_nhwc_conv7x7s2_bias_relu(stream, xin.data_ptr(), k, side, a, b - a, w1.data_ptr(), conv1.bias.data_ptr(),
-                                                  conv1.out_channels, c1buf.data_ptr())
-            if rc:
-                raise RuntimeError("swk_nhwc_conv7x7s2_bias_relu failed (%d)" % rc)
-        else:
-            e = conv2d(nhwc(tiles), conv1.weight, None, stride=conv1.stride)
-            place(e, conv1.bias, c1buf, a, b - a, 0, 0)
-        fuse = self.fuse_pool and self.own_kernels
-        to_pool = c1buf               # a tensor whose max-pool the next squeeze reads (fused into it), or None
-        pool_ring, pool_live = None, (0, 0)        # conv1's output has no ring; the pool tiles behind fire4 and fire8 do
-        x = aux["pool_in"][rows]
-        if not fuse:
-            pool(c1buf, x)
-        pi = 0
-        for j, (kind, layer, tile, off, n, pad, crop) in enumerate(self.plan):
-            if kind == "pool":
-                x = aux["pool_out"][pi][rows]
-                if fuse:
-                    to_pool, pool_ring, pool_live = bufs[j][rows], bufs[j][0:1], (off, n)
-                else:
-                    pool(bufs[j][rows], x)
-                pi += 1
-                continue
-            sq = bufs[j][rows]
-            c, cn = crop
-            c1 = layer.expand1x1.out_channels
-            if live[j] is not None:
-                dest, doff = live[j][rows], 0
-            else:
-                dest, doff = bufs[j + 1][rows], self.plan[j + 1][3]
-            if self.own_kernels:
-                # squeeze and expand1x1 as ONE kernel each on the f32 matrix cores: convolution + bias + ReLU + placement
-                # (csrc/cnn_conv1x1.hip)
-                if fuse and to_pool is not None:
-                    assert (to_pool.shape[2] - 3) // 2 + 1 == n
-                    pool_squeeze(to_pool, layer.squeeze, sq, off, pool_ring, pool_live)
-                    to_pool = None
-                else:
-                    conv1x1(x, 0, n, layer.squeeze, sq, off, 0)
-                # expand1x1 only where the squeeze output depends on the segment (n x n inside the cn x cn square: the ring keeps the
-                # blank image's values the buffers were created with)
-                conv1x1(sq, off, n, layer.expand1x1, dest, doff + off - c, 0)
-            else:
-                place(conv2d(x, layer.squeeze.weight, None), layer.squeeze.bias, sq, 0, n, off, 0)
-                e1 = conv2d(sq, layer.expand1x1.weight, None)
-                place(e1, layer.expand1x1.bias, dest, c, cn, doff, 0)
-            if self.own_kernels:
-                # the 3x3 expand (valid convolution over the squeeze tile) likewise (csrc/cnn_conv3x3.hip)
-                conv3x3(sq, j, layer.expand3x3, dest, doff, c1)
-            else:
-                place(conv2d(sq, layer.expand3x3.weight, None), layer.expand3x3.bias, dest, 0, cn, doff, c1)
-            x = dest
-        # the 512 -> 2 head (1 x 1 convolution + ReLU + spatial sum) as a plain matrix product over the channels-last pixels: no
-        # convolution library on this path, hence no kernel search per batch shape
-        head = m.classifier[1]
-        if dropout is not None:
-            if not (self.own_kernels and head.out_channels == 2 and x.shape[1] in (256, 512, 768, 1024)):
-                raise RuntimeError("dropout sampling runs on the library's HIP head kernel (own kernels, a two-class head)")
-            hw, hb, _ = self._head_operand()
-            keys, seed, samples = dropout
-            return _dropout_head(x, self.head_pos, self.head_bg, int(self.n_pos), hw, hb, keys, seed, samples)
-        if self.own_kernels and head.out_channels == 2 and x.shape[1] in (256, 512, 768, 1024) and x.is_contiguous(memory_format=cl):
-            # the head as one kernel with a fixed summation order (csrc/cnn_aux.hip): scores that do not depend on the batch's row count
-            hw, hb, ring = self._head_operand()
-            out = torch.empty((k, 2), dtype=torch.float32, device=x.device)
-            rc = lib.swk_nhwc_head2_relu_mean(stream, x.data_ptr(), k, x.shape[2] * x.shape[3], x.shape[1], hw.data_ptr(), hb.data_ptr(),
-                                              ring.data_ptr(), self.n_pos, out.data_ptr())
-            if rc:
-                raise RuntimeError("swk_nhwc_head2_relu_mean failed (%d)" % rc)
-            return out
-        px = x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])                       # (B * live positions, 512): a view of the NHWC memory
-        s = torch.relu(torch.nn.functional.linear(px, head.weight.view(head.out_channels, -1), head.bias))
-        s = s.view(k, -1, head.out_channels).sum(dim=1)
-        return (s + self.ring_sum) / self.n_pos
-
-    def _aux_buffers(self, batch):
-        if getattr(self, "_aux_cap", 0) >= batch:
-            return self._aux
-        dev = self.ring_sum.device
-        cl = torch.channels_last
-
-        def buf(c, h):
-            return torch.empty((batch, c, h, h), dtype=torch.float32, device=dev).contiguous(memory_format=cl)
-
-        a, b = self.pool1_slice
-        conv1_c = self.model.features[0].out_channels
-        aux = {"conv1": buf(conv1_c, b - a), "pool_in": buf(conv1_c, (b - a - 3) // 2 + 1), "pool_out": []}
-        for kind, layer, tile, off, n, pad, crop in self.plan:
-            if kind == "pool":
-                aux["pool_out"].append(buf(tile.shape[1], (tile.shape[2] - 3) // 2 + 1))
-        self._aux, self._aux_cap = aux, batch
-        self.version = getattr(self, "version", 0) + 1
-        return aux
+# the network and its cropped evaluation live in squeezenet.py; their names stay importable from here
+from .squeezenet import IMAGENET_MEAN, IMAGENET_STD, PAD, RESIZE, CroppedSqueezeNet10, Fire, Launcher, SqueezeNet10, _affected  # noqa: F401
 
 
 def setup_model(num_classes):
@@ -673,14 +139,17 @@ class SegmentClassifier:
         return min(self.batch_size, -(-k // 512) * 512)
 
     def _forward(self, x):
+        net = self.cropped
+        if net is not None and net.own_kernels:
+            if self._split_rows and x.shape[0] >= self._split_rows and net._gpu_path(x):
+                return self._forward_two_streams(x)
+            return net(x)
         # (nothing of the default GPU path is a MIOpen convolution: the setting only matters for the full network and the cross-check)
-        if self._cudnn_benchmark and (self.cropped is None or not self.cropped.own_kernels):
-            with torch.backends.cudnn.flags(enabled=True, benchmark=True):
-                return self.cropped(x) if self.cropped is not None else self.model(x)
-        if (self._split_rows and x.shape[0] >= self._split_rows and self.cropped is not None and self.cropped.own_kernels
-                and self.cropped._gpu_path(x)):
-            return self._forward_two_streams(x)
-        return self.cropped(x) if self.cropped is not None else self.model(x)
+        forward = self.model if net is None else net
+        if not self._cudnn_benchmark:
+            return forward(x)
+        with torch.backends.cudnn.flags(enabled=True, benchmark=True):
+            return forward(x)
 
     def _full_head_operand(self, n_pos):
         """What the dropout head reads on the full network: the head's weights and bias, and every position as a live one."""
@@ -712,7 +181,7 @@ class SegmentClassifier:
             f = f.contiguous(memory_format=torch.channels_last)
             n_pos = f.shape[2] * f.shape[3]
             hw, hb, pos = self._full_head_operand(n_pos)
-            return _dropout_head(f, pos, None, n_pos, hw, hb, keys, int(seed), samples)
+            return Launcher(self.device, f.shape[0]).dropout_head(f, pos, None, n_pos, hw, hb, keys, int(seed), samples)
 
     def _keys_tensor(self, keys, k):
         if not (isinstance(keys, np.ndarray) and keys.dtype in (np.uint64, np.int64)):
@@ -783,7 +252,7 @@ class SegmentClassifier:
         """A window's worth of segments (<= 512 rows) is some thirty kernels of a few microseconds each: launched one by one from
         Python they cost more host time than GPU time.  The forward on a persistent input slot is captured once per (slot, rows) as a
         HIP graph and replayed with one launch.  Anything that goes wrong while capturing switches this off for the classifier."""
-        key = (x.data_ptr(), int(x.shape[0]), getattr(self.cropped, "version", 0))
+        key = (x.data_ptr(), int(x.shape[0]), self.cropped.version)
         entry = self._graphs.get(key)
         if entry is None:
             try:
@@ -939,22 +408,9 @@ class SegmentClassifier:
     def classify_frames(self, frames):
         """__call__ for many frames with ONE scoring batch: every frame's segments replaced by the kept ones,
         relabelled 1..k per frame (:41-42)."""
-        segs = [s for fr in frames for s in fr.segments]
-        if not segs:
-            return
-        pred = self._window_predictions(segs)                 # segments of one segment_windows / segment_queue call: device-resident
-        if pred is None:
-            pred = self._predict_images(segs)
-        i = 0
-        for fr in frames:
-            kept = []
-            for s in fr.segments:
-                if pred[i] == 1:
-                    kept.append(s)
-                i += 1
-            for j, s in enumerate(kept):
-                s.label = j + 1
-            fr.segments = kept
+        if any(fr.segments for fr in frames):
+            for fr, kept in zip(frames, self._keep_and_relabel([fr.segments for fr in frames])):
+                fr.segments = kept
 
     def _window_predictions(self, segments):
         """Segments that FrameQueue.segment_queue made carry their window (data_structures.WindowBatch) and their index in it:
@@ -975,12 +431,20 @@ class SegmentClassifier:
     def __call__(self, segments):
         """:26-44: keep segments whose argmax is class 1 (ties / all-zero scores give 0 and are
         dropped, as torch.max does), relabel the kept ones 1..k."""
-        if not segments:
-            return []
-        pred = self._window_predictions(segments)
+        return self._keep_and_relabel([segments])[0] if segments else []
+
+    def _keep_and_relabel(self, groups):
+        """The segments of every group (a frame's) that the classifier keeps, relabelled 1..k per group; all groups are scored as ONE
+        batch."""
+        segs = [s for g in groups for s in g]
+        pred = self._window_predictions(segs)                 # segments of one segment_windows / segment_queue call: device-resident
         if pred is None:
-            pred = self._predict_images(segments)
-        kept = [s for s, y in zip(segments, pred) if y == 1]
-        for i, s in enumerate(kept):
-            s.label = i + 1
-        return kept
+            pred = self._predict_images(segs)
+        out, i = [], 0
+        for g in groups:
+            kept = [s for s, y in zip(g, pred[i:i + len(g)]) if y == 1]
+            i += len(g)
+            for j, s in enumerate(kept):
+                s.label = j + 1
+            out.append(kept)
+        return out

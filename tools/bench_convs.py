@@ -1,6 +1,7 @@
 """Per-layer times of the cropped classifier's own kernels inside a real forward (batch 4096 by default): every
-swk_nhwc_* call of CroppedSqueezeNet10._forward_hip_glue is bracketed by events on PyTorch's stream.  Prints one row per
-call with its multiply-accumulate rate and the activation bytes it has to move, and a JSON summary as the last line.
+swk_nhwc_* call of CroppedSqueezeNet10._forward_own (swiftwatcher_amd/squeezenet.py) is bracketed by events on PyTorch's stream:
+its Launcher looks the library up through _lib.load() at every forward, which this tool substitutes with a timing proxy.  Prints one
+row per call with its multiply-accumulate rate and the activation bytes it has to move, and a JSON summary as the last line.
 
     python3 tools/bench_convs.py [batch] [reps] [1x1 ring knob] [split-bf16 Winograd layout knob: 0 default, 1 present, 2 shared-filter]
 """
