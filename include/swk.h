@@ -220,6 +220,55 @@ typedef struct swk_yuv420 {
 int32_t swk_yuv420_to_bgr(swk_ctx *ctx, const swk_yuv420 *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
                           uint8_t *bgr, int32_t bgr_mem);
 
+/* ---- decoder hand-over, every format: planar / semiplanar / mono YUV, 8..16 bits, limited or full range -> BGR ----
+ * What cameras and decoders deliver besides 8-bit 4:2:0: full-range 4:2:0 (yuvj420p), 10-bit (P010 surfaces, C420p10
+ * files), 4:2:2 and 4:4:4, 4:1:1, luma-only thermal video.  One definition in exact integers (PARITY UNPINNED, like
+ * swk_yuv420_to_bgr: cv2.VideoCapture hands BGR over whatever the file holds, and this restates the BT.601 matrix it
+ * applies at every resolution).  bits = d in 8..16, k = d - 8; chroma is subsampled by shifts sx in {0, 1, 2} and sy in
+ * {0, 1} (4:4:4 = (0,0), 4:2:2 = (1,0), 4:2:0 = (1,1), 4:1:1 = (2,0)); the chroma planes hold ceil(H / 2^sy) x
+ * ceil(W / 2^sx) samples and pixel (r, c) uses chroma sample (r >> sy, c >> sx), not interpolated.  Mono behaves as
+ * U = V = 128 << k.
+ *   limited range: Yt = max(Y - (16 << k), 0); (CY, CUB, CUG, CVG, CVR) = (1220542, 2116026, -409993, -852492, 1673527)
+ *   full range:    Yt = Y;                     (CY, CUB, CUG, CVG, CVR) = (1048576, 1858077, -360853, -748826, 1470104)
+ *   uu = U - (128 << k);  vv = V - (128 << k);  h = 1 << (19 + k);  s = 20 + k
+ *   B = sat8((CY * Yt + CUB * uu + h) >> s)
+ *   G = sat8((CY * Yt + CUG * uu + CVG * vv + h) >> s)
+ *   R = sat8((CY * Yt + CVR * vv + h) >> s)
+ * with an arithmetic shift and exact integers (64-bit for d > 8).  The full-range constants are floor(x * 2^20 + 1/2) of
+ * 2 (1 - Kb), -2 Kb (1 - Kb) / Kg, -2 Kr (1 - Kr) / Kg, 2 (1 - Kr) with Kr = 0.299, Kb = 0.114, Kg = 0.587.  Samples are
+ * taken as stored: a value above 2^d - 1 is not masked.  At d = 8, limited range, (sx, sy) = (1, 1) this is
+ * swk_yuv420_to_bgr bit for bit; a d-bit picture whose samples are 8-bit samples << k converts to the 8-bit picture's bytes. */
+enum { SWK_YUV_PLANAR = 0,       /* three planes: Y, U, V (= SWK_YUV_I420 at (1,1)) */
+       SWK_YUV_SEMIPLANAR = 1,   /* two planes: Y, then rows of interleaved (U, V) samples: NV12, NV16, NV24, P010, P016, P210 */
+       SWK_YUV_MONO = 2 };       /* Y only; u and v are ignored and may be null */
+
+/* swk_yuv420 with the format spelled out.  Samples are bytes at bits = 8 and little-endian 16-bit words above; all strides
+ * stay in bytes.  Pixel (r, c) of frame f has its luma sample at y + f * y_frame_stride + r * y_row_stride + c * B (B bytes
+ * per sample) and its chroma at u (and v) + f * c_frame_stride + (r >> sy) * c_row_stride + (c >> sx) * B (planar), at
+ * u + ... + (c >> sx) * 2 B (U) and + B (V) for semiplanar (v is not read). */
+typedef struct swk_yuv {
+    const uint8_t *y, *u, *v;
+    int32_t mem;            /* SWK_MEM_HOST / SWK_MEM_DEVICE: where all planes live */
+    int32_t layout;         /* SWK_YUV_PLANAR / SWK_YUV_SEMIPLANAR / SWK_YUV_MONO */
+    int32_t H, W;           /* frame size in pixels (each 1..32768, odd sizes allowed) */
+    int64_t y_row_stride, y_frame_stride;
+    int64_t c_row_stride, c_frame_stride;
+    int32_t sx, sy;         /* chroma shifts: 0..2 and 0..1 (ignored for mono) */
+    int32_t bits;           /* 8..16 */
+    int32_t msb_aligned;    /* bits > 8: the sample is word >> (16 - bits), as P010 / P016 surfaces store it; planar
+                               high-bit-depth files are LSB-aligned (0) */
+    int32_t full_range;     /* 0 = limited (16..235 << k), 1 = full */
+    int32_t reserved_;
+} swk_yuv;
+
+/* As swk_yuv420_to_bgr: the rectangle [y0, y0 + Hr) x [x0, x0 + Wr) of every frame as dense BGR [count][Hr][Wr][3] in host or
+ * device memory; host or device planes; of a host source only the samples that cover the rectangle (grown to multiples of
+ * 2^sx and 2^sy) are copied up; the device result is what swk_input.frames takes.  SWK_ERR_ARG: bits outside 8..16, sx > 2 or
+ * sy > 1, an unknown layout, a null plane that the layout needs, a rectangle outside the frame, count < 1, a row stride below
+ * the row's bytes, an odd stride or plane address with 2-byte samples. */
+int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
+                       uint8_t *bgr, int32_t bgr_mem);
+
 /* ---- stage-level entry points (host buffers; used by the parity tests and by the
  *      image_filtering.* drop-in functions) ------------------------------------- */
 /* convert_grayscale (image_filtering.py:188-196): [count][H][W][3] -> [count][H][W] */

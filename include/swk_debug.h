@@ -17,7 +17,7 @@ extern "C" {
 /* ---- measurement hooks -----------------------------------------------------------
  * With profiling on, every kernel launch of swk_batch_run is bracketed by HIP events on
  * the context's stream; swk_prof_get returns accumulated device time and launch count per
- * kernel family since the last swk_prof_reset (swk_yuv420_to_bgr's kernel counts as SWK_K_GRAY, the colour conversions).  Family ids: */
+ * kernel family since the last swk_prof_reset (swk_yuv420_to_bgr's and swk_yuv_to_bgr's kernels count as SWK_K_GRAY, the colour conversions).  Family ids: */
 enum {
     SWK_K_GRAY = 0, SWK_K_IALM_STATS = 1, SWK_K_IALM_PASS = 2, SWK_K_IALM_SMALL = 3,
     SWK_K_FILTER = 4, SWK_K_CCL = 5, SWK_K_PROPS = 6, SWK_K_COPY = 7, SWK_K_COUNT = 8

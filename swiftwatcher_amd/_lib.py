@@ -18,6 +18,7 @@ STAGES = ("gray", "rpca", "bilateral", "thresh", "opened", "labels")
 ORDER_RASTER, ORDER_BLOCK2X2 = 0, 1
 GRAY_Q14, GRAY_Q15 = 0, 1
 YUV_I420, YUV_NV12 = 0, 1
+YUV_PLANAR, YUV_SEMIPLANAR, YUV_MONO = 0, 1, 2
 K_GRAY, K_IALM_STATS, K_IALM_PASS, K_IALM_SMALL, K_FILTER, K_CCL, K_PROPS, K_COPY = range(8)
 KERNEL_FAMILIES = ["gray", "ialm_stats", "ialm_pass", "ialm_small", "filter", "ccl", "props", "copy"]
 
@@ -77,6 +78,11 @@ class Yuv420(ctypes.Structure):
                 ("c_row_stride", ctypes.c_int64), ("c_frame_stride", ctypes.c_int64)]
 
 
+class Yuv(ctypes.Structure):
+    _fields_ = Yuv420._fields_ + [("sx", ctypes.c_int32), ("sy", ctypes.c_int32), ("bits", ctypes.c_int32),
+                                  ("msb_aligned", ctypes.c_int32), ("full_range", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -90,6 +96,7 @@ _SIGS = {
     "swk_batch_run": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Params), ctypes.POINTER(Output)]),
     "swk_batch_run_groups": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.c_int32, ctypes.POINTER(Params), ctypes.POINTER(Output)]),
     "swk_yuv420_to_bgr": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv420)] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int32]),
+    "swk_yuv_to_bgr": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv)] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int32]),
     "swk_bgr2gray": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "swk_ialm": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_rpca_epilogue": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -615,6 +622,76 @@ class Context:
             out = np.empty(shape, np.uint8)
             optr, omem = _ptr(out), MEM_HOST
         self._check(self._lib.swk_yuv420_to_bgr(self._h, ctypes.byref(src), count, int(x0), int(y0), int(Hr), int(Wr), optr, omem))
+        return out[0] if single else out
+
+    def yuv_to_bgr(self, y, u=None, v=None, *, subsampling=(1, 1), bits=8, msb_aligned=False, full_range=False, rect=None, device_out=False):
+        """swk_yuv_to_bgr: planar, semiplanar or mono YUV frames of 8..16 bits, limited or full range -> BGR (the definition in
+        include/swk.h).  y: (count, H, W) or (H, W), uint8 at bits = 8 and uint16 above.  subsampling = (sx, sy), the chroma shifts:
+        (0, 0) 4:4:4, (1, 0) 4:2:2, (1, 1) 4:2:0, (2, 0) 4:1:1; a chroma plane is (count, ceil(H / 2^sy), ceil(W / 2^sx)).  Planar: u
+        and v.  Semiplanar (NV12, NV16, NV24, P010, P016, P210): v=None and u the interleaved plane, (count, ch, cw, 2) or
+        (count, ch, 2 cw).  Mono: u=None.  msb_aligned: 16-bit words that hold the sample in their upper bits (P010).  All numpy
+        arrays, or all torch tensors on this context's GPU (read in place); contiguous along a row, any row pitch and frame stride.
+        rect: (x0, y0, Wr, Hr) inside the frame, None = the whole frame.  Returns BGR (count, Hr, Wr, 3) (no count axis for a 2-D y):
+        a numpy array, or with device_out=True a torch uint8 tensor on the GPU -- what batch_run / batch_run_groups take as frames."""
+        bits, (sx, sy) = int(bits), (int(subsampling[0]), int(subsampling[1]))
+        B = 2 if bits > 8 else 1
+        np_dtype = np.uint16 if B == 2 else np.uint8
+        on_device = hasattr(y, "data_ptr") and getattr(y, "is_cuda", False)
+        if u is None and v is not None:
+            raise ValueError("v without u")
+        planes = [y] + ([u] if u is not None else []) + ([v] if v is not None else [])
+        want = ("torch.uint16" if B == 2 else "torch.uint8") if on_device else np.dtype(np_dtype).name
+        if not on_device:
+            planes = [p if isinstance(p, np.ndarray) and p.dtype == np_dtype and p.ndim and p.strides[-1] == B else np.ascontiguousarray(p, np_dtype)
+                      for p in planes]
+        if any((hasattr(p, "data_ptr") and getattr(p, "is_cuda", False)) != on_device or str(p.dtype) != want for p in planes):
+            raise ValueError("the planes must be %s, all numpy arrays or all tensors on the context's GPU" % np.dtype(np_dtype).name)
+        single = len(planes[0].shape) == 2
+        if single:
+            planes = [p[None] for p in planes]
+
+        def geometry(p):          # shape, strides in BYTES, address
+            if on_device:
+                return tuple(p.shape), tuple(int(x) * B for x in p.stride()), p.data_ptr()
+            return tuple(p.shape), tuple(p.strides), p.ctypes.data
+        yshape, ystr, yptr = geometry(planes[0])
+        if len(yshape) != 3 or ystr[2] != B:
+            raise ValueError("y must be (count, H, W), contiguous along a row")
+        count, H, W = yshape
+        uptr = vptr = None
+        cstr = (0, 0)
+        if u is None:
+            layout = YUV_MONO
+        else:
+            if not (0 <= sx <= 2 and 0 <= sy <= 1):
+                ch = cw = -1                                         # (the library refuses the shifts; no shape can be checked)
+            else:
+                ch, cw = ((H - 1) >> sy) + 1, ((W - 1) >> sx) + 1
+            cshape, cstr, uptr = geometry(planes[1])
+            if v is not None:
+                vshape, vstr, vptr = geometry(planes[2])
+                if ch >= 0 and (cshape != (count, ch, cw) or vshape != cshape or cstr[2] != B or vstr != cstr):
+                    raise ValueError("u and v must be (count, %d, %d) with equal strides, contiguous along a row" % (ch, cw))
+                layout = YUV_PLANAR
+            else:
+                ok = (len(cshape) == 4 and cshape == (count, ch, cw, 2) and cstr[3] == B and cstr[2] == 2 * B) or \
+                     (len(cshape) == 3 and cshape == (count, ch, 2 * cw) and cstr[2] == B)
+                if ch >= 0 and not ok:
+                    raise ValueError("the interleaved chroma plane must be (count, %d, %d, 2) or (count, %d, %d)" % (ch, cw, ch, 2 * cw))
+                layout = YUV_SEMIPLANAR
+        x0, y0, Wr, Hr = rect if rect is not None else (0, 0, W, H)
+        src = Yuv(y=yptr, u=uptr, v=vptr, mem=MEM_DEVICE if on_device else MEM_HOST, layout=layout, H=H, W=W,
+                  y_row_stride=ystr[1], y_frame_stride=ystr[0], c_row_stride=cstr[1], c_frame_stride=cstr[0],
+                  sx=sx, sy=sy, bits=bits, msb_aligned=int(bool(msb_aligned)), full_range=int(bool(full_range)))
+        shape = (count, int(Hr), int(Wr), 3) if Hr > 0 and Wr > 0 and count > 0 else (1, 1, 1, 3)          # (the library refuses those)
+        if device_out:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device="cuda:%d" % self.device)
+            optr, omem = ctypes.c_void_p(out.data_ptr()), MEM_DEVICE
+        else:
+            out = np.empty(shape, np.uint8)
+            optr, omem = _ptr(out), MEM_HOST
+        self._check(self._lib.swk_yuv_to_bgr(self._h, ctypes.byref(src), count, int(x0), int(y0), int(Hr), int(Wr), optr, omem))
         return out[0] if single else out
 
     # ---- stage-level entry points ----

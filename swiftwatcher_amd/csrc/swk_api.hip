@@ -1395,6 +1395,81 @@ int32_t swk_yuv420_to_bgr(swk_ctx *ctx, const swk_yuv420 *src, int32_t count, in
     return sync(ctx);
 }
 
+int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr, uint8_t *bgr,
+                       int32_t bgr_mem)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!src || !bgr) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (src->layout != SWK_YUV_PLANAR && src->layout != SWK_YUV_SEMIPLANAR && src->layout != SWK_YUV_MONO)
+        return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_PLANAR, SWK_YUV_SEMIPLANAR or SWK_YUV_MONO)");
+    const bool semi = src->layout == SWK_YUV_SEMIPLANAR, mono = src->layout == SWK_YUV_MONO;
+    if (src->bits < 8 || src->bits > 16) return fail(ctx, SWK_ERR_ARG, "bits must be in 8..16");
+    const int sx = mono ? 0 : src->sx, sy = mono ? 0 : src->sy;
+    if (sx < 0 || sx > 2 || sy < 0 || sy > 1) return fail(ctx, SWK_ERR_ARG, "chroma subsampling shifts must be sx 0..2 and sy 0..1");
+    if (!src->y || (!mono && !src->u) || (!mono && !semi && !src->v)) return fail(ctx, SWK_ERR_ARG, "null YUV plane");
+    if (count < 1 || count > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "count must be in 1..2^24");
+    if ((src->mem != SWK_MEM_HOST && src->mem != SWK_MEM_DEVICE) || (bgr_mem != SWK_MEM_HOST && bgr_mem != SWK_MEM_DEVICE))
+        return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
+    const int H = src->H, W = src->W;
+    if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(ctx, SWK_ERR_ARG, "frame size must be 1..32768 on each side");
+    if (x0 < 0 || y0 < 0 || Hr < 1 || Wr < 1 || (int64_t)x0 + Wr > W || (int64_t)y0 + Hr > H)
+        return fail(ctx, SWK_ERR_ARG, "rectangle outside the frame");
+    const int B = src->bits > 8 ? 2 : 1;                              // bytes per sample
+    const int cbytes = semi ? 2 * B : B;                              // bytes per chroma sample position in a chroma row
+    const int cwf = ((W - 1) >> sx) + 1;                              // chroma samples in a row of the frame
+    if (src->y_row_stride < (int64_t)W * B || (!mono && src->c_row_stride < (int64_t)cwf * cbytes))
+        return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
+    if (B == 2) {
+        const bool frames = count > 1;
+        if ((src->y_row_stride & 1) || (frames && (src->y_frame_stride & 1)) ||
+            (!mono && ((src->c_row_stride & 1) || (frames && (src->c_frame_stride & 1)))))
+            return fail(ctx, SWK_ERR_ARG, "odd stride with 2-byte samples");
+        if (((uintptr_t)src->y & 1) || (!mono && ((uintptr_t)src->u & 1)) || (!mono && !semi && ((uintptr_t)src->v & 1)))
+            return fail(ctx, SWK_ERR_ARG, "odd plane address with 2-byte samples");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const size_t out_b = (size_t)count * Hr * Wr * 3;
+    const uint8_t *dy = src->y, *du = mono ? nullptr : src->u, *dv = mono || semi ? nullptr : src->v;
+    int64_t y_rs = src->y_row_stride, y_fs = src->y_frame_stride, c_rs = mono ? 0 : src->c_row_stride, c_fs = mono ? 0 : src->c_frame_stride;
+    int kx0 = x0, ky0 = y0;
+    if (src->mem == SWK_MEM_HOST) {
+        // only the chroma cells that cover the rectangle, and the luma samples of those cells (the rectangle grown to origins that
+        // are multiples of 2^sx and 2^sy), go to the device, densely; the kernel then sees a frame whose origin is the rectangle's
+        // first chroma cell
+        const int cy0 = y0 >> sy, ch = ((y0 + Hr - 1) >> sy) - cy0 + 1, cx0 = x0 >> sx, cw = ((x0 + Wr - 1) >> sx) - cx0 + 1;
+        const int ly0 = cy0 << sy, lx0 = cx0 << sx, lh = y0 + Hr - ly0, lw = x0 + Wr - lx0;
+        const size_t yb = ((size_t)count * lh * lw * B + 15) & ~(size_t)15;
+        const size_t cb = mono ? 0 : ((size_t)count * ch * cw * cbytes + 15) & ~(size_t)15;
+        uint8_t *din;
+        NEED(ctx, SL_TMP_IN, yb + cb * (semi ? 1 : 2), din);
+        int rc = upload_rects(ctx, din, src->y + (int64_t)ly0 * y_rs + (int64_t)lx0 * B, y_rs, y_fs, (size_t)lw * B, (size_t)lh, count);
+        if (rc) return rc;
+        if (!mono) {
+            const int64_t coff = (int64_t)cy0 * c_rs + (int64_t)cx0 * cbytes;
+            rc = upload_rects(ctx, din + yb, src->u + coff, c_rs, c_fs, (size_t)cw * cbytes, (size_t)ch, count);
+            if (rc) return rc;
+            if (!semi) {
+                rc = upload_rects(ctx, din + yb + cb, src->v + coff, c_rs, c_fs, (size_t)cw * cbytes, (size_t)ch, count);
+                if (rc) return rc;
+            }
+            du = din + yb; dv = semi ? nullptr : din + yb + cb;
+            c_rs = (int64_t)cw * cbytes; c_fs = (int64_t)ch * c_rs;
+        }
+        dy = din;
+        y_rs = (int64_t)lw * B; y_fs = (int64_t)lh * y_rs;
+        kx0 = x0 - lx0; ky0 = y0 - ly0;
+    }
+    uint8_t *dout = bgr;
+    if (bgr_mem == SWK_MEM_HOST) NEED(ctx, SL_TMP_OUT, out_b, dout);
+    {
+        Timed t(ctx, SWK_K_GRAY);
+        launch_yuv_to_bgr(ctx->stream, src->layout, sx, sy, src->bits, src->msb_aligned, src->full_range, dy, du, dv, y_fs, y_rs, c_fs, c_rs,
+                          kx0, ky0, count, Hr, Wr, dout);
+    }
+    if (bgr_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(bgr, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
 int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, double lmbda, double tol, int32_t maxiter,
                  double *A, double *E, int32_t *iters)
 {

@@ -164,6 +164,10 @@ void launch_filter_fused(hipStream_t s, const uint8_t *src, int F, int H, int W,
 // -> dense BGR [F][Hr][Wr][3]
 void launch_yuv420_to_bgr(hipStream_t s, int layout, const uint8_t *y, const uint8_t *u, const uint8_t *v, int64_t y_fs, int64_t y_rs,
                           int64_t c_fs, int64_t c_rs, int x0, int y0, int F, int Hr, int Wr, uint8_t *out);
+// the same for any swk_yuv format (layout SWK_YUV_PLANAR / _SEMIPLANAR / _MONO, chroma shifts sx 0..2 and sy 0..1, bits 8..16)
+void launch_yuv_to_bgr(hipStream_t s, int layout, int sx, int sy, int bits, int msb_aligned, int full_range, const uint8_t *y,
+                       const uint8_t *u, const uint8_t *v, int64_t y_fs, int64_t y_rs, int64_t c_fs, int64_t c_rs, int x0, int y0, int F,
+                       int Hr, int Wr, uint8_t *out);
 
 // classify_input.hip
 void launch_classifier_input(hipStream_t s, const uint8_t *crops, const int64_t *offsets, const int32_t *hw, int nseg,

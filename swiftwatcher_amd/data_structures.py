@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from . import image_filtering as img
-from .io_y4m import Yuv420Frame
+from .io_y4m import Yuv420Frame, YuvFrame
 
 STAGE_KEYS = OrderedDict([("gray", "grayscale"), ("rpca", "RPCA"), ("bilateral", "bilateral"),
                           ("thresh", "thresh_15"), ("opened", "opened"), ("labels", "cc_labeling")])
@@ -481,11 +481,14 @@ def stack_frames(frames, crop_region, min_seg_size, buffer, device=0):
     frame, ROI (Hc, Wc), reversed: the stack holds the frames in the opposite order).  Full decoded frames are cropped to the ROI plus its margin into buffer(shape) (swk_stage_frames).
     RoiFrames of a ROI-stream reader (io_roi_stream.py) already ARE that rectangle: when they sit, in this order, in one of the
     reader's page-locked blocks, the block itself is the stack -- no copy at all.
-    4:2:0 frames (io_y4m.Yuv420Frame) are staged as they are and converted to BGR on GPU `device`: the stack is then a device tensor."""
+    YUV frames (io_y4m.Yuv420Frame, io_y4m.YuvFrame) are staged as they are and converted to BGR on GPU `device`: the stack is then a
+    device tensor."""
     first = frames[0]
     (ya, yb, xa, xb), (x0, y0, x1, y1) = _margin_rect(first.shape, crop_region, min_seg_size)
     if isinstance(first, Yuv420Frame):
         return _stack_yuv420(frames, (ya, yb, xa, xb), buffer, device), (x0 - xa, y0 - ya), (y1 - y0, x1 - x0), False
+    if isinstance(first, YuvFrame):
+        return _stack_yuv(frames, (ya, yb, xa, xb), buffer, device), (x0 - xa, y0 - ya), (y1 - y0, x1 - x0), False
     if hasattr(first, "roi"):
         oy, ox = first.origin
         h, w = first.roi.shape[:2]
@@ -532,6 +535,36 @@ def _stack_yuv420(frames, rect, buffer, device):
     _lib.stage_frames([f.u for f in frames], cy0, cy1, cx0, cx1, U)
     _lib.stage_frames([f.v for f in frames], cy0, cy1, cx0, cx1, V)
     return _lib.default_context(device).yuv420_to_bgr(Y, U, V, rect=(xa - 2 * cx0, ya - 2 * cy0, xb - xa, yb - ya), device_out=True)
+
+
+def _stack_yuv(frames, rect, buffer, device):
+    """_stack_yuv420 for io_y4m.YuvFrame windows of one format: the rectangle grown to multiples of 2^sx and 2^sy, samples of 1 or 2
+    bytes each, converted by swk_yuv_to_bgr.  The same pixels as np.asarray(frame)[ya:yb, xa:xb], bit for bit."""
+    ya, yb, xa, xb = rect
+    first = frames[0]
+    if not all(isinstance(f, YuvFrame) and f.shape == first.shape and f.format == first.format for f in frames):
+        raise ValueError("a window mixes YUV frames of one format with other frames")
+    F, sx, sy, mono = len(frames), first.sx, first.sy, first.u is None
+    B = 2 if first.bits > 8 else 1
+    dtype = np.uint16 if B == 2 else np.uint8
+    cy0, cy1, cx0, cx1 = ya >> sy, ((yb - 1) >> sy) + 1, xa >> sx, ((xb - 1) >> sx) + 1
+    ly0, lx0 = cy0 << sy, cx0 << sx
+    lh, lw, ch, cw = yb - ly0, xb - lx0, cy1 - cy0, cx1 - cx0
+    luma, chroma = F * lh * lw * B, 0 if mono else F * ch * cw * B
+    staged = buffer((luma + 2 * chroma,))
+
+    def fill(planes, nbytes_at, r0, r1, c0, c1):
+        # (bytes: a 16-bit plane is staged through its uint8 view, columns counted in bytes)
+        dst = staged[nbytes_at[0]:nbytes_at[0] + nbytes_at[1]].reshape(F, r1 - r0, (c1 - c0) * B)
+        _lib.stage_frames([p.view(np.uint8) if B == 2 else p for p in planes], r0, r1, c0 * B, c1 * B, dst)
+        return dst.view(dtype) if B == 2 else dst
+    Y = fill([f.y for f in frames], (0, luma), ly0, yb, lx0, xb)
+    U = V = None
+    if not mono:
+        U = fill([f.u for f in frames], (luma, chroma), cy0, cy1, cx0, cx1)
+        V = fill([f.v for f in frames], (luma + chroma, chroma), cy0, cy1, cx0, cx1)
+    return _lib.default_context(device).yuv_to_bgr(Y, U, V, subsampling=(sx, sy), bits=first.bits, full_range=first.full_range,
+                                                   rect=(xa - lx0, ya - ly0, xb - xa, yb - ya), device_out=True)
 
 
 def _margin_rect(frame_shape, crop_region, min_seg_size):

@@ -89,11 +89,11 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
 
 def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, **kw):
     """Decoded frames (oldest first) -> (swift count, events).  frames may also be a reader (get_n_frames / read_frame / total_frames,
-    e.g. io_y4m.Y4MReader: its fps holds) or the path of a .y4m file.  Regions either explicit or from corners=...; params as in
-    swift_counting_algorithm."""
+    e.g. io_y4m.Y4MReader: its fps holds) or the path of a .y4m file (io_y4m.open_y4m: any format it reads).  Regions either explicit
+    or from corners=...; params as in swift_counting_algorithm."""
     if isinstance(frames, (str, bytes)) or hasattr(frames, "__fspath__"):
-        from .io_y4m import Y4MReader
-        frames = Y4MReader(frames)
+        from .io_y4m import open_y4m
+        frames = open_y4m(frames)
     reader = frames if hasattr(frames, "get_n_frames") else ArrayReader(frames, fps=fps)
     events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, **kw)
     return ec.count_swifts(events), events
