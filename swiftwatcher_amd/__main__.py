@@ -1,0 +1,130 @@
+"""python -m swiftwatcher_amd SOURCE [SOURCE ...] (--corners X1,Y1,X2,Y2 | --attributes FILE) [--start N] [--end N]
+       [--classify WEIGHTS] [--out DIR] [--windows-per-call K] [--device D]
+
+The reference's main() (__main__.py:13-53) without its UI: every SOURCE -- a .y4m file, or "-" for a YUV4MPEG2 stream on standard
+input (`ffmpeg -i evening.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners 812,640,1105,642`) -- is counted by
+pipeline.count_swifts, one after the other.  The chimney's corners come from --corners, from --attributes (a file in the format of
+the reference's attributes.json, ui.py:180-194), or, for a file, from <parent>/<stem>/attributes.json (:29-31).  Per source one JSON
+line goes to standard output: {"source", "frames", "events", "count"}; --out DIR gets the reference's result tables
+(io_data.export_results, :49-50; under DIR/<stem> when several sources are given)."""
+import argparse
+import json
+import os
+import sys
+
+
+def parse_corners(text):
+    """"X1,Y1,X2,Y2" -> ((x1, y1), (x2, y2))"""
+    parts = text.replace(" ", "").split(",")
+    try:
+        x1, y1, x2, y2 = (int(p) for p in parts)
+    except ValueError:
+        raise ValueError("corners are four integers X1,Y1,X2,Y2 (got %r)" % text)
+    return ((x1, y1), (x2, y2))
+
+
+def corners_from_file(path):
+    """ui.py:180-194: the "corners" entry of an attributes.json, [[x1, y1], [x2, y2]], as integer pairs."""
+    with open(path) as fh:
+        c = json.load(fh)["corners"]
+    return ((int(c[0][0]), int(c[0][1])), (int(c[1][0]), int(c[1][1])))
+
+
+def default_attributes(source):
+    """<parent>/<stem>/attributes.json of a video file (__main__.py:29-30)."""
+    return os.path.join(os.path.dirname(os.path.abspath(source)), os.path.splitext(os.path.basename(source))[0], "attributes.json")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog="python -m swiftwatcher_amd", description="Count chimney swifts in YUV4MPEG2 videos on the MI355X.")
+    p.add_argument("sources", nargs="+", metavar="SOURCE", help="a .y4m file, or - for a YUV4MPEG2 stream on standard input")
+    where = p.add_mutually_exclusive_group()
+    where.add_argument("--corners", metavar="X1,Y1,X2,Y2", help="the two corners of the chimney's top edge, in pixels")
+    where.add_argument("--attributes", metavar="FILE", help='a JSON file with "corners": [[x1, y1], [x2, y2]]')
+    p.add_argument("--start", type=int, default=0, metavar="N", help="first frame counted")
+    p.add_argument("--end", type=int, default=0, metavar="N", help="frame count to stop at (0: the whole video)")
+    p.add_argument("--classify", metavar="WEIGHTS", help="filter segments with the classifier of this state_dict file")
+    p.add_argument("--out", metavar="DIR", help="write the result tables (CSV) here")
+    p.add_argument("--windows-per-call", type=int, default=1, metavar="K", help="queue-fuls segmented per GPU call")
+    p.add_argument("--device", type=int, default=0, metavar="D", help="GPU index")
+    return p
+
+
+def plan(argv):
+    """(parsed arguments, [(source, corners), ...]); usage errors leave through the parser (exit status 2)."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.sources.count("-") > 1:
+        parser.error("standard input (-) can be given once")
+    if args.start < 0 or args.end < 0 or args.windows_per_call < 1:
+        parser.error("--start and --end are frame numbers, --windows-per-call is at least 1")
+    shared = None
+    try:
+        if args.corners is not None:
+            shared = parse_corners(args.corners)
+        elif args.attributes is not None:
+            shared = corners_from_file(args.attributes)
+    except (OSError, ValueError, KeyError, IndexError, TypeError) as exc:
+        parser.error("no corners: %s" % exc)
+    jobs = []
+    for source in args.sources:
+        corners = shared
+        if corners is None:
+            if source == "-":
+                parser.error("standard input (-) needs --corners or --attributes")
+            found = default_attributes(source)
+            if not os.path.isfile(found):
+                parser.error("%s needs --corners, --attributes or %s" % (source, found))
+            try:
+                corners = corners_from_file(found)
+            except (OSError, ValueError, KeyError, IndexError, TypeError) as exc:
+                parser.error("no corners in %s: %s" % (found, exc))
+        jobs.append((source, corners))
+    return args, jobs
+
+
+def main(argv=None):
+    args, jobs = plan(argv)
+    from . import event_classification as ec
+    from . import pipeline
+    from .io_data import export_results
+    from .io_y4m import open_y4m
+    classifier = None
+    if args.classify:
+        from .segment_classification import SegmentClassifier
+        classifier = SegmentClassifier(args.classify, device="cuda:%d" % args.device)
+    for source, corners in jobs:
+        try:
+            reader = open_y4m(source, args.start, args.end)
+        except (OSError, ValueError) as exc:
+            print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)
+            return 1
+        try:
+            count, events = pipeline.count_swifts(reader, corners=corners, classifier=classifier, device=args.device,
+                                                  windows_per_call=args.windows_per_call)
+            frames, fps, first, last = reader.total_frames, reader.fps, reader.start_frame, reader.end_frame
+        except (OSError, ValueError) as exc:
+            print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)
+            return 1
+        finally:
+            if hasattr(reader, "close"):
+                reader.close()
+        if args.out and events:                                                    # (__main__.py:40-50; without events there is no table)
+            stem = "stdin" if source == "-" else os.path.splitext(os.path.basename(source))[0]
+            out_dir = args.out if len(jobs) == 1 else os.path.join(args.out, stem)
+            with _stdout_to_stderr():                                              # (export_results prints its progress line)
+                export_results(out_dir, ec.classify_events(events), fps, first, last)
+        print(json.dumps({"source": source, "frames": int(frames), "events": len(events), "count": int(count)}), flush=True)
+    return 0
+
+
+class _stdout_to_stderr:
+    def __enter__(self):
+        self._saved, sys.stdout = sys.stdout, sys.stderr
+
+    def __exit__(self, *exc):
+        sys.stdout = self._saved
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -482,7 +482,8 @@ def stack_frames(frames, crop_region, min_seg_size, buffer, device=0):
     RoiFrames of a ROI-stream reader (io_roi_stream.py) already ARE that rectangle: when they sit, in this order, in one of the
     reader's page-locked blocks, the block itself is the stack -- no copy at all.
     YUV frames (io_y4m.Yuv420Frame, io_y4m.YuvFrame) are staged as they are and converted to BGR on GPU `device`: the stack is then a
-    device tensor."""
+    device tensor.  Those of a pipe's reader that hold one rectangle (io_y4m.Yuv420RectFrame, YuvRectFrame) go the same way, the
+    rectangle translated by the frames' origin: the same stack, bit for bit."""
     first = frames[0]
     (ya, yb, xa, xb), (x0, y0, x1, y1) = _margin_rect(first.shape, crop_region, min_seg_size)
     if isinstance(first, Yuv420Frame):
@@ -515,6 +516,20 @@ def _device_stack(stack):
     return None if isinstance(stack, np.ndarray) else stack
 
 
+def _held_origin(frames, luma_rect):
+    """(oy, ox): where the planes of YUV frames start in their picture -- (0, 0) for whole frames, the origin of frames that hold one
+    rectangle (io_y4m.Yuv420RectFrame / YuvRectFrame: it lies on the chroma grid), which must be the same rectangle in every frame
+    and hold the luma rows and columns (r0, r1, c0, c1) that are staged."""
+    first = frames[0]
+    oy, ox = getattr(first, "origin", (0, 0))
+    if any(getattr(f, "origin", (0, 0)) != (oy, ox) or f.y.shape != first.y.shape for f in frames):
+        raise ValueError("a window mixes frames that hold different rectangles")
+    r0, r1, c0, c1 = luma_rect
+    if r0 < oy or c0 < ox or r1 > oy + first.y.shape[0] or c1 > ox + first.y.shape[1]:
+        raise ValueError("the frames do not hold the crop region plus its margin")
+    return oy, ox
+
+
 def _stack_yuv420(frames, rect, buffer, device):
     """The rectangle (ya, yb, xa, xb) of 4:2:0 frames (io_y4m.Yuv420Frame) as a BGR stack (F, yb - ya, xb - xa, 3) ON THE GPU (a
     torch uint8 tensor; batch_run reads it in place): the chroma samples that cover the rectangle and their luma pixels (the
@@ -531,9 +546,10 @@ def _stack_yuv420(frames, rect, buffer, device):
     Y = staged[:luma].reshape(F, lh, lw)
     U = staged[luma:luma + chroma].reshape(F, ch, cw)
     V = staged[luma + chroma:].reshape(F, ch, cw)
-    _lib.stage_frames([f.y for f in frames], 2 * cy0, yb, 2 * cx0, xb, Y)
-    _lib.stage_frames([f.u for f in frames], cy0, cy1, cx0, cx1, U)
-    _lib.stage_frames([f.v for f in frames], cy0, cy1, cx0, cx1, V)
+    oy, ox = _held_origin(frames, (2 * cy0, yb, 2 * cx0, xb))
+    _lib.stage_frames([f.y for f in frames], 2 * cy0 - oy, yb - oy, 2 * cx0 - ox, xb - ox, Y)
+    _lib.stage_frames([f.u for f in frames], cy0 - (oy >> 1), cy1 - (oy >> 1), cx0 - (ox >> 1), cx1 - (ox >> 1), U)
+    _lib.stage_frames([f.v for f in frames], cy0 - (oy >> 1), cy1 - (oy >> 1), cx0 - (ox >> 1), cx1 - (ox >> 1), V)
     return _lib.default_context(device).yuv420_to_bgr(Y, U, V, rect=(xa - 2 * cx0, ya - 2 * cy0, xb - xa, yb - ya), device_out=True)
 
 
@@ -558,11 +574,12 @@ def _stack_yuv(frames, rect, buffer, device):
         dst = staged[nbytes_at[0]:nbytes_at[0] + nbytes_at[1]].reshape(F, r1 - r0, (c1 - c0) * B)
         _lib.stage_frames([p.view(np.uint8) if B == 2 else p for p in planes], r0, r1, c0 * B, c1 * B, dst)
         return dst.view(dtype) if B == 2 else dst
-    Y = fill([f.y for f in frames], (0, luma), ly0, yb, lx0, xb)
+    oy, ox = _held_origin(frames, (ly0, yb, lx0, xb))
+    Y = fill([f.y for f in frames], (0, luma), ly0 - oy, yb - oy, lx0 - ox, xb - ox)
     U = V = None
     if not mono:
-        U = fill([f.u for f in frames], (luma, chroma), cy0, cy1, cx0, cx1)
-        V = fill([f.v for f in frames], (luma + chroma, chroma), cy0, cy1, cx0, cx1)
+        U = fill([f.u for f in frames], (luma, chroma), cy0 - (oy >> sy), cy1 - (oy >> sy), cx0 - (ox >> sx), cx1 - (ox >> sx))
+        V = fill([f.v for f in frames], (luma + chroma, chroma), cy0 - (oy >> sy), cy1 - (oy >> sy), cx0 - (ox >> sx), cx1 - (ox >> sx))
     return _lib.default_context(device).yuv_to_bgr(Y, U, V, subsampling=(sx, sy), bits=first.bits, full_range=first.full_range,
                                                    rect=(xa - lx0, ya - ly0, xb - xa, yb - ya), device_out=True)
 

@@ -13,7 +13,21 @@ same pixels.
 open_y4m(path) picks the reader.  Y4MReader: 8-bit 4:2:0, progressive; it refuses everything else by name.  YuvReader: C420*,
 C422, C444, C411 and Cmono, with the suffixes p9, p10, p12, p14, p16 (mono9, mono10, mono12, mono16: little-endian 16-bit samples),
 limited range or, with XCOLORRANGE=FULL, full range.  Interlaced files, C444alpha and FRAME lines with parameters are refused by
-name."""
+name.
+
+A source that can only be read once, front to back, and whose length nobody knows -- "-" (standard input), a FIFO, a descriptor, a
+binary file object: `ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners ...` -- gets Y4MStreamReader: the
+same formats and refusals, the same frames, numbers, timestamps and counters call by call, total_frames / end_frame as properties
+that look one FRAME marker ahead.  Told the crop region, it hands out Yuv420RectFrame / YuvRectFrame, which hold only the rectangle
+the counting loop reads and index in full-frame coordinates: the bytes it holds do not grow with the video."""
+import datetime
+import os
+import stat
+import sys
+import threading
+import time
+from collections import deque
+
 import numpy as np
 
 from .io_frames import ArrayReader
@@ -377,9 +391,538 @@ class YuvReader(ArrayReader):
         return ArrayReader.get_frame(self, frame_number)
 
 
-def open_y4m(path, start=0, end=0, full_range=None):
-    """The reader of a .y4m file: Y4MReader for an 8-bit 4:2:0 limited-range progressive file, YuvReader for every other supported
-    format.  full_range: None = what the header says, True / False override it."""
+# ---------------------------------------------------------------------------------------------------- reading from a pipe
+def _held_error(r0, r1, c0, c1, oy, ox, h, w):
+    return IndexError("rows %d:%d, columns %d:%d leave the held rectangle (rows %d:%d, columns %d:%d)" % (r0, r1, c0, c1, oy, oy + h, ox, ox + w))
+
+
+class _RectFrame:
+    """What Yuv420RectFrame and YuvRectFrame share: the planes hold luma rows [oy, oy + h) x columns [ox, ox + w) of the picture and
+    the chroma samples that cover them; (oy, ox) lies on the chroma grid, so a pixel's chroma sample is found the same way in the
+    held planes as in the whole ones.  Indexed in full-frame coordinates like io_roi_stream.RoiFrame."""
+    __slots__ = ()
+
+    def _holds_all(self):
+        return self.origin == (0, 0) and self.y.shape == self.shape[:2]
+
+    def __array__(self, dtype=None, copy=None):
+        if not self._holds_all():
+            raise _held_error(0, self.shape[0], 0, self.shape[1], self.origin[0], self.origin[1], *self.y.shape)
+        bgr = self._held_rect(0, self.shape[0], 0, self.shape[1])
+        return bgr if dtype is None else bgr.astype(dtype, copy=False)
+
+    def __getitem__(self, key):
+        """frame[r0:r1, c0:c1] in full-frame coordinates: the BGR pixels the whole picture's frame would give; IndexError for a
+        rectangle that leaves the held one."""
+        if isinstance(key, slice):
+            key = (key, slice(None))
+        if not (isinstance(key, tuple) and len(key) >= 2 and isinstance(key[0], slice) and isinstance(key[1], slice)):
+            if self._holds_all():
+                return np.asarray(self)[key]
+            raise TypeError("a frame that holds a rectangle is indexed with two slices in full-frame coordinates: frame[y0:y1, x0:x1]")
+        if key[0].step not in (None, 1) or key[1].step not in (None, 1):
+            raise TypeError("strided access to a frame that holds a rectangle")
+        r0, r1, _ = key[0].indices(self.shape[0])
+        c0, c1, _ = key[1].indices(self.shape[1])
+        oy, ox = self.origin
+        h, w = self.y.shape
+        if r1 > r0 and c1 > c0 and (r0 < oy or c0 < ox or r1 > oy + h or c1 > ox + w):
+            raise _held_error(r0, r1, c0, c1, oy, ox, h, w)
+        out = self._held_rect(r0, r1, c0, c1)
+        return out[(slice(None), slice(None)) + tuple(key[2:])] if len(key) > 2 else out
+
+
+class Yuv420RectFrame(_RectFrame, Yuv420Frame):
+    """A Yuv420Frame that holds one rectangle of its picture: y (h, w) from the even origin (oy, ox), u and v (ceil(h/2), ceil(w/2))."""
+    __slots__ = ("origin",)
+
+    def __init__(self, y, u, v, origin, full_shape):
+        oy, ox = int(origin[0]), int(origin[1])
+        h, w = y.shape
+        H, W = int(full_shape[0]), int(full_shape[1])
+        if oy & 1 or ox & 1 or oy < 0 or ox < 0 or oy + h > H or ox + w > W:
+            raise ValueError("the held rectangle starts on even rows and columns inside the %dx%d picture" % (W, H))
+        if u.shape != ((h + 1) // 2, (w + 1) // 2) or v.shape != u.shape:
+            raise ValueError("chroma planes of a %dx%d 4:2:0 rectangle are %dx%d" % (w, h, (w + 1) // 2, (h + 1) // 2))
+        self.y, self.u, self.v, self.shape, self.origin = y, u, v, (H, W, 3), (oy, ox)
+
+    def _held_rect(self, r0, r1, c0, c1):
+        oy, ox = self.origin
+        return yuv420_rect_to_bgr(self.y, self.u, self.v, r0 - oy, r1 - oy, c0 - ox, c1 - ox)
+
+
+class YuvRectFrame(_RectFrame, YuvFrame):
+    """A YuvFrame that holds one rectangle of its picture: y (h, w) from the origin (oy, ox), a multiple of (2^sy, 2^sx), u and v
+    (ceil(h / 2^sy), ceil(w / 2^sx)) or None."""
+    __slots__ = ("origin",)
+
+    def __init__(self, y, u, v, origin, full_shape, subsampling=(1, 1), bits=8, full_range=False):
+        YuvFrame.__init__(self, y, u, v, subsampling, bits, full_range)          # (checks the planes against each other)
+        oy, ox = int(origin[0]), int(origin[1])
+        h, w = y.shape
+        H, W = int(full_shape[0]), int(full_shape[1])
+        if oy & ((1 << self.sy) - 1) or ox & ((1 << self.sx) - 1) or oy < 0 or ox < 0 or oy + h > H or ox + w > W:
+            raise ValueError("the held rectangle starts on the chroma grid inside the %dx%d picture" % (W, H))
+        self.shape, self.origin = (H, W, 3), (oy, ox)
+
+    def _held_rect(self, r0, r1, c0, c1):
+        oy, ox = self.origin
+        return yuv_rect_to_bgr(self.y, self.u, self.v, r0 - oy, r1 - oy, c0 - ox, c1 - ox, self.sx, self.sy, self.bits, self.full_range)
+
+
+def held_rect(frame_hw, crop_region, min_seg_size=(24, 24), subsampling=(1, 1)):
+    """(ya, yb, xa, xb) of the luma pixels a frame must hold for the counting loop over crop_region: the crop region plus half the
+    minimum segment size (io_roi_stream.margin_rect), its origin moved up and left onto the chroma grid (what
+    data_structures._stack_yuv420 / _stack_yuv stage)."""
+    from .io_roi_stream import margin_rect
+    ya, yb, xa, xb = margin_rect(frame_hw, crop_region, min_seg_size)
+    sx, sy = subsampling
+    return (ya >> sy) << sy, yb, (xa >> sx) << sx, xb
+
+
+class _ByteSource:
+    """Bytes in order from "-" (standard input), a file descriptor, a path (a FIFO) or a binary file object with readinto or read.
+    fill() loops over short reads; seconds / bytes: time spent in, and bytes got from, the source's read calls."""
+
+    def __init__(self, source):
+        self._own = None
+        if isinstance(source, str) and source == "-":
+            fh, self.name = sys.stdin.buffer, "<stdin>"
+        elif isinstance(source, int):
+            fh = self._own = os.fdopen(source, "rb", buffering=0, closefd=False)          # (closing the wrapper leaves the descriptor open)
+            self.name = "<descriptor %d>" % source
+        elif isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
+            fh = self._own = open(source, "rb", buffering=0)
+            self.name = os.fsdecode(source)
+        else:
+            fh, self.name = source, str(getattr(source, "name", None) or "<%s>" % type(source).__name__)
+        self._readinto, self._read = getattr(fh, "readinto", None), getattr(fh, "read", None)
+        if self._readinto is None and self._read is None:
+            raise TypeError("a YUV4MPEG2 stream needs a binary file object with readinto or read")
+        self.seconds, self.bytes = 0.0, 0
+        try:          # a pipe of the default 64 KiB wakes reader and writer 48 times per 1080p frame: ask for 1 MiB (refusals do not matter)
+            import fcntl
+            fd = fh.fileno()
+            if stat.S_ISFIFO(os.fstat(fd).st_mode):
+                fcntl.fcntl(fd, getattr(fcntl, "F_SETPIPE_SZ", 1031), 1 << 20)
+        except Exception:
+            pass
+
+    def fill(self, buf):
+        """Reads until buf (a writable buffer of bytes) is full or the source ends; returns the bytes got."""
+        view = memoryview(buf).cast("B")
+        want, got = len(view), 0
+        t0 = time.perf_counter()
+        while got < want:
+            if self._readinto is not None:
+                k = self._readinto(view[got:])
+            else:
+                data = self._read(want - got)
+                k = None if data is None else len(data)
+                if k:
+                    view[got:got + k] = data
+            if k is None:
+                raise ValueError("a YUV4MPEG2 stream needs a blocking source: %s has no data ready" % self.name)
+            if k == 0:
+                break
+            got += k
+        self.seconds += time.perf_counter() - t0
+        self.bytes += got
+        return got
+
+    def close(self):
+        if self._own is not None:
+            self._own.close()
+            self._own = None
+
+
+class Y4MStreamReader:
+    """The reference FrameReader's surface and bookkeeping (io_video.py:13-82) over a YUV4MPEG2 source that can only be read once,
+    front to back, and whose length nobody knows: a pipe (`ffmpeg ... -f yuv4mpegpipe - | ...`), a FIFO, a descriptor, a file object.
+    For the same bytes every get_n_frames call returns what the file readers' (Y4MReader / YuvReader) return, counters included.
+
+    total_frames / end_frame are properties: exact once the source has ended or when end= was given, else the number of frames
+    known to exist -- and reading them looks one FRAME marker ahead (it may block), so they are at least one more than the frames
+    handed out while the video goes on.  `while queue.frames_processed < reader.total_frames` therefore decides like over a file.
+
+    crop_region (here or by set_region before the first window): frames are handed out as Yuv420RectFrame / YuvRectFrame holding
+    held_rect(...) only; whole frames (Yuv420Frame / YuvFrame) otherwise.  The first frame stays available in full through
+    read_frame(0, increment=False) until the first window has been handed out (generate_regions needs it).
+
+    ahead: windows read by a background thread beyond the one handed out (counted in frames of the last get_n_frames(n)); 0 reads
+    in the caller's thread, and never more than one FRAME marker beyond the last frame handed out.  read_seconds / read_bytes: time
+    in, and bytes from, the source's read calls."""
+
+    def __init__(self, source, start=0, end=0, full_range=None, crop_region=None, min_seg_size=(24, 24), ahead=1):
+        self._src = _ByteSource(source)
+        self.filepath = source if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__") else self._src.name
+        try:
+            head = bytearray(len(MAGIC))
+            if self._src.fill(head) < len(MAGIC) or bytes(head) != MAGIC:
+                raise ValueError("not a YUV4MPEG2 file: %s" % self._src.name)
+            one = bytearray(1)
+            while self._src.fill(one) == 1 and one != b"\n":
+                head += one
+                if len(head) >= 4096:
+                    break
+            if one != b"\n":
+                raise ValueError("the YUV4MPEG2 header line does not end: %s" % self._src.name)
+            width, height, num, den, fmt = _parse_header(bytes(head), general=True)
+        except BaseException:
+            self._src.close()
+            raise
+        self._header_bytes = len(head) + 1
+        if full_range is not None:
+            fmt = fmt[:4] + (bool(full_range),)
+        self.width, self.height, self.rate, self.fps = width, height, (num, den), num / den
+        self.mono, self.subsampling, self.bits, self.full_range = fmt[0], (fmt[1], fmt[2]), fmt[3], fmt[4]
+        self._plain420 = fmt[:4] == (False, 1, 1, 8) and not fmt[4]          # the formats open_y4m gives Y4MReader: Yuv420Frame
+        self._sample = 2 if self.bits > 8 else 1
+        sx, sy = self.subsampling
+        self._cshape = (((height - 1) >> sy) + 1, ((width - 1) >> sx) + 1)
+        self._luma = width * height * self._sample
+        self._chroma = 0 if self.mono else self._cshape[0] * self._cshape[1] * self._sample
+        self._body_bytes = self._luma + 2 * self._chroma
+        self.start_frame, self._end = int(start), int(end)
+        self.next_frame_number = self.start_frame
+        self.frame_shape = (height, width, 3)
+        self.last_read_frame, self.frames_read, self.read_errors = None, 0, 0
+        self._midnight = datetime.datetime.combine(datetime.date.today(), datetime.time())
+        self.ahead = max(int(ahead), 0)
+        # where the source stands: pictures consumed, whether the next one's FRAME marker is consumed too, whether it has ended
+        self._decoded, self._marked, self._eof, self._fail = 0, False, False, None
+        self._scratch = None                       # one whole picture: what is read past (frames before start, pixels outside the rectangle)
+        self._first, self._first_wanted = None, True
+        # the producer's own counters (it runs ahead of what has been handed out): next number, frames read, read errors, last frame, shape
+        self._cur = [self.start_frame, 0, 0, None, self.frame_shape]
+        self._cv = threading.Condition()
+        self._items, self._cap = deque(), 1
+        self._thread, self._done, self._stop, self._closed = None, False, False, False
+        self._handed = False
+        self.crop_region, self.min_seg_size, self._rect = None, tuple(min_seg_size), None
+        if crop_region is not None:
+            self.set_region(crop_region, min_seg_size)
+
+    # ---- what is kept of a picture ----
+    def set_region(self, crop_region, min_seg_size=(24, 24)):
+        """Frames handed out from here on hold only what the counting loop over crop_region reads (held_rect).  Before the first
+        window; later only the region already set is accepted."""
+        region = [tuple(int(c) for c in crop_region[0]), tuple(int(c) for c in crop_region[1])]
+        size = tuple(int(s) for s in min_seg_size)
+        if self._handed or self._thread is not None:
+            if (region, size) != (self.crop_region, self.min_seg_size):
+                raise ValueError("the region of a stream reader is set before its first window is read")
+            return
+        self.crop_region, self.min_seg_size = region, size
+        ya, yb, xa, xb = held_rect((self.height, self.width), region, size, self.subsampling)
+        if yb <= ya or xb <= xa:
+            raise ValueError("the crop region lies outside the %dx%d picture" % (self.width, self.height))
+        self._rect = (ya, yb, xa, xb)
+
+    def _planes(self, buf):
+        """(y, u, v) views of a buffer that holds one whole picture."""
+        def plane(at, nbytes, shape):
+            raw = buf[at:at + nbytes]
+            return (raw.view("<u2") if self._sample == 2 else raw).reshape(shape)
+        y = plane(0, self._luma, (self.height, self.width))
+        if self.mono:
+            return y, None, None
+        return y, plane(self._luma, self._chroma, self._cshape), plane(self._luma + self._chroma, self._chroma, self._cshape)
+
+    def _rect_shapes(self):
+        ya, yb, xa, xb = self._rect
+        sx, sy = self.subsampling
+        return (yb - ya, xb - xa), (((yb - 1) >> sy) + 1 - (ya >> sy), ((xb - 1) >> sx) + 1 - (xa >> sx))
+
+    def _rect_frame(self, y, u, v):
+        origin = (self._rect[0], self._rect[2])
+        if self._plain420:
+            return Yuv420RectFrame(y, u, v, origin, self.frame_shape)
+        return YuvRectFrame(y, u, v, origin, self.frame_shape, self.subsampling, self.bits, self.full_range)
+
+    def _held(self, planes):
+        """The frame handed out for a picture whose whole planes are `planes`: they themselves, or a copy of the rectangle."""
+        y, u, v = planes
+        if self._rect is None:
+            if self._plain420:
+                return Yuv420Frame(y, u, v)
+            return YuvFrame(y, u, v, self.subsampling, self.bits, self.full_range)
+        ya, yb, xa, xb = self._rect
+        sx, sy = self.subsampling
+        (lh, lw), (ch, cw) = self._rect_shapes()
+        dt = y.dtype
+        block = np.empty(lh * lw + (0 if self.mono else 2 * ch * cw), dt)          # one allocation per frame
+        hy = block[:lh * lw].reshape(lh, lw)
+        np.copyto(hy, y[ya:yb, xa:xb])
+        if self.mono:
+            return self._rect_frame(hy, None, None)
+        hu = block[lh * lw:lh * lw + ch * cw].reshape(ch, cw)
+        hv = block[lh * lw + ch * cw:].reshape(ch, cw)
+        np.copyto(hu, u[ya >> sy:(ya >> sy) + ch, xa >> sx:(xa >> sx) + cw])
+        np.copyto(hv, v[ya >> sy:(ya >> sy) + ch, xa >> sx:(xa >> sx) + cw])
+        return self._rect_frame(hy, hu, hv)
+
+    def _null(self):
+        """The reference's null frame (io_video.py:40-44) in the form this reader's frames have."""
+        if self._rect is None:
+            if self._plain420:
+                return Yuv420Frame.null(self.height, self.width)
+            return YuvFrame.null(self.height, self.width, self.subsampling, self.bits, self.full_range, self.mono)
+        (lh, lw), cshape = self._rect_shapes()
+        dt = np.uint16 if self._sample == 2 else np.uint8
+        y = np.zeros((lh, lw), dt)
+        if self.mono:
+            return self._rect_frame(y, None, None)
+        return self._rect_frame(y, np.full(cshape, 128 << (self.bits - 8), dt), np.full(cshape, 128 << (self.bits - 8), dt))
+
+    # ---- the source, picture by picture (one thread at a time: the read-ahead thread while it runs, else the caller's) ----
+    def _known(self):
+        return self._decoded + (1 if self._marked else 0)
+
+    def _wake(self):
+        with self._cv:
+            self._cv.notify_all()
+
+    def _mark(self):
+        """Consumes the next picture's FRAME marker; False when the source has ended in front of it.  A marker that is cut or wrong
+        counts as a picture: reading that picture raises."""
+        if self._eof:
+            return False
+        if self._marked:
+            return True
+        mark = bytearray(len(FRAME_MARK))
+        got = self._src.fill(mark)
+        if got == 0:
+            self._eof = True
+            self._wake()
+            return False
+        if got < len(FRAME_MARK):
+            self._fail = ValueError("%s ends inside the FRAME marker of frame %d: %d of its %d bytes arrived"
+                                    % (self._src.name, self._decoded, got, len(FRAME_MARK)))
+        elif bytes(mark[:5]) == b"FRAME" and mark[5] != 0x0A:
+            self._fail = ValueError("FRAME headers with parameters are not supported: %s" % self._src.name)
+        elif bytes(mark) != FRAME_MARK:
+            self._fail = ValueError("no FRAME marker %s: %s" % ("after the header" if self._decoded == 0 else "in front of frame %d" % self._decoded,
+                                                                self._src.name))
+        self._marked = True
+        self._wake()
+        return True
+
+    def _body(self, keep):
+        """Consumes the marked picture's planes; keep: returns the frame to hand out, else the picture is read past."""
+        if self._fail is not None:
+            raise self._fail
+        first = self._decoded == 0 and self._first_wanted
+        if first or (keep and self._rect is None):
+            buf = np.empty(self._body_bytes, np.uint8)          # a frame that is held whole owns its buffer
+        else:
+            if self._scratch is None:
+                self._scratch = np.empty(self._body_bytes, np.uint8)
+            buf = self._scratch
+        got = self._src.fill(buf)
+        if got < self._body_bytes:
+            plane = "luma" if got < self._luma else "chroma"
+            self._fail = ValueError("%s ends inside frame %d (in its %s): %d of its %d bytes arrived"
+                                    % (self._src.name, self._decoded, plane, got, self._body_bytes))
+            raise self._fail
+        planes = self._planes(buf)
+        if first:
+            self._first = planes
+        self._marked = False
+        self._decoded += 1
+        self._wake()
+        return self._held(planes) if keep else None
+
+    def _seek(self, k):
+        """Reads past the pictures in front of picture k and consumes its marker; False when the source ends before it."""
+        while self._mark():
+            if self._decoded >= k:
+                return True
+            self._body(False)
+        return False
+
+    def _picture(self, k):
+        """The frame to hand out for picture k (the pictures are asked for in order), None when the source ends before it."""
+        if k < self._decoded:
+            if k == 0 and self._first is not None:          # read early by read_frame(0, increment=False)
+                return self._held(self._first)
+            raise ValueError("a stream cannot go back to frame %d" % k)
+        return self._body(True) if self._seek(k) else None
+
+    def _produce(self):
+        """The next (frame, number, timestamp, counters after it) of get_frame's sequence (io_video.py:40-59), None when a null frame
+        follows.  Counters change only once the frame is there."""
+        nxt, nread, nerr, last, shape = self._cur
+        if nxt < self.start_frame or (self._end > 0 and nxt > self._end):
+            return None
+        frame = self._picture(nxt)
+        if frame is None and self._end == 0 and nxt > self._decoded:          # (the source has ended: _decoded is the frame count)
+            return None
+        stamp = self.frame_number_to_timestamp(nxt)
+        if frame is None:
+            frame, nerr = last, nerr + 1                                       # :51-53
+        else:
+            last, nread, shape = frame, nread + 1, frame.shape
+        self._cur = [nxt + 1, nread, nerr, last, shape]
+        return frame, nxt, stamp, (nxt + 1, nread, nerr, last, shape)
+
+    # ---- reading ahead ----
+    def _run(self):
+        try:
+            while True:
+                with self._cv:
+                    self._cv.wait_for(lambda: self._stop or len(self._items) < max(self._cap, 1))
+                    if self._stop:
+                        break
+                item = self._produce()
+                if item is None:
+                    break
+                with self._cv:
+                    self._items.append(item)
+                    self._cv.notify_all()
+        except BaseException as exc:                  # surfaces in the get_n_frames call that needed the frame
+            with self._cv:
+                self._items.append(exc)
+        finally:
+            with self._cv:
+                self._done = True
+                self._cv.notify_all()
+
+    def _take(self):
+        if self._thread is not None:
+            with self._cv:
+                self._cv.wait_for(lambda: self._items or self._done)
+                if self._items:
+                    item = self._items[0]
+                    if isinstance(item, BaseException):
+                        raise item
+                    self._items.popleft()
+                    self._cv.notify_all()
+                    return item
+        return self._produce()          # no thread, or it has finished: null frames follow (or the error it met)
+
+    # ---- the reference reader's surface ----
+    @property
+    def end_frame(self):
+        if self._end > 0:
+            return self._end
+        want = self.next_frame_number + 1
+        if self._thread is not None and not self._done:
+            with self._cv:
+                self._cv.wait_for(lambda: self._eof or self._done or self._known() >= want)
+        if (self._thread is None or self._done) and not self._eof and self._fail is None and self._known() < want:
+            try:
+                self._seek(want - 1)
+            except ValueError:
+                pass                                  # a picture that cannot be read: get_n_frames raises when it is asked for
+        return self._known()
+
+    @property
+    def total_frames(self):
+        return self.end_frame - self.start_frame
+
+    def frame_number_to_timestamp(self, frame_number):
+        from .io_data import frame_timestamp_ns
+        return self._midnight + datetime.timedelta(microseconds=frame_timestamp_ns(frame_number, self.fps) // 1000)
+
+    def read_frame(self, frame_number, increment=True):
+        """The video's first frame in full, until the first window has been handed out (swift_counting_algorithm reads it for
+        generate_regions); None when the video has no frame.  A stream has no other frame to offer out of turn."""
+        if frame_number != 0 or increment or self._handed or self._thread is not None:
+            raise ValueError("a stream reader only offers read_frame(0, increment=False), before its first window")
+        if self._first is None and self._decoded == 0 and self._seek(0):
+            self._body(False)
+        return None if self._first is None else self._whole_first()
+
+    def _whole_first(self):
+        y, u, v = self._first
+        if self._plain420:
+            return Yuv420Frame(y, u, v)
+        return YuvFrame(y, u, v, self.subsampling, self.bits, self.full_range)
+
+    def _hand(self, item):
+        if item is None:
+            return self._null(), -1, "00:00:00.000"          # (:40-44)
+        frame, number, stamp, (self.next_frame_number, self.frames_read, self.read_errors, self.last_read_frame, self.frame_shape) = item
+        return frame, number, stamp
+
+    def get_frame(self, frame_number=None):
+        if frame_number is not None and frame_number != self.next_frame_number:
+            raise ValueError("a stream reader hands its frames out in order (next: %d)" % self.next_frame_number)
+        frames, numbers, stamps = self.get_n_frames(1)
+        return frames[0], numbers[0], stamps[0]
+
+    def get_n_frames(self, n):
+        if self._closed:
+            raise ValueError("the stream reader is closed")
+        if self.ahead > 0 and self._thread is None:
+            self._cap = self.ahead * int(n)
+            self._thread = threading.Thread(target=self._run, name="swk-y4m-read", daemon=True)
+            self._thread.start()
+        elif self._thread is not None:
+            with self._cv:
+                self._cap = max(self.ahead, 1) * int(n)
+                self._cv.notify_all()
+        frames, numbers, stamps = [], [], []
+        for _ in range(n):
+            f, k, t = self._hand(self._take())
+            frames.append(f); numbers.append(k); stamps.append(t)
+        self._handed = True
+        self._first, self._first_wanted = None, False
+        return frames, numbers, stamps
+
+    @property
+    def read_seconds(self):
+        return self._src.seconds
+
+    @property
+    def read_bytes(self):
+        return self._src.bytes
+
+    def close(self):
+        """Stops the read-ahead thread and closes what the reader opened itself (not standard input, not a file object or a
+        descriptor it was given)."""
+        if self._closed:
+            return
+        self._closed = True
+        with self._cv:
+            self._stop = True
+            self._cv.notify_all()
+        if self._thread is not None:
+            self._thread.join(2.0)
+        if self._thread is None or not self._thread.is_alive():          # (a thread still waiting in read keeps its descriptor)
+            self._src.close()
+        self._items.clear()
+        self._first = self._scratch = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+def _is_stream(source):
+    """True for a source open_y4m reads front to back: "-", a file descriptor, a binary file object, the path of a FIFO."""
+    if isinstance(source, bool):
+        return False
+    if isinstance(source, int) or (isinstance(source, str) and source == "-"):
+        return True
+    if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__"):
+        try:
+            return stat.S_ISFIFO(os.stat(source).st_mode)
+        except OSError:
+            return False          # (the file reader names what is wrong with the path)
+    return hasattr(source, "readinto") or hasattr(source, "read")
+
+
+def open_y4m(source, start=0, end=0, full_range=None, crop_region=None, min_seg_size=(24, 24), ahead=1):
+    """The reader of a YUV4MPEG2 video.  The path of a regular file: Y4MReader for an 8-bit 4:2:0 limited-range progressive file,
+    YuvReader for every other supported format (crop_region, min_seg_size and ahead do not apply to them).  A source that can only
+    be read once, front to back -- the path of a FIFO, "-" (standard input), a file descriptor, a binary file object --:
+    Y4MStreamReader.  full_range: None = what the header says, True / False override it."""
+    if _is_stream(source):
+        return Y4MStreamReader(source, start, end, full_range, crop_region, min_seg_size, ahead)
+    path = source
     with open(path, "rb") as fh:
         head = fh.read(4096)
     if not head.startswith(MAGIC):

@@ -24,12 +24,14 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
         crop_region, roi_mask, _ = img.generate_regions(first_frame, corners)      # :63
     if crop_region is None or roi_mask is None:
         raise ValueError("either corners or crop_region + roi_mask are needed")
+    if hasattr(reader, "set_region"):                # a reader of a pipe (io_y4m.Y4MStreamReader): it keeps only what this loop reads
+        reader.set_region(crop_region, min_seg_size)
     tracker = SegmentTracker(roi_mask)
     if classifier is not None and getattr(reader, "_classifier_hint", False) is None:
         import weakref
         reader._classifier_hint = weakref.ref(classifier)          # a reader that segments ahead scores every batch for this classifier
     if windows_per_call > 1:
-        if hasattr(reader, "ahead"):                 # a reader that reads ahead (io_roi_stream): as far as one GPU call takes
+        if hasattr(reader, "ahead"):                 # a reader that reads ahead (io_roi_stream, io_y4m's of a pipe): as far as one GPU call takes
             reader.ahead = max(reader.ahead, windows_per_call)
         # producer thread: reads ahead and segments (GPU call and array copies release the GIL);
         # this thread: classifier and the strictly sequential tracker
@@ -89,14 +91,29 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
 
 def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, **kw):
     """Decoded frames (oldest first) -> (swift count, events).  frames may also be a reader (get_n_frames / read_frame / total_frames,
-    e.g. io_y4m.Y4MReader: its fps holds) or the path of a .y4m file (io_y4m.open_y4m: any format it reads).  Regions either explicit
-    or from corners=...; params as in swift_counting_algorithm."""
-    if isinstance(frames, (str, bytes)) or hasattr(frames, "__fspath__"):
+    e.g. io_y4m.Y4MReader: its fps holds) or anything io_y4m.open_y4m opens: the path of a .y4m file (any format it reads), or a
+    YUV4MPEG2 stream of unknown length -- "-" (standard input), a FIFO's path, a file descriptor, a binary file object (a pipe from a
+    decoder: proc.stdout).  Regions either explicit or from corners=...; params as in swift_counting_algorithm."""
+    opened = None
+    if _is_video_source(frames):
         from .io_y4m import open_y4m
-        frames = open_y4m(frames)
+        frames = opened = open_y4m(frames)
     reader = frames if hasattr(frames, "get_n_frames") else ArrayReader(frames, fps=fps)
-    events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, **kw)
+    try:
+        events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, **kw)
+    finally:
+        if opened is not None and hasattr(opened, "close"):
+            opened.close()
     return ec.count_swifts(events), events
+
+
+def _is_video_source(video):
+    """What io_y4m.open_y4m opens: a path, "-" (standard input), a file descriptor, a binary file object."""
+    if isinstance(video, (str, bytes)) or hasattr(video, "__fspath__"):
+        return True
+    if isinstance(video, bool) or hasattr(video, "get_n_frames"):
+        return False
+    return isinstance(video, int) or hasattr(video, "readinto") or hasattr(video, "read")
 
 
 def plan_calls(items, n, pad_factor=2.0):
@@ -166,10 +183,23 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
     GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
     windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
     frames one by one in the reference's order, so every count and event list equals count_swifts on that video alone.
-    videos: readers (read_frame / get_n_frames / total_frames) or decoded frame arrays (oldest first); regions: per video
+    videos: readers (read_frame / get_n_frames / total_frames), decoded frame arrays (oldest first) or what io_y4m.open_y4m opens (a
+    .y4m path, "-", a FIFO, a descriptor, a binary file object); regions: per video
     (crop_region, roi_mask), or corners: per video the chimney's top edge (the regions then come from its first frame, :62-63).
     Returns [(count, events), ...] in input order."""
-    readers = [v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
+    from .io_y4m import open_y4m
+    readers = [open_y4m(v) if _is_video_source(v) else v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
+    opened = [r for r, v in zip(readers, videos) if r is not v and hasattr(r, "close")]          # (closed again when the count is done)
+    try:
+        return _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device,
+                             pad_factor, params)
+    finally:
+        for r in opened:
+            r.close()
+
+
+def _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device, pad_factor, params):
+    """count_swifts_videos over readers."""
     if regions is None:
         if corners is None:
             raise ValueError("either regions or corners are needed")
@@ -179,6 +209,10 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
             regions.append((crop_region, roi_mask))
     if len(regions) != len(readers):
         raise ValueError("one region pair per video")
+    for r, (crop_region, _) in zip(readers, regions):
+        if hasattr(r, "set_region"):                 # a reader of a pipe (io_y4m.Y4MStreamReader): it keeps only what this loop reads
+            r.set_region(crop_region, min_seg_size)
+            r.ahead = max(r.ahead, windows_per_call)
     trackers = [SegmentTracker(mask) for _, mask in regions]
     sizes = [(cr[1][0] - cr[0][0]) * (cr[1][1] - cr[0][1]) for cr, _ in regions]
 
