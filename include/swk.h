@@ -42,7 +42,8 @@ enum {
     SWK_ERR_NOGPU = -3,     /* no usable gfx950 device                      */
     SWK_ERR_CAPACITY = -4,  /* request exceeds what the context was sized for */
     SWK_ERR_NOMEM = -5,
-    SWK_ERR_STALE = -6      /* the batch a call refers to is no longer held by the context */
+    SWK_ERR_STALE = -6,     /* the batch a call refers to is no longer held by the context */
+    SWK_ERR_TRACK_STATUS = -7 /* swk_track_window: a segment without a status, the reference's TypeError */
 };
 
 enum { SWK_MEM_HOST = 0, SWK_MEM_DEVICE = 1 };
@@ -459,6 +460,56 @@ int32_t swk_track_costs(const double *prev_c, const double *prev_hist0, const ui
 /* apply_hungarian_algorithm (segment_tracking.py:257-263): scipy.optimize.linear_sum_assignment's algorithm
  * with its tie rule; col4row[i] = column assigned to row i (n_rows <= n_cols). */
 int32_t swk_lsap(const double *cost, int32_t n_rows, int32_t n_cols, int32_t *col4row);
+
+/* ---- the tracker, a whole window of frames per call (host, no GPU, no context) -----------------------
+ * A swk_tracker carries what SegmentTracker carries between frames (segment_tracking.py:17-44): the ROI mask (copied at creation,
+ * [H][W] uint8) and the cached frame's segments.  Segments are named by ORDINALS: a running int64 count since creation, in frame
+ * order and then segment order; the caller keeps whatever else belongs to a segment under that number.  Per live segment (a segment
+ * of the last frame) the handle keeps its centroid, its chain (the ordinals of its segment_history, oldest first -- the reference
+ * shares ONE list along a chain of matches, :149-152, so a chain has one owner here) and the centroid of the chain's first member,
+ * the only history value a cost reads (:225-227).
+ * A handle is NOT thread-safe: serialise the calls on it.  Different handles are independent. */
+typedef struct swk_tracker swk_tracker;
+int32_t swk_tracker_create(const uint8_t *roi_mask, int32_t H, int32_t W, swk_tracker **out);
+void swk_tracker_destroy(swk_tracker *t);
+
+/* SegmentTracker.step (:46-176: cost matrix, assignment, statuses, history take-over, events, caching) for `nframes` consecutive frames,
+ * in order, against the state in `t`.  nseg[nframes] = segments per frame (0 is valid, and so is nframes = 0); centroids = the
+ * (row, col) float64 pairs of all of them, frame after frame.  The frames' segments get the ordinals *first_ordinal,
+ * *first_ordinal + 1, ...  Per frame exactly what the per-frame path does: swk_track_costs and swk_lsap themselves (the same libm
+ * calls in the same order, the same tie-breaking); a previous segment becomes matched or disappeared, a current one appeared only on
+ * its own diagonal cell (store_assignments :104-131); a matched segment takes over its predecessor's chain and appends the
+ * predecessor (:133-152); then, over the previous frame's segments in their order, a disappeared one with
+ * roi_mask[int(row), int(col)] == 255 (numpy's indexing: truncation towards zero, negative indices count from the end) and a chain
+ * of at least one member is an EVENT (:154-176), its path the chain plus the segment itself.
+ * Events of this window, in detection order, in CSR form: event e is event_ordinals[event_offsets[e] .. event_offsets[e + 1]).
+ * event_offsets holds event_capacity + 1 entries, event_ordinals ordinal_capacity.  *n_events / *n_ordinals = what the window
+ * needs; when either exceeds its capacity the call returns SWK_ERR_CAPACITY and has changed NOTHING in `t`: call again with larger
+ * buffers.  *frames_done = frames applied (nframes unless SWK_ERR_TRACK_STATUS).  *min_live (optional) = the smallest ordinal a live
+ * segment or its chain still names: nothing below it can appear in a later event (= the next ordinal when nothing is live).
+ * SWK_ERR_TRACK_STATUS: at frame *frames_done a current segment is neither matched nor on its diagonal, where the reference's
+ * link_matching_segments raises TypeError (:139; only an assignment no optimal solver returns gets there).  The frames before it are
+ * applied and their events returned; that frame and those behind it are not.
+ * SWK_ERR_ARG: a null pointer with a non-zero count, a negative count, or a disappeared segment whose centroid lies outside the mask
+ * (numpy would raise); `t` is unchanged then. */
+int32_t swk_track_window(swk_tracker *t, int32_t nframes, const int32_t *nseg, const double *centroids,
+                         int32_t event_capacity, int64_t ordinal_capacity, int64_t *event_offsets, int64_t *event_ordinals,
+                         int32_t *n_events, int64_t *n_ordinals, int32_t *frames_done, int64_t *first_ordinal,
+                         int64_t *min_live);
+
+/* The live state, out and in: for a caller that moves between this path and SegmentTracker's per-frame methods.
+ * swk_tracker_export: per live segment its centroid, its ordinal and its chain (CSR: chain_offsets[n + 1], chain_ordinals);
+ * *n_segments / *n_chain_ordinals = what is needed, SWK_ERR_CAPACITY when a buffer is smaller (chain_offsets holds
+ * segment_capacity + 1 entries).  `t` is not changed.
+ * swk_tracker_import: replaces the live state by n_segments segments with the given centroids; chain_lengths[k] = members of segment
+ * k's chain, chain_first[k] = (row, col) of its first member (ignored for an empty chain).  The imported segments are numbered like
+ * a frame's: from *first_ordinal (the handle's next ordinal) the chain members of segment 0 oldest first, those of segment 1, ...,
+ * then the n_segments segments themselves. */
+int32_t swk_tracker_export(swk_tracker *t, int32_t segment_capacity, int64_t ordinal_capacity, double *centroids,
+                           int64_t *ordinals, int64_t *chain_offsets, int64_t *chain_ordinals, int32_t *n_segments,
+                           int64_t *n_chain_ordinals);
+int32_t swk_tracker_import(swk_tracker *t, int32_t n_segments, const double *centroids, const int64_t *chain_lengths,
+                           const double *chain_first, int64_t *first_ordinal);
 
 /* ---- ROI mask of a video (host side, no GPU, no context): SURVEY section 8f rank 3 -----------------------
  * image_filtering.py:99-180, run once per video on its first frame.  PARITY UNPINNED (OpenCV 4.1.0 semantics restated:

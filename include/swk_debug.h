@@ -133,6 +133,12 @@ int32_t swk_prof_refined_windows(swk_ctx *ctx, int64_t *refined, int64_t *unrefi
  * Pillow, integer for integer: a fused multiply-add or another summation order in the device code would show here. */
 int32_t swk_debug_resize_table(swk_ctx *ctx, int32_t first, int32_t count, int32_t route, int32_t *bounds, int32_t *coeffs);
 
+/* White-box hook of the window tracker's tests: after skip_frames more frames, the next frame that swk_track_window steps takes
+ * col4row[n] (n = its previous plus its current segments, each entry in [0, n)) instead of the solver's assignment -- the one way to an
+ * assignment that leaves a current segment without a status (SWK_ERR_TRACK_STATUS), which no optimal solver returns.  Used up by that
+ * frame; SWK_ERR_ARG from swk_track_window when n is not that frame's size. */
+int32_t swk_debug_tracker_force_assignment(swk_tracker *t, int32_t skip_frames, const int32_t *col4row, int32_t n);
+
 /* ---- classifier kernels: A/B switches ---- */
 /* Measurement knobs of the classifier kernels (A/B runs).  knob 0: workgroup layout of the 1 x 1 kernel (0 = 16-wave workgroups, the
  * default; 1 = 8 waves with the deepest activation ring that fits; results do not depend on it).  knob 1: 1 = the Fire modules' expand1x1

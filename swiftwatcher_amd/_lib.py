@@ -149,6 +149,14 @@ _SIGS = {
     "swk_classifier_input_window": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "swk_track_costs": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "swk_lsap": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+    "swk_tracker_create": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]),
+    "swk_tracker_destroy": (None, [ctypes.c_void_p]),
+    "swk_track_window": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
+    "swk_tracker_export": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64] + [ctypes.c_void_p] * 6),
+    "swk_tracker_import": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32] + [ctypes.c_void_p] * 4),
+    "swk_debug_tracker_force_assignment": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
     "swk_median_blur_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "swk_otsu_threshold_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_canny_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
@@ -965,6 +973,106 @@ def lsap(cost):
     if rc:
         raise SwkError("swk_lsap failed (%d)" % rc)
     return out
+
+
+ERR_CAPACITY, ERR_TRACK_STATUS = -4, -7
+
+
+class Tracker:
+    """A swk_tracker handle (include/swk.h): SegmentTracker's state between frames, stepped a whole window per call.  Host code, no GPU,
+    no Context.  Not thread-safe, like the handle."""
+
+    def __init__(self, roi_mask, event_capacity=32, ordinal_capacity=1024):
+        mask = np.asarray(roi_mask)
+        if mask.ndim != 2:
+            raise ValueError("the ROI mask is a 2-D array")
+        mask = np.ascontiguousarray(np.where(mask == 255, 255, 0), np.uint8)          # all the tracker asks of it is `== 255`
+        self._lib = load()
+        handle = ctypes.c_void_p()
+        rc = self._lib.swk_tracker_create(mask.ctypes.data, mask.shape[0], mask.shape[1], ctypes.byref(handle))
+        if rc:
+            raise SwkError("swk_tracker_create failed (%d)" % rc)
+        self._handle = handle
+        self._fn = self._lib.swk_track_window
+        self.event_capacity, self.ordinal_capacity = int(event_capacity), int(ordinal_capacity)
+        self._offsets = self._ordinals = None
+        self._out32 = np.zeros(2, np.int32)           # n_events, frames_done
+        self._out64 = np.zeros(3, np.int64)           # n_ordinals, first_ordinal, min_live
+
+    def __del__(self):
+        try:
+            if self._handle:
+                self._lib.swk_tracker_destroy(self._handle)
+                self._handle = None
+        except Exception:
+            pass
+
+    def track_window(self, nseg, centroids):
+        """swk_track_window.  nseg: segments per frame; centroids: their (row, col) pairs, flat or (total, 2).  Returns (status_error,
+        frames_done, first_ordinal, min_live, event offsets, event ordinals), the last two as lists (CSR).  status_error: frame
+        `frames_done` holds a segment without a status (SWK_ERR_TRACK_STATUS); the frames before it are applied.  Event buffers that
+        turn out too small are enlarged and the call is made again: the refused call changed nothing."""
+        counts = np.ascontiguousarray(nseg, np.int32).reshape(-1)
+        cents = np.ascontiguousarray(centroids, np.float64).reshape(-1)
+        if counts.size and int(counts.min()) < 0:
+            raise ValueError("a negative segment count")
+        if cents.size != 2 * int(counts.sum()):
+            raise ValueError("%d centroid values for %d segments" % (cents.size, int(counts.sum())))
+        o32, o64 = self._out32, self._out64
+        p32, p64 = o32.ctypes.data, o64.ctypes.data
+        while True:
+            if self._offsets is None or len(self._offsets) != self.event_capacity + 1:
+                self._offsets = np.empty(self.event_capacity + 1, np.int64)
+            if self._ordinals is None or len(self._ordinals) != max(self.ordinal_capacity, 1):
+                self._ordinals = np.empty(max(self.ordinal_capacity, 1), np.int64)
+            rc = self._fn(self._handle, counts.size, counts.ctypes.data, cents.ctypes.data, self.event_capacity, self.ordinal_capacity,
+                          self._offsets.ctypes.data, self._ordinals.ctypes.data, p32, p64, p32 + 4, p64 + 8, p64 + 16)
+            if rc != ERR_CAPACITY:
+                break
+            self.event_capacity = max(self.event_capacity, 2 * int(o32[0]))
+            self.ordinal_capacity = max(self.ordinal_capacity, 2 * int(o64[0]))
+        if rc not in (0, ERR_TRACK_STATUS):
+            raise SwkError("swk_track_window failed (%d)" % rc)
+        n_events, done = o32.tolist()
+        n_ordinals, first, min_live = o64.tolist()
+        return (rc == ERR_TRACK_STATUS, done, first, min_live, self._offsets[:n_events + 1].tolist(), self._ordinals[:n_ordinals].tolist())
+
+    def export_state(self):
+        """swk_tracker_export: (centroids (n, 2), ordinals (n,), chain offsets (n + 1,), chain ordinals) of the live segments."""
+        n32, n64 = ctypes.c_int32(0), ctypes.c_int64(0)
+        seg_cap, ord_cap = 0, 0
+        while True:
+            cents, ords = np.empty((seg_cap, 2), np.float64), np.empty(seg_cap, np.int64)
+            offs, chain = np.zeros(seg_cap + 1, np.int64), np.empty(max(ord_cap, 1), np.int64)
+            rc = self._lib.swk_tracker_export(self._handle, seg_cap, ord_cap, cents.ctypes.data, ords.ctypes.data, offs.ctypes.data,
+                                              chain.ctypes.data, ctypes.byref(n32), ctypes.byref(n64))
+            if rc != ERR_CAPACITY:
+                break
+            seg_cap, ord_cap = n32.value, n64.value
+        if rc:
+            raise SwkError("swk_tracker_export failed (%d)" % rc)
+        return cents[:n32.value], ords[:n32.value], offs[:n32.value + 1], chain[:n64.value]
+
+    def import_state(self, centroids, chain_lengths, chain_first):
+        """swk_tracker_import: the live segments' centroids (n, 2), the lengths of their chains and the centroids of the chains' first
+        members (n, 2; ignored where a chain is empty).  Returns the first ordinal of the numbering the header describes."""
+        lens = np.ascontiguousarray(chain_lengths, np.int64).reshape(-1)
+        cents = np.ascontiguousarray(centroids, np.float64).reshape(-1)
+        first = np.ascontiguousarray(chain_first, np.float64).reshape(-1)
+        if cents.size != 2 * lens.size or first.size != 2 * lens.size:
+            raise ValueError("one centroid pair and one first-of-chain pair per segment")
+        out = ctypes.c_int64(0)
+        rc = self._lib.swk_tracker_import(self._handle, lens.size, cents.ctypes.data, lens.ctypes.data, first.ctypes.data, ctypes.byref(out))
+        if rc:
+            raise SwkError("swk_tracker_import failed (%d)" % rc)
+        return out.value
+
+    def force_assignment(self, col4row, skip_frames=0):
+        """swk_debug_tracker_force_assignment (include/swk_debug.h): the tests' white-box hook."""
+        a = np.ascontiguousarray(col4row, np.int32).reshape(-1)
+        rc = self._lib.swk_debug_tracker_force_assignment(self._handle, int(skip_frames), a.ctypes.data, a.size)
+        if rc:
+            raise SwkError("swk_debug_tracker_force_assignment failed (%d)" % rc)
 
 
 def pinned_empty(shape, dtype=np.uint8, device=0):

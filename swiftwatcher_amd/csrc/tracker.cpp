@@ -1,14 +1,16 @@
 // Host-side pieces of the segment tracker: the two-frame cost matrix of
 // segment_tracking.py:46-102,179-254 and the assignment solve behind apply_hungarian_algorithm (:257-263).
 // Plain C++ (no GPU): the reference runs this part on the host too; it is per-frame sequential logic on
-// matrices of a few dozen rows.  The Python bookkeeping (statuses, shared history lists, events) lives in
-// swiftwatcher_amd/segment_tracking.py.
+// matrices of a few dozen rows.  The bookkeeping around them (statuses, shared history lists, events) exists twice:
+// per frame in Python (swiftwatcher_amd/segment_tracking.py, SegmentTracker.step) and per window of frames below
+// (swk_track_window, behind SegmentTracker.step_window).
 #include <math.h>
 #include <stdint.h>
 #include <float.h>
+#include <new>
 #include <vector>
 #include <algorithm>
-#include "swk.h"
+#include "swk_debug.h"
 
 #pragma GCC visibility push(default)
 extern "C" {
@@ -117,6 +119,282 @@ int32_t swk_lsap(const double *cost, int32_t n_rows, int32_t n_cols, int32_t *co
             if (r == cur) break;
         }
     }
+    return SWK_OK;
+}
+
+}  // extern "C"
+#pragma GCC visibility pop
+
+// ---- a whole window of frames per call: the bookkeeping of SegmentTracker.step (store_assignments :104-131,
+// link_matching_segments :133-152, check_for_events :154-176) on arrays, around the two functions above ----
+//
+// A segment is named by its ordinal (0, 1, 2, ... in frame order, then segment order).  Of the reference's shared
+// history lists only what a later step reads is kept: per live segment (a segment of the last frame) its centroid, its
+// chain (the ordinals of its history, oldest first) and the centroid of the chain's first member -- the only history
+// value a cost reads (:225-227).  A chain has one owner: a matched segment takes its predecessor's (a move, like the
+// reference's take-over of the list object), so "shared, not copied" costs nothing here.
+namespace {
+
+struct LiveSegment {
+    double r, c;                    // centroid (row, col)
+    double h0r, h0c;                // centroid of chain[0]; meaningless while the chain is empty
+    int64_t ordinal;
+    std::vector<int64_t> chain;     // segment_history as ordinals
+};
+
+struct TrackState {
+    std::vector<LiveSegment> live;  // the cached frame's segments
+    int64_t next_ordinal = 0;
+    std::vector<int32_t> forced;    // swk_debug_tracker_force_assignment: the assignment of the frame after forced_skip more, if has_forced
+    int32_t forced_skip = 0;
+    bool has_forced = false;
+};
+
+enum { STATUS_NONE = -2, STATUS_APPEARED = -1 };          // a current segment's status; >= 0: index of its predecessor
+
+}  // namespace
+
+struct swk_tracker {
+    std::vector<uint8_t> roi;
+    int32_t H = 0, W = 0;
+    TrackState st;
+    // the last window's events, kept between the run and the copy into the caller's buffers
+    std::vector<int64_t> ev_off, ev_ord;
+    // per-frame scratch
+    std::vector<double> prev_c, prev_h0, cost;
+    std::vector<uint8_t> has_hist;
+    std::vector<int32_t> assign, prev_status, curr_status;
+};
+
+namespace {
+
+// roi_mask[int(r), int(c)] as numpy reads it: int() truncates towards zero, a negative index counts from the end.
+// false: numpy would raise (IndexError, or ValueError / OverflowError for a centroid that is no finite number).
+bool mask_index(double v, int32_t size, int64_t *idx)
+{
+    const double t = trunc(v);
+    if (!(t >= -(double)size && t < (double)size)) return false;
+    *idx = (int64_t)t < 0 ? (int64_t)t + size : (int64_t)t;
+    return true;
+}
+
+// One SegmentTracker.step against `st`.  Events are appended to t->ev_off / t->ev_ord.
+int32_t step_frame(swk_tracker *t, TrackState &st, const double *curr_c, int32_t n_curr)
+{
+    std::vector<LiveSegment> &prev = st.live;
+    const int32_t n_prev = (int32_t)prev.size(), n = n_prev + n_curr;
+    t->prev_status.assign(n_prev, 0);
+    t->curr_status.assign(n_curr, STATUS_NONE);
+    if (n) {
+        // formulate_cost_matrix + apply_hungarian_algorithm: the same two functions the per-frame path calls
+        t->prev_c.resize(2 * (size_t)n_prev);
+        t->prev_h0.resize(2 * (size_t)n_prev);
+        t->has_hist.resize(n_prev);
+        for (int32_t i = 0; i < n_prev; ++i) {
+            t->prev_c[2 * i] = prev[i].r;
+            t->prev_c[2 * i + 1] = prev[i].c;
+            const bool hist = !prev[i].chain.empty();
+            t->has_hist[i] = hist;
+            t->prev_h0[2 * i] = hist ? prev[i].h0r : 0.0;
+            t->prev_h0[2 * i + 1] = hist ? prev[i].h0c : 0.0;
+        }
+        t->cost.resize((size_t)n * n);
+        t->assign.resize(n);
+        int32_t rc = swk_track_costs(t->prev_c.data(), t->prev_h0.data(), t->has_hist.data(), curr_c, n_prev, n_curr, t->cost.data());
+        if (rc == SWK_OK) rc = swk_lsap(t->cost.data(), n, n, t->assign.data());
+        if (rc != SWK_OK) return rc;
+    }
+    if (st.has_forced && st.forced_skip-- == 0) {
+        if ((int32_t)st.forced.size() != n) return SWK_ERR_ARG;
+        t->assign = st.forced;
+        st.has_forced = false;
+    }
+    // store_assignments (:104-131)
+    for (int32_t i = 0; i < n_prev; ++i) {
+        const int32_t target = t->assign[i] - n_prev;
+        t->prev_status[i] = target;                                   // < 0: "D"
+        if (target >= 0) t->curr_status[target] = i;
+    }
+    for (int32_t j = 0; j < n_curr; ++j)
+        if (t->assign[n_prev + j] - n_prev == j) t->curr_status[j] = STATUS_APPEARED;
+    for (int32_t j = 0; j < n_curr; ++j)
+        if (t->curr_status[j] == STATUS_NONE) return SWK_ERR_TRACK_STATUS;       // the reference indexes a list with None (:139)
+    // link_matching_segments (:133-152)
+    std::vector<LiveSegment> curr(n_curr);
+    for (int32_t j = 0; j < n_curr; ++j) {
+        LiveSegment &s = curr[j];
+        s.r = curr_c[2 * j];
+        s.c = curr_c[2 * j + 1];
+        s.h0r = s.h0c = 0.0;
+        s.ordinal = st.next_ordinal + j;
+        const int32_t status = t->curr_status[j];
+        if (status == STATUS_APPEARED) continue;
+        LiveSegment &matched = prev[status];
+        if (matched.chain.empty()) { s.h0r = matched.r; s.h0c = matched.c; }
+        else { s.h0r = matched.h0r; s.h0c = matched.h0c; }
+        s.chain = std::move(matched.chain);
+        matched.chain.clear();
+        s.chain.push_back(matched.ordinal);
+    }
+    // check_for_events (:154-176)
+    for (int32_t i = 0; i < n_prev; ++i) {
+        if (t->prev_status[i] >= 0) continue;
+        int64_t row, col;
+        if (!mask_index(prev[i].r, t->H, &row) || !mask_index(prev[i].c, t->W, &col)) return SWK_ERR_ARG;
+        if (t->roi[(size_t)row * t->W + col] != 255) continue;
+        if (prev[i].chain.empty()) continue;
+        t->ev_ord.insert(t->ev_ord.end(), prev[i].chain.begin(), prev[i].chain.end());
+        t->ev_ord.push_back(prev[i].ordinal);
+        t->ev_off.push_back((int64_t)t->ev_ord.size());
+    }
+    st.next_ordinal += n_curr;
+    st.live = std::move(curr);
+    return SWK_OK;
+}
+
+int64_t min_live_ordinal(const TrackState &st)
+{
+    int64_t m = st.next_ordinal;
+    for (const LiveSegment &s : st.live) m = std::min(m, s.chain.empty() ? s.ordinal : s.chain[0]);
+    return m;
+}
+
+}  // namespace
+
+#pragma GCC visibility push(default)
+extern "C" {
+
+int32_t swk_tracker_create(const uint8_t *roi_mask, int32_t H, int32_t W, swk_tracker **out)
+{
+    if (!out) return SWK_ERR_ARG;
+    *out = nullptr;
+    if (H < 0 || W < 0 || (!roi_mask && H > 0 && W > 0)) return SWK_ERR_ARG;
+    try {
+        swk_tracker *t = new swk_tracker();
+        t->H = H;
+        t->W = W;
+        if (H > 0 && W > 0) t->roi.assign(roi_mask, roi_mask + (size_t)H * W);
+        *out = t;
+    } catch (const std::bad_alloc &) {
+        return SWK_ERR_NOMEM;
+    }
+    return SWK_OK;
+}
+
+void swk_tracker_destroy(swk_tracker *t)
+{
+    delete t;
+}
+
+int32_t swk_track_window(swk_tracker *t, int32_t nframes, const int32_t *nseg, const double *centroids,
+                         int32_t event_capacity, int64_t ordinal_capacity, int64_t *event_offsets, int64_t *event_ordinals,
+                         int32_t *n_events, int64_t *n_ordinals, int32_t *frames_done, int64_t *first_ordinal,
+                         int64_t *min_live)
+{
+    if (!t || nframes < 0 || event_capacity < 0 || ordinal_capacity < 0 || (nframes > 0 && !nseg)) return SWK_ERR_ARG;
+    if (!n_events || !n_ordinals || !frames_done || !event_offsets || (ordinal_capacity > 0 && !event_ordinals)) return SWK_ERR_ARG;
+    int64_t total = 0;
+    for (int32_t f = 0; f < nframes; ++f) {
+        if (nseg[f] < 0) return SWK_ERR_ARG;
+        total += nseg[f];
+    }
+    if (total > 0 && !centroids) return SWK_ERR_ARG;
+    try {
+        TrackState work = t->st;                  // the window runs on a copy: a refused call changes nothing
+        t->ev_off.assign(1, 0);
+        t->ev_ord.clear();
+        int32_t rc = SWK_OK, done = 0;
+        const double *c = centroids;
+        for (; done < nframes; ++done) {
+            rc = step_frame(t, work, c, nseg[done]);
+            if (rc == SWK_ERR_TRACK_STATUS) break;          // found before the frame changed anything: the frames before it stay applied
+            if (rc != SWK_OK) return rc;                    // (nothing applied)
+            c += 2 * (size_t)nseg[done];
+        }
+        const int64_t events = (int64_t)t->ev_off.size() - 1, ords = (int64_t)t->ev_ord.size();
+        *n_events = (int32_t)events;
+        *n_ordinals = ords;
+        if (events > event_capacity || ords > ordinal_capacity) return SWK_ERR_CAPACITY;
+        std::copy(t->ev_off.begin(), t->ev_off.end(), event_offsets);
+        std::copy(t->ev_ord.begin(), t->ev_ord.end(), event_ordinals);
+        *frames_done = done;
+        if (first_ordinal) *first_ordinal = t->st.next_ordinal;
+        t->st = std::move(work);
+        if (min_live) *min_live = min_live_ordinal(t->st);
+        return rc;
+    } catch (const std::bad_alloc &) {
+        return SWK_ERR_NOMEM;
+    }
+}
+
+int32_t swk_tracker_export(swk_tracker *t, int32_t segment_capacity, int64_t ordinal_capacity, double *centroids,
+                           int64_t *ordinals, int64_t *chain_offsets, int64_t *chain_ordinals, int32_t *n_segments,
+                           int64_t *n_chain_ordinals)
+{
+    if (!t || segment_capacity < 0 || ordinal_capacity < 0 || !n_segments || !n_chain_ordinals || !chain_offsets) return SWK_ERR_ARG;
+    if ((segment_capacity > 0 && (!centroids || !ordinals)) || (ordinal_capacity > 0 && !chain_ordinals)) return SWK_ERR_ARG;
+    const std::vector<LiveSegment> &live = t->st.live;
+    int64_t ords = 0;
+    for (const LiveSegment &s : live) ords += (int64_t)s.chain.size();
+    *n_segments = (int32_t)live.size();
+    *n_chain_ordinals = ords;
+    if ((int64_t)live.size() > segment_capacity || ords > ordinal_capacity) return SWK_ERR_CAPACITY;
+    int64_t at = 0;
+    chain_offsets[0] = 0;
+    for (size_t k = 0; k < live.size(); ++k) {
+        centroids[2 * k] = live[k].r;
+        centroids[2 * k + 1] = live[k].c;
+        ordinals[k] = live[k].ordinal;
+        std::copy(live[k].chain.begin(), live[k].chain.end(), chain_ordinals + at);
+        at += (int64_t)live[k].chain.size();
+        chain_offsets[k + 1] = at;
+    }
+    return SWK_OK;
+}
+
+int32_t swk_tracker_import(swk_tracker *t, int32_t n_segments, const double *centroids, const int64_t *chain_lengths,
+                           const double *chain_first, int64_t *first_ordinal)
+{
+    if (!t || n_segments < 0 || (n_segments > 0 && (!centroids || !chain_lengths || !chain_first))) return SWK_ERR_ARG;
+    int64_t members = 0;
+    for (int32_t k = 0; k < n_segments; ++k) {
+        if (chain_lengths[k] < 0) return SWK_ERR_ARG;
+        members += chain_lengths[k];
+    }
+    try {
+        std::vector<LiveSegment> live(n_segments);
+        int64_t at = t->st.next_ordinal;
+        for (int32_t k = 0; k < n_segments; ++k) {
+            LiveSegment &s = live[k];
+            s.r = centroids[2 * k];
+            s.c = centroids[2 * k + 1];
+            s.h0r = chain_lengths[k] ? chain_first[2 * k] : 0.0;
+            s.h0c = chain_lengths[k] ? chain_first[2 * k + 1] : 0.0;
+            s.chain.resize((size_t)chain_lengths[k]);
+            for (int64_t m = 0; m < chain_lengths[k]; ++m) s.chain[m] = at++;
+        }
+        for (int32_t k = 0; k < n_segments; ++k) live[k].ordinal = at++;
+        if (first_ordinal) *first_ordinal = t->st.next_ordinal;
+        t->st.live = std::move(live);
+        t->st.next_ordinal += members + n_segments;
+        return SWK_OK;
+    } catch (const std::bad_alloc &) {
+        return SWK_ERR_NOMEM;
+    }
+}
+
+int32_t swk_debug_tracker_force_assignment(swk_tracker *t, int32_t skip_frames, const int32_t *col4row, int32_t n)
+{
+    if (!t || skip_frames < 0 || n < 0 || (n > 0 && !col4row)) return SWK_ERR_ARG;
+    for (int32_t i = 0; i < n; ++i)
+        if (col4row[i] < 0 || col4row[i] >= n) return SWK_ERR_ARG;
+    try {
+        t->st.forced.assign(col4row, col4row + n);
+    } catch (const std::bad_alloc &) {
+        return SWK_ERR_NOMEM;
+    }
+    t->st.forced_skip = skip_frames;
+    t->st.has_forced = true;
     return SWK_OK;
 }
 

@@ -12,12 +12,15 @@ from . import image_filtering as img
 
 
 def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size=21, classifier=None, min_seg_size=(24, 24),
-                             device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None):
+                             device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None,
+                             track_by_window=True):
     """Same call order as __main__.py:62-100.  corners = ((x1, y1), (x2, y2)) of the chimney's top edge: crop region
     and ROI mask are then generated from the video's first frame (:62-63) instead of being passed in.  Returns the tracker's detected events (lists of Segment objects,
     the structure the reference hands to event classification).  windows_per_call > 1 reads that many queue-fuls
     ahead and segments (and classifies) them in one GPU call each; the tracker still sees the frames one by one in
-    the reference's order, so the events are the same.  params: a _lib.default_params(...) struct for the segment path (bilateral
+    the reference's order, so the events are the same.  track_by_window (windows_per_call > 1 only): the tracker takes each
+    window's frames in one library call (SegmentTracker.step_window) instead of one step per frame -- the same events; False is the
+    per-frame path.  params: a _lib.default_params(...) struct for the segment path (bilateral
     diameter and sigmas, threshold, ...); None = the reference's values."""
     if corners is not None:
         first_frame = reader.read_frame(0, increment=False)                        # :62
@@ -64,8 +67,7 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
             if classifier is not None:
                 classifier.classify_frames([fr for popped in batches for fr in popped])
             for popped in batches:
-                for frame in popped:
-                    tracker.step(frame)
+                _track(tracker, popped, track_by_window)
         worker.join()
         return tracker.detected_events
     queue = FrameQueue(queue_size, device=device, params=params, keep_stages=keep_stages)
@@ -87,6 +89,16 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
             if export_dir is not None:                                         # :94-96 (--export): needs keep_stages=True (the "crop" image)
                 frame.export_segments(min_seg_size, crop_region, export_dir)
     return tracker.detected_events
+
+
+def _track(tracker, popped, by_window):
+    """One window's popped frames (oldest first) to the tracker: in one call where it is asked for and the tracker has one (anything
+    with the reference's step() alone is stepped per frame)."""
+    if by_window and hasattr(tracker, "step_window"):
+        tracker.step_window(popped)
+    else:
+        for frame in popped:
+            tracker.step(frame)
 
 
 def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, **kw):
@@ -178,11 +190,12 @@ def schedule_videos(readers, sizes, segment, consume, in_flight=4, windows_per_c
 
 
 def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows_per_call=1, classifier=None, queue_size=21,
-                        min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None):
+                        min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True):
     """count_swifts over a list of videos (the reference's loop over its video list, __main__.py:21), several videos at a time on one
     GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
     windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
     frames one by one in the reference's order, so every count and event list equals count_swifts on that video alone.
+    track_by_window: each tracker takes a window's frames in one library call (SegmentTracker.step_window); False steps per frame.
     videos: readers (read_frame / get_n_frames / total_frames), decoded frame arrays (oldest first) or what io_y4m.open_y4m opens (a
     .y4m path, "-", a FIFO, a descriptor, a binary file object); regions: per video
     (crop_region, roi_mask), or corners: per video the chimney's top edge (the regions then come from its first frame, :62-63).
@@ -192,13 +205,14 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
     opened = [r for r, v in zip(readers, videos) if r is not v and hasattr(r, "close")]          # (closed again when the count is done)
     try:
         return _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device,
-                             pad_factor, params)
+                             pad_factor, params, track_by_window)
     finally:
         for r in opened:
             r.close()
 
 
-def _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device, pad_factor, params):
+def _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device, pad_factor, params,
+                  track_by_window=True):
     """count_swifts_videos over readers."""
     if regions is None:
         if corners is None:
@@ -225,8 +239,7 @@ def _count_videos(readers, regions, corners, in_flight, windows_per_call, classi
 
     def consume(v, popped_lists):
         for popped in popped_lists:
-            for frame in popped:
-                trackers[v].step(frame)
+            _track(trackers[v], popped, track_by_window)
 
     schedule_videos(readers, sizes, segment, consume, in_flight=in_flight, windows_per_call=windows_per_call, queue_size=queue_size,
                     pad_factor=pad_factor)
