@@ -270,6 +270,66 @@ typedef struct swk_yuv {
 int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
                        uint8_t *bgr, int32_t bgr_mem);
 
+/* ---- review video: BGR -> 8-bit 4:2:0 YUV, with the overlay of a count drawn in ---------------------------------
+ * The reference shows what it counted with `--export`: one overlay PNG per segment (data_structures.py:65-113).  Here the
+ * ROI frames of a call leave as 4:2:0 video frames (what Y4MWriter stores and ffmpeg / mpv open) with the segments, the
+ * rejected segments, the events and the ROI mask drawn in; the overlay is this project's own definition.
+ *
+ * Source frames: `in` names them exactly as swk_batch_run reads them -- frame f = w * n + j at frames + f * frame_stride (may be
+ * negative), ROI pixel (r, c) at + (y0 + r) * row_stride + (x0 + c) * channels, host or device memory, channels 3 (BGR) or 1
+ * (gray, taken as B = G = R); of a host source only the ROI's rows and columns are copied to the device.  The `frame` fields
+ * of boxes and marks and the index of frame_style are this f.
+ *
+ * Composition, per pixel of frame f, in exact integers, with blend(p, col, a) = (p * (256 - a) + col * a + 128) >> 8 per channel;
+ * the layers apply in this order (the blends do not commute):
+ *   1. mask: where mask[r][c] != 0, blend with the colour and fill_alpha of style mask_style.
+ *   2. boxes of this frame, in array order: a pixel with r0 <= r < r1 and c0 <= c < c1 is blended once, with line_alpha if
+ *      r == r0 || r == r1 - 1 || c == c0 || c == c1 - 1, else with fill_alpha.  Boxes may leave the frame (they are clipped by the
+ *      pixel test alone: an edge outside the frame is not drawn); empty boxes draw nothing.
+ *   3. marks of this frame, in array order: the pixels (r + d, c) and (r, c + d), |d| <= mark_arm, that lie in the frame are
+ *      blended once each (the centre once) with line_alpha.
+ *   4. border: if frame_style[f] != 0, pixels with r < border || r >= Hc - border || c < border || c >= Wc - border are blended
+ *      with that style's line_alpha.
+ * Style k is styles[k - 1]; style 0 draws nothing.
+ *
+ * Conversion: cv2.cvtColor(bgr, COLOR_BGR2YUV_I420) of OpenCV 4.1.0 (requirements.txt:8) restated.  PARITY UNPINNED, like its
+ * inverse swk_yuv420_to_bgr (ITU-R BT.601, limited range, 20-bit fixed point, all in int32, arithmetic shift):
+ *   Y = ( 269484 R + 528482 G + 102760 B + (1 << 19) + (16  << 20)) >> 20
+ *   U = (-155188 R - 305135 G + 460324 B + (1 << 19) + (128 << 20)) >> 20
+ *   V = ( 460324 R - 385875 G -  74448 B + (1 << 19) + (128 << 20)) >> 20
+ * Y comes from every composed pixel; U and V of chroma cell (i, j) from the composed pixel (2 i, 2 j) alone, the cell's top-left
+ * pixel as 4.1.0 samples it (no averaging).  The chroma planes hold ceil(Hc / 2) x ceil(Wc / 2) samples, so odd sizes work and
+ * the sampled pixel always exists.  Over all 2^24 colours Y stays in 16..235 and U, V in 16..240: nothing saturates; converting
+ * back with swk_yuv420_to_bgr is off by at most 2 in B and R and 1 in G. */
+typedef struct swk_yuv420_dst {           /* 8-bit 4:2:0 destination of Hc x Wc pixel frames (in->Hc, in->Wc) */
+    uint8_t *y, *u, *v;                   /* NV12: u is the interleaved plane, v is not used */
+    int32_t mem;                          /* SWK_MEM_HOST / SWK_MEM_DEVICE */
+    int32_t layout;                       /* SWK_YUV_I420 / SWK_YUV_NV12 */
+    int64_t y_row_stride, y_frame_stride, c_row_stride, c_frame_stride;   /* bytes, row strides may exceed the row */
+} swk_yuv420_dst;
+
+typedef struct swk_review_style { uint8_t b, g, r, reserved_; int32_t fill_alpha, line_alpha; } swk_review_style;  /* alphas 0..256 */
+typedef struct swk_review_box   { int32_t frame, r0, c0, r1, c1, style; } swk_review_box;    /* half-open, like swk_segment */
+typedef struct swk_review_mark  { int32_t frame, r, c, style; } swk_review_mark;
+
+typedef struct swk_review {
+    const uint8_t *mask; int32_t mask_style;          /* host u8 [Hc][Wc] or NULL; pixels != 0 are tinted */
+    const swk_review_box *boxes;   int32_t nboxes;    /* ascending .frame */
+    const swk_review_mark *marks;  int32_t nmarks;    /* ascending .frame */
+    int32_t mark_arm;                                 /* plus sign: centre +- mark_arm pixels */
+    const int32_t *frame_style;    int32_t border;    /* [frames] or NULL; border thickness in pixels */
+    const swk_review_style *styles; int32_t nstyles;  /* style k = styles[k - 1]; style 0 draws nothing */
+} swk_review;
+
+/* The ROI of every frame of `in` as 4:2:0 frames in dst, converted (swk_bgr_to_yuv420) or composed with the overlay and then
+ * converted (swk_render_review; the former is the latter without drawing: one kernel).  rv, boxes, marks, styles, mask and
+ * frame_style are host memory.  SWK_ERR_ARG, before anything is launched and with dst untouched: a null plane the layout needs, a
+ * row stride below the row's bytes, an unknown layout or mem, an alpha outside 0..256, a style index outside 0..nstyles, a box or
+ * mark `frame` outside 0 .. nwin * n - 1, boxes or marks not in ascending `frame`, negative mark_arm or border, channels other
+ * than 1 or 3, an empty batch, a negative ROI origin.  SWK_ERR_CAPACITY: more than 2^24 frames, or an ROI side above 32768. */
+int32_t swk_bgr_to_yuv420(swk_ctx *ctx, const swk_input *in, swk_yuv420_dst *dst);
+int32_t swk_render_review(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv420_dst *dst);
+
 /* ---- stage-level entry points (host buffers; used by the parity tests and by the
  *      image_filtering.* drop-in functions) ------------------------------------- */
 /* convert_grayscale (image_filtering.py:188-196): [count][H][W][3] -> [count][H][W] */

@@ -1,12 +1,15 @@
 """python -m swiftwatcher_amd SOURCE [SOURCE ...] (--corners X1,Y1,X2,Y2 | --attributes FILE) [--start N] [--end N]
-       [--classify WEIGHTS] [--out DIR] [--windows-per-call K] [--device D]
+       [--classify WEIGHTS] [--out DIR] [--review PATH] [--windows-per-call K] [--device D]
 
 The reference's main() (__main__.py:13-53) without its UI: every SOURCE -- a .y4m file, or "-" for a YUV4MPEG2 stream on standard
 input (`ffmpeg -i evening.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners 812,640,1105,642`) -- is counted by
 pipeline.count_swifts, one after the other.  The chimney's corners come from --corners, from --attributes (a file in the format of
 the reference's attributes.json, ui.py:180-194), or, for a file, from <parent>/<stem>/attributes.json (:29-31).  Per source one JSON
 line goes to standard output: {"source", "frames", "events", "count"}; --out DIR gets the reference's result tables
-(io_data.export_results, :49-50; under DIR/<stem> when several sources are given)."""
+(io_data.export_results, :49-50; under DIR/<stem> when several sources are given).  --review PATH writes the review video of the
+count (review.py: the crop region as a 4:2:0 .y4m with segments, removed segments, ROI mask and events drawn in; PATH/<stem>.y4m when
+several sources are given).  PATH may be a FIFO (`--review fifo & ffmpeg -i fifo out.mp4`), not "-": standard output carries the
+JSON lines."""
 import argparse
 import json
 import os
@@ -35,6 +38,12 @@ def default_attributes(source):
     return os.path.join(os.path.dirname(os.path.abspath(source)), os.path.splitext(os.path.basename(source))[0], "attributes.json")
 
 
+def _review_path(text):
+    if text == "-":
+        raise argparse.ArgumentTypeError("standard output carries the JSON lines: give a file's or a FIFO's path")
+    return text
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m swiftwatcher_amd", description="Count chimney swifts in YUV4MPEG2 videos on the MI355X.")
     p.add_argument("sources", nargs="+", metavar="SOURCE", help="a .y4m file, or - for a YUV4MPEG2 stream on standard input")
@@ -45,6 +54,7 @@ def build_parser():
     p.add_argument("--end", type=int, default=0, metavar="N", help="frame count to stop at (0: the whole video)")
     p.add_argument("--classify", metavar="WEIGHTS", help="filter segments with the classifier of this state_dict file")
     p.add_argument("--out", metavar="DIR", help="write the result tables (CSV) here")
+    p.add_argument("--review", type=_review_path, metavar="PATH", help="write a review video (.y4m) of the count here")
     p.add_argument("--windows-per-call", type=int, default=1, metavar="K", help="queue-fuls segmented per GPU call")
     p.add_argument("--device", type=int, default=0, metavar="D", help="GPU index")
     return p
@@ -99,9 +109,14 @@ def main(argv=None):
         except (OSError, ValueError) as exc:
             print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)
             return 1
+        stem = "stdin" if source == "-" else os.path.splitext(os.path.basename(source))[0]
+        review = args.review
+        if review and len(jobs) > 1:
+            os.makedirs(review, exist_ok=True)
+            review = os.path.join(review, stem + ".y4m")
         try:
             count, events = pipeline.count_swifts(reader, corners=corners, classifier=classifier, device=args.device,
-                                                  windows_per_call=args.windows_per_call)
+                                                  windows_per_call=args.windows_per_call, review=review or None)
             frames, fps, first, last = reader.total_frames, reader.fps, reader.start_frame, reader.end_frame
         except (OSError, ValueError) as exc:
             print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)
@@ -110,7 +125,6 @@ def main(argv=None):
             if hasattr(reader, "close"):
                 reader.close()
         if args.out and events:                                                    # (__main__.py:40-50; without events there is no table)
-            stem = "stdin" if source == "-" else os.path.splitext(os.path.basename(source))[0]
             out_dir = args.out if len(jobs) == 1 else os.path.join(args.out, stem)
             with _stdout_to_stderr():                                              # (export_results prints its progress line)
                 export_results(out_dir, ec.classify_events(events), fps, first, last)

@@ -83,6 +83,30 @@ class Yuv(ctypes.Structure):
                                   ("msb_aligned", ctypes.c_int32), ("full_range", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
 
 
+class Yuv420Dst(ctypes.Structure):
+    _fields_ = [("y", ctypes.c_void_p), ("u", ctypes.c_void_p), ("v", ctypes.c_void_p), ("mem", ctypes.c_int32),
+                ("layout", ctypes.c_int32), ("y_row_stride", ctypes.c_int64), ("y_frame_stride", ctypes.c_int64),
+                ("c_row_stride", ctypes.c_int64), ("c_frame_stride", ctypes.c_int64)]
+
+
+class ReviewStyle(ctypes.Structure):
+    _fields_ = [("b", ctypes.c_uint8), ("g", ctypes.c_uint8), ("r", ctypes.c_uint8), ("reserved_", ctypes.c_uint8),
+                ("fill_alpha", ctypes.c_int32), ("line_alpha", ctypes.c_int32)]
+
+
+class Review(ctypes.Structure):
+    _fields_ = [("mask", ctypes.c_void_p), ("mask_style", ctypes.c_int32),
+                ("boxes", ctypes.c_void_p), ("nboxes", ctypes.c_int32),
+                ("marks", ctypes.c_void_p), ("nmarks", ctypes.c_int32), ("mark_arm", ctypes.c_int32),
+                ("frame_style", ctypes.c_void_p), ("border", ctypes.c_int32),
+                ("styles", ctypes.c_void_p), ("nstyles", ctypes.c_int32)]
+
+
+REVIEW_BOX_DTYPE = np.dtype([("frame", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("r1", "<i4"), ("c1", "<i4"), ("style", "<i4")])
+REVIEW_MARK_DTYPE = np.dtype([("frame", "<i4"), ("r", "<i4"), ("c", "<i4"), ("style", "<i4")])
+REVIEW_STYLE_DTYPE = np.dtype([("b", "u1"), ("g", "u1"), ("r", "u1"), ("reserved_", "u1"), ("fill_alpha", "<i4"), ("line_alpha", "<i4")])
+assert REVIEW_STYLE_DTYPE.itemsize == ctypes.sizeof(ReviewStyle) == 12 and REVIEW_BOX_DTYPE.itemsize == 24 and REVIEW_MARK_DTYPE.itemsize == 16
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -97,6 +121,8 @@ _SIGS = {
     "swk_batch_run_groups": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.c_int32, ctypes.POINTER(Params), ctypes.POINTER(Output)]),
     "swk_yuv420_to_bgr": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv420)] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int32]),
     "swk_yuv_to_bgr": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv)] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int32]),
+    "swk_bgr_to_yuv420": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Yuv420Dst)]),
+    "swk_render_review": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Review), ctypes.POINTER(Yuv420Dst)]),
     "swk_bgr2gray": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "swk_ialm": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_rpca_epilogue": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -701,6 +727,104 @@ class Context:
             optr, omem = _ptr(out), MEM_HOST
         self._check(self._lib.swk_yuv_to_bgr(self._h, ctypes.byref(src), count, int(x0), int(y0), int(Hr), int(Wr), optr, omem))
         return out[0] if single else out
+
+    # ---- review video ----
+    def _review_io(self, frames, rect, layout, device_out, dst):
+        """(Input, Yuv420Dst, result planes) of bgr_to_yuv420 / render_review.  frames: uint8 (F, H, W, 3) BGR or (F, H, W) gray, a
+        numpy array or a torch tensor on this context's GPU (read in place), contiguous along columns / channels, any row pitch and
+        frame stride.  dst: a ready Yuv420Dst (the planes are then the caller's business) or None."""
+        on_device = hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False)
+        shape = tuple(frames.shape)
+        if str(frames.dtype) != ("torch.uint8" if on_device else "uint8") or len(shape) not in (3, 4):
+            raise ValueError("frames must be uint8 (F, H, W[, C])")
+        if on_device:
+            strides, base = tuple(int(x) for x in frames.stride()), frames.data_ptr()
+        else:
+            strides, base = frames.strides, frames.ctypes.data
+        ch = 1 if len(shape) == 3 else shape[3]
+        if (len(shape) == 4 and (strides[3] != 1 or strides[2] != ch)) or (len(shape) == 3 and strides[2] != 1):
+            raise ValueError("frames must be contiguous along columns/channels")
+        F, H, W = shape[:3]
+        x0, y0, Wc, Hc = rect if rect is not None else (0, 0, W, H)
+        if x0 < 0 or y0 < 0 or x0 + Wc > W or y0 + Hc > H:
+            raise ValueError("rectangle outside the frame")
+        inp = Input(frames=base, mem=MEM_DEVICE if on_device else MEM_HOST, channels=ch, nwin=1, n=F, Hc=Hc, Wc=Wc, x0=x0, y0=y0,
+                    frame_stride=strides[0], row_stride=strides[1])
+        if dst is not None:
+            return inp, dst, None
+        if layout not in ("i420", "nv12"):
+            raise ValueError('layout is "i420" or "nv12"')
+        Fa, Ha, Wa = max(F, 1), max(Hc, 1), max(Wc, 1)               # (the library refuses empty ones)
+        hc, wc = (Ha + 1) // 2, (Wa + 1) // 2
+        cshape = (Fa, hc, wc) if layout == "i420" else (Fa, hc, wc, 2)
+        nplanes = 3 if layout == "i420" else 2
+        if device_out:
+            import torch
+            planes = [torch.empty(sh, dtype=torch.uint8, device="cuda:%d" % self.device) for sh in [(Fa, Ha, Wa)] + [cshape] * (nplanes - 1)]
+            ptrs = [p.data_ptr() for p in planes]
+        else:
+            planes = [np.empty(sh, np.uint8) for sh in [(Fa, Ha, Wa)] + [cshape] * (nplanes - 1)]
+            ptrs = [p.ctypes.data for p in planes]
+        crow = wc * (1 if layout == "i420" else 2)
+        dst = Yuv420Dst(y=ptrs[0], u=ptrs[1], v=ptrs[2] if nplanes == 3 else None, mem=MEM_DEVICE if device_out else MEM_HOST,
+                        layout=YUV_I420 if layout == "i420" else YUV_NV12, y_row_stride=Wa, y_frame_stride=Ha * Wa,
+                        c_row_stride=crow, c_frame_stride=hc * crow)
+        return inp, dst, tuple(planes)
+
+    def bgr_to_yuv420(self, frames, rect=None, layout="i420", device_out=False, dst=None):
+        """swk_bgr_to_yuv420: BGR (F, H, W, 3) or gray (F, H, W) uint8 frames -> 8-bit 4:2:0 (cv2.cvtColor COLOR_BGR2YUV_I420 of OpenCV
+        4.1.0 restated, include/swk.h; chroma from each cell's top-left pixel).  frames: a numpy array or a torch tensor on this
+        context's GPU.  rect: (x0, y0, Wr, Hr) inside the frame, None = the whole frame.  Returns (y, u, v) for layout "i420" --
+        y (F, Hr, Wr), u and v (F, ceil(Hr / 2), ceil(Wr / 2)) -- or (y, uv) for "nv12", uv (F, ceil(Hr / 2), ceil(Wr / 2), 2): numpy
+        arrays, or with device_out=True torch uint8 tensors on the GPU.  dst: a Yuv420Dst of the caller's (any strides, host or
+        device); nothing is returned then."""
+        inp, dst, planes = self._review_io(frames, rect, layout, device_out, dst)
+        self._check(self._lib.swk_bgr_to_yuv420(self._h, ctypes.byref(inp), ctypes.byref(dst)))
+        return planes
+
+    def render_review(self, frames, boxes=None, marks=None, frame_style=None, mask=None, styles=None, mask_style=0, mark_arm=0, border=0,
+                      rect=None, layout="i420", device_out=False, dst=None):
+        """swk_render_review: bgr_to_yuv420 of the frames composed with an overlay (include/swk.h): boxes -- REVIEW_BOX_DTYPE records
+        or rows (frame, r0, c0, r1, c1, style), ascending frame --, marks -- REVIEW_MARK_DTYPE records or rows (frame, r, c, style),
+        ascending frame --, frame_style (F,) int32 border style per frame, mask (Hr, Wr) uint8 tinted in mask_style where != 0, styles
+        -- REVIEW_STYLE_DTYPE records or rows (b, g, r, fill_alpha, line_alpha); style k is styles[k - 1], 0 draws nothing."""
+        def records(a, dtype, cols):
+            if a is None:
+                return np.zeros(0, dtype)
+            if isinstance(a, np.ndarray) and a.dtype == dtype:
+                return np.ascontiguousarray(a)
+            rows = np.asarray(a, dtype=np.int64).reshape(-1, len(cols))
+            out = np.zeros(len(rows), dtype)
+            for k, name in enumerate(cols):
+                out[name] = rows[:, k]
+            return out
+        boxes = records(boxes, REVIEW_BOX_DTYPE, ("frame", "r0", "c0", "r1", "c1", "style"))
+        marks = records(marks, REVIEW_MARK_DTYPE, ("frame", "r", "c", "style"))
+        if isinstance(styles, np.ndarray) and styles.dtype == REVIEW_STYLE_DTYPE:
+            styles = np.ascontiguousarray(styles)
+        else:
+            rows = np.asarray(styles if styles is not None else [], dtype=np.int64).reshape(-1, 5)
+            if rows.size and (rows[:, :3].min() < 0 or rows[:, :3].max() > 255):
+                raise ValueError("a style's colour is three bytes (b, g, r)")
+            styles = np.zeros(len(rows), REVIEW_STYLE_DTYPE)
+            for k, name in enumerate(("b", "g", "r", "fill_alpha", "line_alpha")):
+                styles[name] = rows[:, k]
+        inp, dst, planes = self._review_io(frames, rect, layout, device_out, dst)
+        if frame_style is not None:
+            frame_style = np.ascontiguousarray(frame_style, np.int32)
+            if frame_style.shape != (inp.n,):
+                raise ValueError("frame_style holds one style per frame")
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8)
+            if mask.shape != (inp.Hc, inp.Wc):
+                raise ValueError("mask must be (Hr, Wr)")
+        rv = Review(mask=mask.ctypes.data if mask is not None else None, mask_style=int(mask_style),
+                    boxes=boxes.ctypes.data if len(boxes) else None, nboxes=len(boxes),
+                    marks=marks.ctypes.data if len(marks) else None, nmarks=len(marks), mark_arm=int(mark_arm),
+                    frame_style=frame_style.ctypes.data if frame_style is not None else None, border=int(border),
+                    styles=styles.ctypes.data if len(styles) else None, nstyles=len(styles))
+        self._check(self._lib.swk_render_review(self._h, ctypes.byref(inp), ctypes.byref(rv), ctypes.byref(dst)))
+        return planes
 
     # ---- stage-level entry points ----
     def bgr2gray(self, bgr, gray_mode=GRAY_Q14):

@@ -1,0 +1,243 @@
+// Review video on gfx950: BGR (or gray) ROI frames -> 8-bit 4:2:0 YUV, with the overlay of a count drawn in on the way
+// (swk_render_review, swk_bgr_to_yuv420; include/swk.h has the definition).
+//
+// Composition per pixel, exact integers, blend(p, col, a) = (p * (256 - a) + col * a + 128) >> 8 per channel, in this order:
+// ROI mask tint, the frame's boxes in array order (edge pixels with the style's line alpha, inner pixels with its fill alpha),
+// the frame's marks in array order (plus signs, line alpha), the frame's border (line alpha).  Then BGR -> YUV, OpenCV 4.1.0's
+// COLOR_BGR2YUV_I420 restated (BT.601 limited range, 20-bit fixed point, int32; PARITY UNPINNED like its inverse in yuv.hip):
+//   Y = ( 269484 R + 528482 G + 102760 B + (1 << 19) + (16  << 20)) >> 20
+//   U = (-155188 R - 305135 G + 460324 B + (1 << 19) + (128 << 20)) >> 20
+//   V = ( 460324 R - 385875 G -  74448 B + (1 << 19) + (128 << 20)) >> 20
+// Y of every composed pixel; U and V of chroma cell (i, j) from the composed pixel (2 i, 2 j) alone (no averaging); no value
+// leaves 16..235 / 16..240, so nothing saturates.
+//
+// A byte-streaming kernel: 3 B read and 1.5 B written per pixel.  One thread owns a strip of 8 x 2 pixels (four whole 2 x 2
+// cells): two 24-byte runs of source pixels in, two 8-byte luma runs and four chroma samples per plane (I420) or four (U, V) pairs
+// (NV12) out, each run as the widest accesses its address allows (8, 4, 2 bytes, else bytes), so consecutive lanes stay on
+// consecutive addresses whatever the ROI's origin, the strides and the sizes' parity.  blockIdx.y is the frame: a workgroup reads
+// its frame's boxes and marks, style already resolved by the host, into LDS in chunks of kChunk, so a frame may carry any number;
+// a strip tests a box's rectangle once and walks its 16 pixels only where they meet.
+#include "swk_internal.h"
+
+namespace swk {
+
+namespace {
+
+constexpr int kChunk = 128;
+constexpr int kYR = 269484, kYG = 528482, kYB = 102760, kUR = -155188, kUG = -305135, kUB = 460324, kVR = 460324, kVG = -385875,
+              kVB = -74448;
+
+__device__ __forceinline__ int blend1(int p, int col, int a) { return (p * (256 - a) + col * a + 128) >> 8; }
+
+__device__ __forceinline__ void blend3(int (&px)[3], uint32_t colour, int a)
+{
+    px[0] = blend1(px[0], (int)(colour & 255u), a);
+    px[1] = blend1(px[1], (int)((colour >> 8) & 255u), a);
+    px[2] = blend1(px[2], (int)((colour >> 16) & 255u), a);
+}
+
+// n <= 8 bytes of w (w[0] = bytes 0..3) to p, with the widest stores the address allows
+__device__ __forceinline__ void store_run8(uint8_t *p, uint32_t w0, uint32_t w1, int n)
+{
+    if (n == 8) {
+        const uintptr_t a = (uintptr_t)p;
+        if ((a & 7) == 0) { *(uint2 *)p = make_uint2(w0, w1); return; }
+        if ((a & 3) == 0) { ((uint32_t *)p)[0] = w0; ((uint32_t *)p)[1] = w1; return; }
+        if ((a & 1) == 0) {
+            uint16_t *q = (uint16_t *)p;
+            q[0] = (uint16_t)w0; q[1] = (uint16_t)(w0 >> 16); q[2] = (uint16_t)w1; q[3] = (uint16_t)(w1 >> 16);
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+        if (k < n) p[k] = (uint8_t)((k < 4 ? w0 >> (8 * k) : w1 >> (8 * (k - 4))) & 255u);
+}
+
+__device__ __forceinline__ void store_run4(uint8_t *p, uint32_t w, int n)
+{
+    if (n == 4) {
+        const uintptr_t a = (uintptr_t)p;
+        if ((a & 3) == 0) { *(uint32_t *)p = w; return; }
+        if ((a & 1) == 0) { ((uint16_t *)p)[0] = (uint16_t)w; ((uint16_t *)p)[1] = (uint16_t)(w >> 16); return; }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k < n) p[k] = (uint8_t)((w >> (8 * k)) & 255u);
+}
+
+}  // namespace
+
+template <bool DRAW>
+__global__ __launch_bounds__(256) void k_review(ReviewArgs a, int f0)
+{
+    __shared__ int32_t lds[kChunk * 6];
+    const int f = f0 + (int)blockIdx.y;
+    const int sw = (a.Wc + 7) >> 3, sh = (a.Hc + 1) >> 1;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = idx < sw * sh;
+    const int sr = live ? idx / sw : 0, sc = live ? idx - sr * sw : 0;
+    const int r0 = 2 * sr, c0 = 8 * sc;                                  // the strip's first pixel: even row, column a multiple of 8
+    const int ncol = !live ? 0 : (a.Wc - c0 < 8 ? a.Wc - c0 : 8);
+    const int nrow = !live ? 0 : (a.Hc - r0 < 2 ? a.Hc - r0 : 2);
+
+    // ---- source pixels: two runs of ncol pixels
+    int px[16][3];
+#pragma unroll
+    for (int dr = 0; dr < 2; ++dr) {
+        const uint8_t *s = a.src + (int64_t)f * a.fs + (int64_t)(a.y0 + r0 + dr) * a.rs + (int64_t)(a.x0 + c0) * a.channels;
+        if (dr >= nrow) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) px[8 * dr + k][0] = px[8 * dr + k][1] = px[8 * dr + k][2] = 0;
+        } else if (a.channels == 3) {
+            if (ncol == 8 && ((uintptr_t)s & 3) == 0) {
+                uint32_t w[6];
+                if (((uintptr_t)s & 7) == 0) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) { const uint2 q = ((const uint2 *)s)[k]; w[2 * k] = q.x; w[2 * k + 1] = q.y; }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) w[k] = ((const uint32_t *)s)[k];
+                }
+#pragma unroll
+                for (int k = 0; k < 24; ++k) px[8 * dr + k / 3][k % 3] = (int)((w[k >> 2] >> (8 * (k & 3))) & 255u);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 24; ++k) px[8 * dr + k / 3][k % 3] = k / 3 < ncol ? (int)s[k] : 0;
+            }
+        } else {
+            if (ncol == 8 && ((uintptr_t)s & 3) == 0) {
+                const uint32_t w0 = ((const uint32_t *)s)[0], w1 = ((const uint32_t *)s)[1];
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    px[8 * dr + k][0] = px[8 * dr + k][1] = px[8 * dr + k][2] = (int)(((k < 4 ? w0 : w1) >> (8 * (k & 3))) & 255u);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) px[8 * dr + k][0] = px[8 * dr + k][1] = px[8 * dr + k][2] = k < ncol ? (int)s[k] : 0;
+            }
+        }
+    }
+
+    if (DRAW) {
+        // ---- 1. the ROI mask
+        if (a.mask && a.mask_alpha != 0) {
+#pragma unroll
+            for (int dr = 0; dr < 2; ++dr) {
+                if (dr < nrow) {
+                    const uint8_t *m = a.mask + (int64_t)(r0 + dr) * a.Wc + c0;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (k < ncol && m[k] != 0) blend3(px[8 * dr + k], a.mask_colour, a.mask_alpha);
+                }
+            }
+        }
+        // ---- 2. the frame's boxes, in array order: LDS entries (r0, c0, r1, c1, colour, fill alpha | line alpha << 16)
+        const int b_begin = a.box_start[f], b_end = a.box_start[f + 1];
+        for (int base = b_begin; base < b_end; base += kChunk) {
+            const int cnt = b_end - base < kChunk ? b_end - base : kChunk;
+            __syncthreads();
+            for (int k = threadIdx.x; k < cnt * 6; k += blockDim.x) lds[k] = a.boxes[(int64_t)base * 6 + k];
+            __syncthreads();
+            for (int b = 0; b < cnt; ++b) {
+                const int br0 = lds[6 * b], bc0 = lds[6 * b + 1], br1 = lds[6 * b + 2], bc1 = lds[6 * b + 3];
+                if (!live || br0 >= r0 + nrow || br1 <= r0 || bc0 >= c0 + ncol || bc1 <= c0) continue;
+                const uint32_t colour = (uint32_t)lds[6 * b + 4];
+                const int fill = lds[6 * b + 5] & 0xffff, line = lds[6 * b + 5] >> 16;
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int r = r0 + (k >> 3), c = c0 + (k & 7);
+                    if (r >= br0 && r < br1 && c >= bc0 && c < bc1) {
+                        const bool edge = r == br0 || r == br1 - 1 || c == bc0 || c == bc1 - 1;
+                        blend3(px[k], colour, edge ? line : fill);
+                    }
+                }
+            }
+        }
+        // ---- 3. the frame's marks, in array order: LDS entries (r, c, colour, line alpha)
+        const int m_begin = a.mark_start[f], m_end = a.mark_start[f + 1];
+        for (int base = m_begin; base < m_end; base += kChunk) {
+            const int cnt = m_end - base < kChunk ? m_end - base : kChunk;
+            __syncthreads();
+            for (int k = threadIdx.x; k < cnt * 4; k += blockDim.x) lds[k] = a.marks[(int64_t)base * 4 + k];
+            __syncthreads();
+            for (int m = 0; m < cnt; ++m) {
+                const int64_t mr = lds[4 * m], mc = lds[4 * m + 1], arm = a.mark_arm;
+                // the strip meets the vertical or the horizontal bar?
+                const bool vbar = mc >= c0 && mc < c0 + ncol && mr + arm >= r0 && mr - arm < r0 + nrow;
+                const bool hbar = mr >= r0 && mr < r0 + nrow && mc + arm >= c0 && mc - arm < c0 + ncol;
+                if (!live || (!vbar && !hbar)) continue;
+                const uint32_t colour = (uint32_t)lds[4 * m + 2];
+                const int line = lds[4 * m + 3];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int64_t r = r0 + (k >> 3), c = c0 + (k & 7);
+                    const int64_t dr = r > mr ? r - mr : mr - r, dc = c > mc ? c - mc : mc - c;
+                    if ((c == mc && dr <= arm) || (r == mr && dc <= arm)) blend3(px[k], colour, line);
+                }
+            }
+        }
+        // ---- 4. the frame's border: (colour, line alpha) per frame, alpha < 0 = none
+        if (a.frame_border) {
+            const uint32_t colour = (uint32_t)a.frame_border[2 * (int64_t)f];
+            const int line = a.frame_border[2 * (int64_t)f + 1];
+            if (line >= 0 && a.border > 0) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int r = r0 + (k >> 3), c = c0 + (k & 7);
+                    if (r < a.border || r >= a.Hc - a.border || c < a.border || c >= a.Wc - a.border) blend3(px[k], colour, line);
+                }
+            }
+        }
+    }
+    if (!live) return;
+
+    // ---- conversion and stores
+    constexpr int h = 1 << 19;
+#pragma unroll
+    for (int dr = 0; dr < 2; ++dr) {
+        if (dr < nrow) {
+            uint32_t w[2] = {0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int *p = px[8 * dr + k];
+                const int Y = (kYR * p[2] + kYG * p[1] + kYB * p[0] + h + (16 << 20)) >> 20;
+                w[k >> 2] |= (uint32_t)Y << (8 * (k & 3));
+            }
+            store_run8(a.y + (int64_t)f * a.y_fs + (int64_t)(r0 + dr) * a.y_rs + c0, w[0], w[1], ncol);
+        }
+    }
+    const int ncell = (ncol + 1) >> 1;
+    uint32_t uw = 0u, vw = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int *p = px[2 * k];                                        // pixel (2 i, 2 j): the cell's top-left
+        const int U = (kUR * p[2] + kUG * p[1] + kUB * p[0] + h + (128 << 20)) >> 20;
+        const int V = (kVR * p[2] + kVG * p[1] + kVB * p[0] + h + (128 << 20)) >> 20;
+        uw |= (uint32_t)U << (8 * k);
+        vw |= (uint32_t)V << (8 * k);
+    }
+    const int64_t crow = (int64_t)f * a.c_fs + (int64_t)sr * a.c_rs;
+    if (a.layout == SWK_YUV_I420) {
+        store_run4(a.u + crow + 4 * sc, uw, ncell);
+        store_run4(a.v + crow + 4 * sc, vw, ncell);
+    } else {
+        const uint32_t lo = (uw & 255u) | ((vw & 255u) << 8) | (((uw >> 8) & 255u) << 16) | (((vw >> 8) & 255u) << 24);
+        const uint32_t hi = ((uw >> 16) & 255u) | (((vw >> 16) & 255u) << 8) | ((uw >> 24) << 16) | ((vw >> 24) << 24);
+        store_run8(a.u + crow + 8 * sc, lo, hi, 2 * ncell);
+    }
+}
+
+void launch_review(hipStream_t s, const ReviewArgs &a, int F, bool draw)
+{
+    const int strips = ((a.Wc + 7) >> 3) * ((a.Hc + 1) >> 1);
+    // grid.y is limited to 65535: split the frame range
+    for (int f0 = 0; f0 < F; f0 += 32768) {
+        const int fc = F - f0 < 32768 ? F - f0 : 32768;
+        const dim3 grid((strips + 255) / 256, fc);
+        if (draw) hipLaunchKernelGGL(k_review<true>, grid, dim3(256), 0, s, a, f0);
+        else hipLaunchKernelGGL(k_review<false>, grid, dim3(256), 0, s, a, f0);
+        note_launch();
+    }
+}
+
+}  // namespace swk

@@ -23,7 +23,7 @@ enum Slot {
     SL_ROI = 0, SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8, SL_LAB32, SL_A, SL_Y, SL_E, SL_PN,
     SL_BM, SL_VPREV, SL_GPART, SL_ZZPART, SL_WIN, SL_ACTIVE, SL_PARENT, SL_ROOTBITS, SL_WORDPREFIX,
     SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_TMP_IN, SL_TMP_OUT, SL_TMP_AUX, SL_COLORW, SL_SPACEW,
-    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_SEGLARGE, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_COUNT
+    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_SEGLARGE, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_REVIEW, SL_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int fam; };
@@ -1468,6 +1468,188 @@ int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t 
     }
     if (bgr_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(bgr, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
+}
+
+// ---- review video (review.hip): the ROI of a call's frames, composed with the overlay, as 8-bit 4:2:0 -----------------------------
+namespace {
+
+// plane rows of `count` device frames (dense: rows x width bytes each) to a host plane with its own strides
+int download_rects(swk_ctx *ctx, uint8_t *dst, int64_t rs, int64_t fs, const uint8_t *src, size_t width, size_t rows, int count)
+{
+    const size_t per = width * rows;
+    if ((size_t)rs == width && (count == 1 || fs == (int64_t)per)) {
+        HIPCHK(ctx, hipMemcpyAsync(dst, src, per * count, hipMemcpyDeviceToHost, ctx->stream));
+        return SWK_OK;
+    }
+    for (int f = 0; f < count; ++f) {
+        uint8_t *d = dst + (int64_t)f * fs;
+        if ((size_t)rs == width) HIPCHK(ctx, hipMemcpyAsync(d, src + (size_t)f * per, per, hipMemcpyDeviceToHost, ctx->stream));
+        else HIPCHK(ctx, hipMemcpy2DAsync(d, (size_t)rs, src + (size_t)f * per, width, width, rows, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return SWK_OK;
+}
+
+int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv420_dst *dst)
+{
+    if (!in || !dst) return fail(ctx, SWK_ERR_ARG, "null argument");
+    // ---- every refusal comes before anything is copied or launched
+    if (!in->frames) return fail(ctx, SWK_ERR_ARG, "null frames");
+    if (in->nwin < 1 || in->n < 1 || in->Hc < 1 || in->Wc < 1) return fail(ctx, SWK_ERR_ARG, "empty batch");
+    if (in->channels != 1 && in->channels != 3) return fail(ctx, SWK_ERR_ARG, "channels must be 1 or 3");
+    if ((in->mem != SWK_MEM_HOST && in->mem != SWK_MEM_DEVICE) || (dst->mem != SWK_MEM_HOST && dst->mem != SWK_MEM_DEVICE))
+        return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
+    if (in->x0 < 0 || in->y0 < 0) return fail(ctx, SWK_ERR_ARG, "negative ROI origin");
+    if ((int64_t)in->nwin * in->n > (1 << 24)) return fail(ctx, SWK_ERR_CAPACITY, "too many frames in one call (2^24 at most)");
+    if (in->Hc > 32768 || in->Wc > 32768) return fail(ctx, SWK_ERR_CAPACITY, "ROI side above 32768");
+    const int F = in->nwin * in->n, Hc = in->Hc, Wc = in->Wc, ch = (Hc + 1) / 2, cw = (Wc + 1) / 2;
+    if (in->row_stride < ((int64_t)in->x0 + Wc) * in->channels) return fail(ctx, SWK_ERR_ARG, "source row stride smaller than the ROI's row");
+    if (dst->layout != SWK_YUV_I420 && dst->layout != SWK_YUV_NV12) return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_I420 or SWK_YUV_NV12)");
+    const bool nv12 = dst->layout == SWK_YUV_NV12;
+    const int cbytes = nv12 ? 2 : 1;
+    if (!dst->y || !dst->u || (!nv12 && !dst->v)) return fail(ctx, SWK_ERR_ARG, "null YUV plane");
+    if (dst->y_row_stride < Wc || dst->c_row_stride < (int64_t)cw * cbytes) return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
+    std::vector<int32_t> meta;
+    size_t o_boxes = 0, o_bstart = 0, o_marks = 0, o_mstart = 0, o_border = 0, o_mask = 0;
+    uint32_t mask_colour = 0; int mask_alpha = 0;
+    if (rv) {
+        if (rv->nstyles < 0 || (rv->nstyles > 0 && !rv->styles)) return fail(ctx, SWK_ERR_ARG, "styles");
+        if (rv->nboxes < 0 || rv->nmarks < 0 || (rv->nboxes > 0 && !rv->boxes) || (rv->nmarks > 0 && !rv->marks))
+            return fail(ctx, SWK_ERR_ARG, "a null array with a non-zero count, or a negative count");
+        if (rv->mark_arm < 0 || rv->border < 0) return fail(ctx, SWK_ERR_ARG, "negative mark_arm or border");
+        for (int k = 0; k < rv->nstyles; ++k)
+            if (rv->styles[k].fill_alpha < 0 || rv->styles[k].fill_alpha > 256 || rv->styles[k].line_alpha < 0 || rv->styles[k].line_alpha > 256)
+                return fail(ctx, SWK_ERR_ARG, "an alpha outside 0..256");
+        auto bad_style = [&](int st) { return st < 0 || st > rv->nstyles; };
+        auto colour = [&](int st) { const swk_review_style &y = rv->styles[st - 1]; return (uint32_t)y.b | ((uint32_t)y.g << 8) | ((uint32_t)y.r << 16); };
+        if (bad_style(rv->mask_style)) return fail(ctx, SWK_ERR_ARG, "mask style outside 0..nstyles");
+        int prev = 0;
+        for (int k = 0; k < rv->nboxes; ++k) {
+            const swk_review_box &b = rv->boxes[k];
+            if (b.frame < 0 || b.frame >= F) return fail(ctx, SWK_ERR_ARG, "a box's frame outside the call's frames");
+            if (b.frame < prev) return fail(ctx, SWK_ERR_ARG, "boxes not in ascending frame order");
+            if (bad_style(b.style)) return fail(ctx, SWK_ERR_ARG, "a box's style outside 0..nstyles");
+            prev = b.frame;
+        }
+        prev = 0;
+        for (int k = 0; k < rv->nmarks; ++k) {
+            const swk_review_mark &m = rv->marks[k];
+            if (m.frame < 0 || m.frame >= F) return fail(ctx, SWK_ERR_ARG, "a mark's frame outside the call's frames");
+            if (m.frame < prev) return fail(ctx, SWK_ERR_ARG, "marks not in ascending frame order");
+            if (bad_style(m.style)) return fail(ctx, SWK_ERR_ARG, "a mark's style outside 0..nstyles");
+            prev = m.frame;
+        }
+        if (rv->frame_style)
+            for (int f = 0; f < F; ++f)
+                if (bad_style(rv->frame_style[f])) return fail(ctx, SWK_ERR_ARG, "a frame's border style outside 0..nstyles");
+        // ---- the kernel's tables, styles resolved, in one block of int32 (launch_review, swk_internal.h)
+        o_boxes = 0;
+        meta.resize((size_t)rv->nboxes * 6);
+        for (int k = 0; k < rv->nboxes; ++k) {
+            const swk_review_box &b = rv->boxes[k];
+            int32_t *e = &meta[(size_t)k * 6];
+            e[0] = b.r0; e[1] = b.c0; e[2] = b.r1; e[3] = b.c1; e[4] = 0; e[5] = 0;
+            if (b.style == 0) { e[2] = b.r0; continue; }                  // style 0 draws nothing: an empty box
+            e[4] = (int32_t)colour(b.style);
+            e[5] = rv->styles[b.style - 1].fill_alpha | (rv->styles[b.style - 1].line_alpha << 16);
+        }
+        o_bstart = meta.size();
+        meta.resize(o_bstart + F + 1, 0);
+        for (int k = 0; k < rv->nboxes; ++k) meta[o_bstart + rv->boxes[k].frame + 1] += 1;
+        for (int f = 0; f < F; ++f) meta[o_bstart + f + 1] += meta[o_bstart + f];
+        o_marks = meta.size();
+        meta.resize(o_marks + (size_t)rv->nmarks * 4);
+        for (int k = 0; k < rv->nmarks; ++k) {
+            const swk_review_mark &m = rv->marks[k];
+            int32_t *e = &meta[o_marks + (size_t)k * 4];
+            e[0] = m.r; e[1] = m.c;
+            e[2] = m.style ? (int32_t)colour(m.style) : 0;
+            e[3] = m.style ? rv->styles[m.style - 1].line_alpha : 0;   // (alpha 0 is the identity)
+        }
+        o_mstart = meta.size();
+        meta.resize(o_mstart + F + 1, 0);
+        for (int k = 0; k < rv->nmarks; ++k) meta[o_mstart + rv->marks[k].frame + 1] += 1;
+        for (int f = 0; f < F; ++f) meta[o_mstart + f + 1] += meta[o_mstart + f];
+        o_border = meta.size();
+        if (rv->frame_style) {
+            meta.resize(o_border + (size_t)F * 2);
+            for (int f = 0; f < F; ++f) {
+                const int st = rv->frame_style[f];
+                meta[o_border + 2 * (size_t)f] = st ? (int32_t)colour(st) : 0;
+                meta[o_border + 2 * (size_t)f + 1] = st ? rv->styles[st - 1].line_alpha : -1;
+            }
+        }
+        o_mask = meta.size();
+        if (rv->mask && rv->mask_style) {
+            meta.resize(o_mask + ((size_t)Hc * Wc + 3) / 4);
+            memcpy(&meta[o_mask], rv->mask, (size_t)Hc * Wc);
+            mask_colour = colour(rv->mask_style);
+            mask_alpha = rv->styles[rv->mask_style - 1].fill_alpha;
+        }
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ReviewArgs a{};
+    a.src = in->frames; a.fs = in->frame_stride; a.rs = in->row_stride; a.x0 = in->x0; a.y0 = in->y0;
+    a.Hc = Hc; a.Wc = Wc; a.channels = in->channels; a.layout = dst->layout;
+    if (in->mem == SWK_MEM_HOST) {
+        // the ROI alone, densely
+        const size_t rowb = (size_t)Wc * in->channels;
+        uint8_t *din;
+        NEED(ctx, SL_TMP_IN, (size_t)F * Hc * rowb, din);
+        const int rc = upload_rects(ctx, din, in->frames + (int64_t)in->y0 * in->row_stride + (int64_t)in->x0 * in->channels, in->row_stride,
+                                    in->frame_stride, rowb, (size_t)Hc, F);
+        if (rc) return rc;
+        a.src = din; a.fs = (int64_t)Hc * rowb; a.rs = (int64_t)rowb; a.x0 = a.y0 = 0;
+    }
+    const size_t yb = ((size_t)F * Hc * Wc + 15) & ~(size_t)15, cb = ((size_t)F * ch * cw * cbytes + 15) & ~(size_t)15;
+    if (dst->mem == SWK_MEM_HOST) {
+        uint8_t *dout;
+        NEED(ctx, SL_TMP_OUT, yb + cb * (nv12 ? 1 : 2), dout);
+        a.y = dout; a.u = dout + yb; a.v = nv12 ? nullptr : dout + yb + cb;
+        a.y_rs = Wc; a.y_fs = (int64_t)Hc * Wc; a.c_rs = (int64_t)cw * cbytes; a.c_fs = (int64_t)ch * a.c_rs;
+    } else {
+        a.y = dst->y; a.u = dst->u; a.v = nv12 ? nullptr : dst->v;
+        a.y_rs = dst->y_row_stride; a.y_fs = dst->y_frame_stride; a.c_rs = dst->c_row_stride; a.c_fs = dst->c_frame_stride;
+    }
+    if (rv) {
+        int32_t *dmeta;
+        NEED(ctx, SL_REVIEW, meta.size() * 4, dmeta);
+        if (!meta.empty()) HIPCHK(ctx, hipMemcpyAsync(dmeta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        a.boxes = dmeta + o_boxes; a.box_start = dmeta + o_bstart; a.marks = dmeta + o_marks; a.mark_start = dmeta + o_mstart;
+        a.frame_border = rv->frame_style ? dmeta + o_border : nullptr;
+        a.mask = mask_alpha ? (const uint8_t *)(dmeta + o_mask) : nullptr;
+        a.mask_colour = mask_colour; a.mask_alpha = mask_alpha;
+        a.mark_arm = rv->mark_arm; a.border = rv->border;
+    }
+    {
+        Timed t(ctx, SWK_K_GRAY);
+        launch_review(ctx->stream, a, F, rv != nullptr);
+    }
+    if (dst->mem == SWK_MEM_HOST) {
+        int rc = download_rects(ctx, dst->y, dst->y_row_stride, dst->y_frame_stride, a.y, (size_t)Wc, (size_t)Hc, F);
+        if (rc) return rc;
+        rc = download_rects(ctx, dst->u, dst->c_row_stride, dst->c_frame_stride, a.u, (size_t)cw * cbytes, (size_t)ch, F);
+        if (rc) return rc;
+        if (!nv12) {
+            rc = download_rects(ctx, dst->v, dst->c_row_stride, dst->c_frame_stride, a.v, (size_t)cw, (size_t)ch, F);
+            if (rc) return rc;
+        }
+    }
+    return sync(ctx);            // (meta lives on this stack frame)
+}
+
+}  // namespace
+
+int32_t swk_bgr_to_yuv420(swk_ctx *ctx, const swk_input *in, swk_yuv420_dst *dst)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    return review_call(ctx, in, nullptr, dst);
+}
+
+int32_t swk_render_review(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv420_dst *dst)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!rv) return fail(ctx, SWK_ERR_ARG, "null argument");
+    return review_call(ctx, in, rv, dst);
 }
 
 int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, double lmbda, double tol, int32_t maxiter,

@@ -169,6 +169,25 @@ void launch_yuv_to_bgr(hipStream_t s, int layout, int sx, int sy, int bits, int 
                        const uint8_t *u, const uint8_t *v, int64_t y_fs, int64_t y_rs, int64_t c_fs, int64_t c_rs, int x0, int y0, int F,
                        int Hr, int Wr, uint8_t *out);
 
+// review.hip: F source frames' ROI (frame f at src + f * fs, ROI pixel (r, c) at + (y0 + r) * rs + (x0 + c) * channels; device memory)
+// composed with the review overlay and converted to 8-bit 4:2:0 in device memory (include/swk.h, swk_render_review).  The host
+// resolves styles: boxes [nboxes][6] = (r0, c0, r1, c1, colour b | g << 8 | r << 16, fill alpha | line alpha << 16) with
+// box_start [F + 1] the first box of every frame, marks [nmarks][4] = (r, c, colour, line alpha) with mark_start [F + 1],
+// frame_border [F][2] = (colour, line alpha or -1 for none) or null.  draw = false: the conversion alone (nothing but the source, the
+// geometry and the destination is read).
+struct ReviewArgs {
+    const uint8_t *src;
+    int64_t fs, rs;
+    int x0, y0, Hc, Wc, channels, layout;
+    uint8_t *y, *u, *v;
+    int64_t y_fs, y_rs, c_fs, c_rs;
+    const uint8_t *mask;               // [Hc][Wc] or null
+    uint32_t mask_colour; int mask_alpha;
+    const int32_t *boxes, *box_start, *marks, *mark_start, *frame_border;
+    int mark_arm, border;
+};
+void launch_review(hipStream_t s, const ReviewArgs &a, int F, bool draw);
+
 // classify_input.hip
 void launch_classifier_input(hipStream_t s, const uint8_t *crops, const int64_t *offsets, const int32_t *hw, int nseg,
                              uint8_t *patches, float *net, int pad, bool nhwc, const float *mean, const float *sd);

@@ -979,6 +979,23 @@ class Y4MWriter:
             self._fh.write(p.tobytes())
         self.frames += 1
 
+    def append_bgr(self, frames, ctx=None):
+        """BGR frames (F, H, W, 3) or one (H, W, 3), uint8 (a numpy array, or a torch tensor on the context's GPU), converted to 4:2:0 on
+        the GPU (swk_bgr_to_yuv420: cv2's COLOR_BGR2YUV_I420 restated, chroma from each cell's top-left pixel) and appended.  For an
+        8-bit 4:2:0 writer.  ctx: a _lib.Context (None: GPU 0's default context)."""
+        if self.mono or (self.sx, self.sy) != (1, 1) or self.bits != 8:
+            raise ValueError("append_bgr writes 8-bit 4:2:0")
+        if len(frames.shape) == 3:
+            frames = frames[None]
+        if tuple(frames.shape[1:]) != (self.height, self.width, 3):
+            raise ValueError("a %dx%d writer needs BGR frames (%d, %d, 3)" % (self.width, self.height, self.height, self.width))
+        if ctx is None:
+            from . import _lib
+            ctx = _lib.default_context(0)
+        y, u, v = ctx.bgr_to_yuv420(frames)
+        for k in range(len(y)):
+            self.append(y[k], u[k], v[k])
+
     def close(self):
         if self._fh is not None:
             self._fh.close()

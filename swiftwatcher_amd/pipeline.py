@@ -13,7 +13,7 @@ from . import image_filtering as img
 
 def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size=21, classifier=None, min_seg_size=(24, 24),
                              device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None,
-                             track_by_window=True):
+                             track_by_window=True, review=None):
     """Same call order as __main__.py:62-100.  corners = ((x1, y1), (x2, y2)) of the chimney's top edge: crop region
     and ROI mask are then generated from the video's first frame (:62-63) instead of being passed in.  Returns the tracker's detected events (lists of Segment objects,
     the structure the reference hands to event classification).  windows_per_call > 1 reads that many queue-fuls
@@ -21,7 +21,10 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     the reference's order, so the events are the same.  track_by_window (windows_per_call > 1 only): the tracker takes each
     window's frames in one library call (SegmentTracker.step_window) instead of one step per frame -- the same events; False is the
     per-frame path.  params: a _lib.default_params(...) struct for the segment path (bilateral
-    diameter and sigmas, threshold, ...); None = the reference's values."""
+    diameter and sigmas, threshold, ...); None = the reference's values.  review: a path (a file's or a FIFO's) or a review.ReviewWriter:
+    every window's frames are written there as a 4:2:0 video of the crop region with the segments, the boxes the classifier removed,
+    the ROI mask and the events drawn in (review.py); a writer made here from a path is closed when the count ends.  Counts and
+    events are the same with and without it."""
     if corners is not None:
         first_frame = reader.read_frame(0, increment=False)                        # :62
         crop_region, roi_mask, _ = img.generate_regions(first_frame, corners)      # :63
@@ -30,6 +33,22 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     if hasattr(reader, "set_region"):                # a reader of a pipe (io_y4m.Y4MStreamReader): it keeps only what this loop reads
         reader.set_region(crop_region, min_seg_size)
     tracker = SegmentTracker(roi_mask)
+    own_review = None
+    if review is not None and not hasattr(review, "write_window"):
+        from .review import ReviewWriter
+        review = own_review = ReviewWriter(review, crop_region, roi_mask, getattr(reader, "fps", 30.0), device=device)
+    try:
+        return _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_seg_size, device, keep_stages, windows_per_call,
+                              export_dir, params, track_by_window, tracker, review)
+    finally:
+        if own_review is not None:
+            own_review.close()
+
+
+def _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_seg_size, device, keep_stages, windows_per_call, export_dir,
+                   params, track_by_window, tracker, review):
+    """swift_counting_algorithm once the regions, the tracker and the review writer exist."""
+    seen = 0                                         # events already handed to the review
     if classifier is not None and getattr(reader, "_classifier_hint", False) is None:
         import weakref
         reader._classifier_hint = weakref.ref(classifier)          # a reader that segments ahead scores every batch for this classifier
@@ -64,10 +83,19 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
                 break
             if isinstance(batches, BaseException):
                 raise batches
+            removed = {}
             if classifier is not None:
-                classifier.classify_frames([fr for popped in batches for fr in popped])
+                flat = [fr for popped in batches for fr in popped]
+                before = [list(fr.segments) for fr in flat] if review is not None else None          # (the boxes the classifier removes)
+                classifier.classify_frames(flat)
+                if review is not None:
+                    from .review import removed_boxes
+                    removed = {id(fr): gone for fr, gone in zip(flat, removed_boxes(before, flat))}
             for popped in batches:
                 _track(tracker, popped, track_by_window)
+                if review is not None:
+                    review.write_window(popped, [removed.get(id(fr)) for fr in popped], tracker.detected_events[seen:])
+                    seen = len(tracker.detected_events)
         worker.join()
         return tracker.detected_events
     queue = FrameQueue(queue_size, device=device, params=params, keep_stages=keep_stages)
@@ -76,10 +104,16 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
         queue.push_list_of_frames(frames, numbers, stamps)                     # :74
         queue.preprocess_queue(crop_region, None)                              # :77
         queue.segment_queue(min_seg_size, crop_region)                         # :78
+        popped, removed = [], []
         while not queue.is_empty():                                            # :81
             frame = queue.pop_frame()
+            popped.append(frame)
             if classifier is not None:                                         # :84-85 (--classify)
+                before = frame.segments
                 frame.segments = classifier(frame.segments)
+                if review is not None:
+                    kept = {id(s) for s in frame.segments}
+                    removed.append([tuple(s.bbox) for s in before if id(s) not in kept])
             tracker.set_current_frame(frame)                                   # :87-92, call by call
             cost_matrix = tracker.formulate_cost_matrix()
             tracker.store_assignments(apply_hungarian_algorithm(cost_matrix))
@@ -88,6 +122,9 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
             tracker.cache_current_frame()
             if export_dir is not None:                                         # :94-96 (--export): needs keep_stages=True (the "crop" image)
                 frame.export_segments(min_seg_size, crop_region, export_dir)
+        if review is not None:
+            review.write_window(popped, removed if classifier is not None else None, tracker.detected_events[seen:])
+            seen = len(tracker.detected_events)
     return tracker.detected_events
 
 
@@ -101,18 +138,19 @@ def _track(tracker, popped, by_window):
             tracker.step(frame)
 
 
-def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, **kw):
+def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, review=None, **kw):
     """Decoded frames (oldest first) -> (swift count, events).  frames may also be a reader (get_n_frames / read_frame / total_frames,
     e.g. io_y4m.Y4MReader: its fps holds) or anything io_y4m.open_y4m opens: the path of a .y4m file (any format it reads), or a
     YUV4MPEG2 stream of unknown length -- "-" (standard input), a FIFO's path, a file descriptor, a binary file object (a pipe from a
-    decoder: proc.stdout).  Regions either explicit or from corners=...; params as in swift_counting_algorithm."""
+    decoder: proc.stdout).  Regions either explicit or from corners=...; params and review (a path or a
+    review.ReviewWriter: the review video of the count) as in swift_counting_algorithm."""
     opened = None
     if _is_video_source(frames):
         from .io_y4m import open_y4m
         frames = opened = open_y4m(frames)
     reader = frames if hasattr(frames, "get_n_frames") else ArrayReader(frames, fps=fps)
     try:
-        events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, **kw)
+        events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, review=review, **kw)
     finally:
         if opened is not None and hasattr(opened, "close"):
             opened.close()
@@ -190,7 +228,7 @@ def schedule_videos(readers, sizes, segment, consume, in_flight=4, windows_per_c
 
 
 def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows_per_call=1, classifier=None, queue_size=21,
-                        min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True):
+                        min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True, reviews=None):
     """count_swifts over a list of videos (the reference's loop over its video list, __main__.py:21), several videos at a time on one
     GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
     windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
@@ -199,20 +237,21 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
     videos: readers (read_frame / get_n_frames / total_frames), decoded frame arrays (oldest first) or what io_y4m.open_y4m opens (a
     .y4m path, "-", a FIFO, a descriptor, a binary file object); regions: per video
     (crop_region, roi_mask), or corners: per video the chimney's top edge (the regions then come from its first frame, :62-63).
+    reviews: per video a path, a review.ReviewWriter or None -- that video's review video (swift_counting_algorithm's review=).
     Returns [(count, events), ...] in input order."""
     from .io_y4m import open_y4m
     readers = [open_y4m(v) if _is_video_source(v) else v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
     opened = [r for r, v in zip(readers, videos) if r is not v and hasattr(r, "close")]          # (closed again when the count is done)
     try:
         return _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device,
-                             pad_factor, params, track_by_window)
+                             pad_factor, params, track_by_window, reviews)
     finally:
         for r in opened:
             r.close()
 
 
 def _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device, pad_factor, params,
-                  track_by_window=True):
+                  track_by_window=True, reviews=None):
     """count_swifts_videos over readers."""
     if regions is None:
         if corners is None:
@@ -229,18 +268,43 @@ def _count_videos(readers, regions, corners, in_flight, windows_per_call, classi
             r.ahead = max(r.ahead, windows_per_call)
     trackers = [SegmentTracker(mask) for _, mask in regions]
     sizes = [(cr[1][0] - cr[0][0]) * (cr[1][1] - cr[0][1]) for cr, _ in regions]
+    reviews = list(reviews) if reviews is not None else [None] * len(readers)
+    if len(reviews) != len(readers):
+        raise ValueError("one review (or None) per video")
+    own_reviews = []
+    try:
+        for v, rv in enumerate(reviews):
+            if rv is not None and not hasattr(rv, "write_window"):
+                from .review import ReviewWriter
+                reviews[v] = ReviewWriter(rv, regions[v][0], regions[v][1], getattr(readers[v], "fps", 30.0), device=device)
+                own_reviews.append(reviews[v])
+        seen = [0] * len(readers)                    # events already handed to each video's review
+        removed = {}                                 # id(frame) -> the boxes the classifier removed from it, until its window is written
 
-    def segment(groups):
-        out = segment_window_groups([(w, regions[v][0]) for v, w in groups], min_seg_size, device=device, params=params,
-                                    classifier=classifier)
-        if classifier is not None:
-            classifier.classify_frames([fr for per in out for popped in per for fr in popped])
-        return out
+        def segment(groups):
+            out = segment_window_groups([(w, regions[v][0]) for v, w in groups], min_seg_size, device=device, params=params,
+                                        classifier=classifier)
+            if classifier is not None:
+                flat = [fr for per in out for popped in per for fr in popped]
+                watched = [fr for (v, _), per in zip(groups, out) if reviews[v] is not None for popped in per for fr in popped]
+                before = [list(fr.segments) for fr in watched]
+                classifier.classify_frames(flat)
+                if watched:
+                    from .review import removed_boxes
+                    removed.update((id(fr), gone) for fr, gone in zip(watched, removed_boxes(before, watched)))
+            return out
 
-    def consume(v, popped_lists):
-        for popped in popped_lists:
-            _track(trackers[v], popped, track_by_window)
+        def consume(v, popped_lists):
+            for popped in popped_lists:
+                _track(trackers[v], popped, track_by_window)
+                if reviews[v] is not None:
+                    events = trackers[v].detected_events
+                    reviews[v].write_window(popped, [removed.pop(id(fr), None) for fr in popped], events[seen[v]:])
+                    seen[v] = len(events)
 
-    schedule_videos(readers, sizes, segment, consume, in_flight=in_flight, windows_per_call=windows_per_call, queue_size=queue_size,
-                    pad_factor=pad_factor)
+        schedule_videos(readers, sizes, segment, consume, in_flight=in_flight, windows_per_call=windows_per_call, queue_size=queue_size,
+                        pad_factor=pad_factor)
+    finally:
+        for rv in own_reviews:
+            rv.close()
     return [(ec.count_swifts(t.detected_events), t.detected_events) for t in trackers]

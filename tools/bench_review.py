@@ -1,0 +1,102 @@
+"""The review video's cost (csrc/review.hip, swiftwatcher_amd/review.py).
+1. The kernel alone: swk_bgr_to_yuv420 and swk_render_review (about 12 boxes per frame, a mark per frame, the mask, a border on every
+   fifth frame) on device BGR frames with a device destination, at 424 x 212 x 64 frames and 850 x 425 x 21 frames, timed with the
+   library's HIP events on the context's stream.  Reports ms per call and achieved bytes/s against the 4.5 B per pixel it must move
+   (3 read, 1.5 written) and the MI355X's 8 TB/s HBM peak.
+2. The counting loop: pipeline.count_swifts over a seeded synthetic clip (crop region 424 x 212) with and without review=, alternating
+   round by round, the review written to --out (a file on the local disk).  Reports frames/s of each, their ratio, and what the
+   review's frames weigh, so the loop's extra time can be set against the device-to-host copy plus the file write.
+    python tools/bench_review.py [--reps 50] [--rounds 5] [--frames 210] [--windows-per-call 2] [--out /tmp/review_bench.y4m]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from swiftwatcher_amd import _lib          # noqa: E402
+
+PEAK = 8.0e12
+STYLES = [(0, 255, 0, 32, 256), (0, 0, 255, 0, 160), (0, 255, 255, 0, 256), (255, 128, 0, 40, 0)]
+
+
+def kernel_rows(ctx, reps):
+    import torch
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(1)
+    rng = np.random.default_rng(2)
+    out = []
+    for Wc, Hc, F in ((424, 212, 64), (850, 425, 21)):
+        frames = torch.randint(0, 256, (F, Hc, Wc, 3), dtype=torch.uint8, device="cuda:0", generator=g)
+        r0, c0 = rng.integers(0, Hc - 40, (F, 12)), rng.integers(0, Wc - 60, (F, 12))
+        boxes = [(f, int(r0[f, k]), int(c0[f, k]), int(r0[f, k] + rng.integers(8, 40)), int(c0[f, k] + rng.integers(8, 60)), 1 + k % 2)
+                 for f in range(F) for k in range(12)]
+        marks = [(f, Hc // 2, Wc // 2, 3) for f in range(F)]
+        frame_style = np.array([3 if f % 5 == 0 else 0 for f in range(F)], np.int32)
+        mask = np.zeros((Hc, Wc), np.uint8)
+        mask[int(Hc * 0.8):, Wc // 10:Wc * 9 // 10] = 255
+        calls = {"convert": lambda: ctx.bgr_to_yuv420(frames, device_out=True),
+                 "render": lambda: ctx.render_review(frames, boxes=boxes, marks=marks, frame_style=frame_style, mask=mask, styles=STYLES,
+                                                     mask_style=4, mark_arm=4, border=3, device_out=True)}
+        moved = F * Hc * Wc * 4.5
+        for name, call in calls.items():
+            for _ in range(3):
+                call()
+            ctx.prof_enable(True)
+            ctx.prof_reset()
+            for _ in range(reps):
+                call()
+            ms, launches = ctx.prof()["gray"]
+            ctx.prof_enable(False)
+            per = ms / reps
+            out.append({"bench": "review_kernel", "call": name, "Wc": Wc, "Hc": Hc, "frames": F, "ms": round(per, 5), "launches_per_call": launches // reps,
+                        "GBps": round(moved / per / 1e6, 1), "of_hbm_peak": round(moved / (per * 1e-3) / PEAK, 4), "bytes_moved": int(moved)})
+    return out
+
+
+def loop_rows(frames_n, rounds, wpc, path):
+    from swiftwatcher_amd import pipeline, synthetic
+    crop = [(28, 29), (28 + 424, 29 + 212)]
+    frames = synthetic.full_frames(500, frames_n, crop, frame_hw=(270, 480))[::-1].copy()
+    roi_mask = np.zeros((212, 424), np.uint8)
+    roi_mask[int(212 * 0.8):, :] = 255
+    kw = dict(crop_region=crop, roi_mask=roi_mask, windows_per_call=wpc)
+    want = pipeline.count_swifts(frames, **kw)                                   # warm-up, and the count both variants must give
+    pipeline.count_swifts(frames, review=path, **kw)
+    times = {"plain": [], "review": []}
+    for _ in range(rounds):
+        for name in ("plain", "review"):
+            t0 = time.perf_counter()
+            got = pipeline.count_swifts(frames, review=path if name == "review" else None, **kw)
+            times[name].append(time.perf_counter() - t0)
+            assert got[0] == want[0] and len(got[1]) == len(want[1])
+    size = os.path.getsize(path)
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    return [{"bench": "review_loop", "frames": frames_n, "windows_per_call": wpc, "crop": [424, 212], "events": len(want[1]),
+             "plain_fps": round(frames_n / med["plain"], 1), "review_fps": round(frames_n / med["review"], 1),
+             "plain_s": [round(t, 4) for t in times["plain"]], "review_s": [round(t, 4) for t in times["review"]],
+             "review_over_plain": round(med["review"] / med["plain"], 4), "review_extra_ms_per_frame": round((med["review"] - med["plain"]) / frames_n * 1e3, 4),
+             "review_file_bytes": size, "review_bytes_per_frame": size // max(frames_n, 1)}]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--frames", type=int, default=210)
+    ap.add_argument("--windows-per-call", type=int, default=2)
+    ap.add_argument("--out", default=os.path.join("/tmp", "review_bench.y4m"))
+    a = ap.parse_args()
+    ctx = _lib.default_context(0)
+    for row in kernel_rows(ctx, a.reps):
+        print(json.dumps(row), flush=True)
+    for wpc in sorted({1, a.windows_per_call}):
+        for row in loop_rows(a.frames, a.rounds, wpc, a.out):
+            print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()
