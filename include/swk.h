@@ -330,6 +330,34 @@ typedef struct swk_review {
 int32_t swk_bgr_to_yuv420(swk_ctx *ctx, const swk_input *in, swk_yuv420_dst *dst);
 int32_t swk_render_review(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv420_dst *dst);
 
+/* ---- review video, layer 5: labels (short strings in a built-in bitmap font) -----------------------------------
+ * Font: glyphs 5 wide and 7 high, one byte per glyph row, bit 4 the leftmost column; the table is written by hand in
+ * csrc/review.hip.  Character set: space, 0-9, A-Z and # : . - + / = %; every other byte is refused.  swk_review_font (host
+ * only, no context) copies the table out: out[ch][0..6] the glyph's rows, out[ch][7] = 1 for a byte of the set, else 0 (and
+ * rows of zeros).
+ *
+ * A label: (r, c) is the top-left ink pixel position of the first glyph (may be negative or outside the frame), scale 1..8,
+ * len 0..32 bytes of text; `style` gives the ink's colour and line_alpha (style 0 draws no ink: ink pixels stay as they are),
+ * `plate` is a style index whose colour and fill_alpha give the background plate (0: no plate).
+ *
+ * Pixels, with s = scale: the label's rectangle is rows [r - s, r + 8 s) and columns [c - s, c + 6 s len) -- a character cell
+ * is 6 x 8 units with the ink in its top-left 5 x 7, and one unit of margin lies on every side.  For a pixel (y, x) inside
+ * the rectangle and inside the frame let v = y - r, u = x - c.  The pixel is ink if v >= 0, u >= 0, v / s < 7,
+ * (u / s) % 6 < 5 and bit 4 - (u / s) % 6 of font[text[u / (6 s)]][v / s] is set; an ink pixel is blended once with the colour
+ * and line_alpha of `style`; every other pixel of the rectangle is blended once with the colour and fill_alpha of `plate`, if
+ * plate != 0.  The blend is blend(p, col, a) above.  Labels are layer 5: after the border, in array order within a frame (later
+ * labels lie over earlier ones); conversion and chroma sampling as above.  A len of 0 draws nothing. */
+typedef struct swk_review_label { int32_t frame, r, c, style, plate, scale, len, reserved_; uint8_t text[32]; } swk_review_label;
+
+void swk_review_font(uint8_t out[128][8]);
+
+/* swk_render_review with labels (host memory, ascending .frame).  rv must not be null; nlabels == 0 equals swk_render_review
+ * bit for bit.  SWK_ERR_ARG, before anything is copied or launched and with dst untouched, besides swk_render_review's list: a
+ * null array with a non-zero count, or a negative count; a label's frame outside 0 .. nwin * n - 1; labels not in ascending
+ * `frame`; scale outside 1..8; len outside 0..32; style or plate outside 0..nstyles; a byte of text[0..len) outside the set. */
+int32_t swk_render_review_labels(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels,
+                                 int32_t nlabels, swk_yuv420_dst *dst);
+
 /* ---- stage-level entry points (host buffers; used by the parity tests and by the
  *      image_filtering.* drop-in functions) ------------------------------------- */
 /* convert_grayscale (image_filtering.py:188-196): [count][H][W][3] -> [count][H][W] */

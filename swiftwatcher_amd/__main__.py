@@ -1,5 +1,5 @@
 """python -m swiftwatcher_amd SOURCE [SOURCE ...] (--corners X1,Y1,X2,Y2 | --attributes FILE) [--start N] [--end N]
-       [--classify WEIGHTS] [--out DIR] [--review PATH] [--windows-per-call K] [--device D]
+       [--classify WEIGHTS] [--out DIR] [--review PATH [--review-text]] [--windows-per-call K] [--device D]
 
 The reference's main() (__main__.py:13-53) without its UI: every SOURCE -- a .y4m file, or "-" for a YUV4MPEG2 stream on standard
 input (`ffmpeg -i evening.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners 812,640,1105,642`) -- is counted by
@@ -9,7 +9,9 @@ line goes to standard output: {"source", "frames", "events", "count"}; --out DIR
 (io_data.export_results, :49-50; under DIR/<stem> when several sources are given).  --review PATH writes the review video of the
 count (review.py: the crop region as a 4:2:0 .y4m with segments, removed segments, ROI mask and events drawn in; PATH/<stem>.y4m when
 several sources are given).  PATH may be a FIFO (`--review fifo & ffmpeg -i fifo out.mp4`), not "-": standard output carries the
-JSON lines."""
+JSON lines.  --review-text (with --review only) writes the tables' keys into every frame of the review: a status line "F000123
+00:00:04.104 S03 R01 E007" (frame number, timestamp, segments, boxes the classifier removed, events so far) and the number #k of
+every event shown, k its row in the events table."""
 import argparse
 import json
 import os
@@ -55,6 +57,7 @@ def build_parser():
     p.add_argument("--classify", metavar="WEIGHTS", help="filter segments with the classifier of this state_dict file")
     p.add_argument("--out", metavar="DIR", help="write the result tables (CSV) here")
     p.add_argument("--review", type=_review_path, metavar="PATH", help="write a review video (.y4m) of the count here")
+    p.add_argument("--review-text", action="store_true", help="with --review: draw frame number, time, counts and event numbers into it")
     p.add_argument("--windows-per-call", type=int, default=1, metavar="K", help="queue-fuls segmented per GPU call")
     p.add_argument("--device", type=int, default=0, metavar="D", help="GPU index")
     return p
@@ -68,6 +71,8 @@ def plan(argv):
         parser.error("standard input (-) can be given once")
     if args.start < 0 or args.end < 0 or args.windows_per_call < 1:
         parser.error("--start and --end are frame numbers, --windows-per-call is at least 1")
+    if args.review_text and not args.review:
+        parser.error("--review-text needs --review PATH")
     shared = None
     try:
         if args.corners is not None:
@@ -116,7 +121,7 @@ def main(argv=None):
             review = os.path.join(review, stem + ".y4m")
         try:
             count, events = pipeline.count_swifts(reader, corners=corners, classifier=classifier, device=args.device,
-                                                  windows_per_call=args.windows_per_call, review=review or None)
+                                                  windows_per_call=args.windows_per_call, review=review or None, review_text=args.review_text)
             frames, fps, first, last = reader.total_frames, reader.fps, reader.start_frame, reader.end_frame
         except (OSError, ValueError) as exc:
             print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)

@@ -106,6 +106,39 @@ REVIEW_BOX_DTYPE = np.dtype([("frame", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("r
 REVIEW_MARK_DTYPE = np.dtype([("frame", "<i4"), ("r", "<i4"), ("c", "<i4"), ("style", "<i4")])
 REVIEW_STYLE_DTYPE = np.dtype([("b", "u1"), ("g", "u1"), ("r", "u1"), ("reserved_", "u1"), ("fill_alpha", "<i4"), ("line_alpha", "<i4")])
 assert REVIEW_STYLE_DTYPE.itemsize == ctypes.sizeof(ReviewStyle) == 12 and REVIEW_BOX_DTYPE.itemsize == 24 and REVIEW_MARK_DTYPE.itemsize == 16
+REVIEW_LABEL_DTYPE = np.dtype([("frame", "<i4"), ("r", "<i4"), ("c", "<i4"), ("style", "<i4"), ("plate", "<i4"), ("scale", "<i4"), ("len", "<i4"),
+                               ("reserved_", "<i4"), ("text", "u1", (32,))])
+assert REVIEW_LABEL_DTYPE.itemsize == 64
+
+
+
+def label_records(labels):
+    """REVIEW_LABEL_DTYPE records of tuples (frame, r, c, style, plate, scale, text), text a str (ASCII) or bytes of at most 32 bytes;
+    records pass through."""
+    if isinstance(labels, np.ndarray) and labels.dtype == REVIEW_LABEL_DTYPE:
+        return np.ascontiguousarray(labels)
+    labels = list(labels)
+    out = np.zeros(len(labels), REVIEW_LABEL_DTYPE)
+    if not labels:
+        return out
+    texts = [lab[6].encode("ascii") if isinstance(lab[6], str) else bytes(lab[6]) for lab in labels]
+    if max(len(raw) for raw in texts) > 32:
+        raise ValueError("a label holds at most 32 bytes")
+    rows = np.array([lab[:6] for lab in labels], dtype=np.int64).reshape(-1, 6)
+    for k, name in enumerate(("frame", "r", "c", "style", "plate", "scale")):
+        out[name] = rows[:, k]
+    out["len"] = [len(raw) for raw in texts]
+    out["text"] = np.frombuffer(b"".join(raw.ljust(32, b"\0") for raw in texts), np.uint8).reshape(-1, 32)
+    return out
+
+
+def review_font():
+    """swk_review_font: uint8 (128, 8) -- rows 0..6 of byte ch's 5 x 7 glyph (bit 4 = the leftmost column), [ch, 7] = 1 where ch is in
+    the labels' character set."""
+    out = np.zeros((128, 8), np.uint8)
+    load().swk_review_font(out.ctypes.data)
+    return out
+
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -123,6 +156,9 @@ _SIGS = {
     "swk_yuv_to_bgr": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv)] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int32]),
     "swk_bgr_to_yuv420": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Yuv420Dst)]),
     "swk_render_review": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Review), ctypes.POINTER(Yuv420Dst)]),
+    "swk_render_review_labels": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Review), ctypes.c_void_p, ctypes.c_int32,
+                                                  ctypes.POINTER(Yuv420Dst)]),
+    "swk_review_font": (None, [ctypes.c_void_p]),
     "swk_bgr2gray": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "swk_ialm": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_rpca_epilogue": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -783,11 +819,13 @@ class Context:
         return planes
 
     def render_review(self, frames, boxes=None, marks=None, frame_style=None, mask=None, styles=None, mask_style=0, mark_arm=0, border=0,
-                      rect=None, layout="i420", device_out=False, dst=None):
+                      rect=None, layout="i420", device_out=False, dst=None, labels=None):
         """swk_render_review: bgr_to_yuv420 of the frames composed with an overlay (include/swk.h): boxes -- REVIEW_BOX_DTYPE records
         or rows (frame, r0, c0, r1, c1, style), ascending frame --, marks -- REVIEW_MARK_DTYPE records or rows (frame, r, c, style),
         ascending frame --, frame_style (F,) int32 border style per frame, mask (Hr, Wr) uint8 tinted in mask_style where != 0, styles
-        -- REVIEW_STYLE_DTYPE records or rows (b, g, r, fill_alpha, line_alpha); style k is styles[k - 1], 0 draws nothing."""
+        -- REVIEW_STYLE_DTYPE records or rows (b, g, r, fill_alpha, line_alpha); style k is styles[k - 1], 0 draws nothing.
+        labels (None: swk_render_review is called; else swk_render_review_labels, the fifth layer) -- REVIEW_LABEL_DTYPE records or
+        tuples (frame, r, c, style, plate, scale, text), ascending frame, text a str or bytes of the font's character set."""
         def records(a, dtype, cols):
             if a is None:
                 return np.zeros(0, dtype)
@@ -823,7 +861,12 @@ class Context:
                     marks=marks.ctypes.data if len(marks) else None, nmarks=len(marks), mark_arm=int(mark_arm),
                     frame_style=frame_style.ctypes.data if frame_style is not None else None, border=int(border),
                     styles=styles.ctypes.data if len(styles) else None, nstyles=len(styles))
-        self._check(self._lib.swk_render_review(self._h, ctypes.byref(inp), ctypes.byref(rv), ctypes.byref(dst)))
+        if labels is None:
+            self._check(self._lib.swk_render_review(self._h, ctypes.byref(inp), ctypes.byref(rv), ctypes.byref(dst)))
+            return planes
+        labels = label_records(labels)
+        self._check(self._lib.swk_render_review_labels(self._h, ctypes.byref(inp), ctypes.byref(rv), labels.ctypes.data if len(labels) else None,
+                                                       len(labels), ctypes.byref(dst)))
         return planes
 
     # ---- stage-level entry points ----

@@ -17,6 +17,16 @@
 // consecutive addresses whatever the ROI's origin, the strides and the sizes' parity.  blockIdx.y is the frame: a workgroup reads
 // its frame's boxes and marks, style already resolved by the host, into LDS in chunks of kChunk, so a frame may carry any number;
 // a strip tests a box's rectangle once and walks its 16 pixels only where they meet.
+//
+// Labels (layer 5, swk_render_review_labels) are a further template flag, so the instantiations without text keep their registers,
+// LDS and kernel arguments (the label tables are an argument that only the instantiation with text has): the records (16 words:
+// geometry, resolved ink and plate, 32 bytes of text as font indices) are staged through the same LDS words in chunks of kLabelChunk,
+// the font's rows sit in 512 bytes of LDS beside them, and a strip tests a label's rectangle in 64 bits before it walks its pixels
+// in 32-bit offsets from the label's origin.
+#include <string.h>
+
+#include <type_traits>
+
 #include "swk_internal.h"
 
 namespace swk {
@@ -24,6 +34,36 @@ namespace swk {
 namespace {
 
 constexpr int kChunk = 128;
+constexpr int kLabelChunk = kChunk * 6 / 16;          // 48 labels of 16 words: the LDS words of a chunk of boxes
+
+// The font: 5 x 7 glyphs, one byte per row, bit 4 the leftmost column, row 7 = 1 for a byte of the character set; bytes
+// kReviewFontFirst (space) .. 'Z'.  Drawn by hand for this library.
+#define G(a, b, c, d, e, f, g) {0x##a, 0x##b, 0x##c, 0x##d, 0x##e, 0x##f, 0x##g, 1}
+#define NONE {0, 0, 0, 0, 0, 0, 0, 0}
+#define SWK_REVIEW_FONT_ROWS {                                                                                                  \
+    /* space ! " # */ G(00, 00, 00, 00, 00, 00, 00), NONE, NONE, G(0A, 0A, 1F, 0A, 1F, 0A, 0A),                                 \
+    /* $ % & ' */     NONE, G(19, 19, 02, 04, 08, 13, 13), NONE, NONE,                                                          \
+    /* ( ) * + */     NONE, NONE, NONE, G(00, 04, 04, 1F, 04, 04, 00),                                                          \
+    /* , - . / */     NONE, G(00, 00, 00, 1F, 00, 00, 00), G(00, 00, 00, 00, 00, 0C, 0C), G(01, 01, 02, 04, 08, 10, 10),        \
+    /* 0 1 2 */       G(0E, 11, 13, 15, 19, 11, 0E), G(04, 0C, 04, 04, 04, 04, 0E), G(0E, 11, 01, 02, 04, 08, 1F),              \
+    /* 3 4 5 */       G(1F, 02, 04, 02, 01, 11, 0E), G(02, 06, 0A, 12, 1F, 02, 02), G(1F, 10, 1E, 01, 01, 11, 0E),              \
+    /* 6 7 8 */       G(06, 08, 10, 1E, 11, 11, 0E), G(1F, 01, 02, 04, 08, 08, 08), G(0E, 11, 11, 0E, 11, 11, 0E),              \
+    /* 9 : ; */       G(0E, 11, 11, 0F, 01, 02, 0C), G(00, 0C, 0C, 00, 0C, 0C, 00), NONE,                                       \
+    /* < = > ? @ */   NONE, G(00, 00, 1F, 00, 1F, 00, 00), NONE, NONE, NONE,                                                    \
+    /* A B C */       G(0E, 11, 11, 1F, 11, 11, 11), G(1E, 11, 11, 1E, 11, 11, 1E), G(0E, 11, 10, 10, 10, 11, 0E),              \
+    /* D E F */       G(1C, 12, 11, 11, 11, 12, 1C), G(1F, 10, 10, 1E, 10, 10, 1F), G(1F, 10, 10, 1E, 10, 10, 10),              \
+    /* G H I */       G(0E, 11, 10, 17, 11, 11, 0F), G(11, 11, 11, 1F, 11, 11, 11), G(0E, 04, 04, 04, 04, 04, 0E),              \
+    /* J K L */       G(07, 02, 02, 02, 02, 12, 0C), G(11, 12, 14, 18, 14, 12, 11), G(10, 10, 10, 10, 10, 10, 1F),              \
+    /* M N O */       G(11, 1B, 15, 15, 11, 11, 11), G(11, 11, 19, 15, 13, 11, 11), G(0E, 11, 11, 11, 11, 11, 0E),              \
+    /* P Q R */       G(1E, 11, 11, 1E, 10, 10, 10), G(0E, 11, 11, 11, 15, 12, 0D), G(1E, 11, 11, 1E, 14, 12, 11),              \
+    /* S T U */       G(0F, 10, 10, 0E, 01, 01, 1E), G(1F, 04, 04, 04, 04, 04, 04), G(11, 11, 11, 11, 11, 11, 0E),              \
+    /* V W X */       G(11, 11, 11, 11, 11, 0A, 04), G(11, 11, 11, 15, 15, 15, 0A), G(11, 11, 0A, 04, 0A, 11, 11),              \
+    /* Y Z */         G(11, 11, 11, 0A, 04, 04, 04), G(1F, 01, 02, 04, 08, 10, 1F)}
+const uint8_t h_font[kReviewFontCount][8] = SWK_REVIEW_FONT_ROWS;
+__constant__ uint8_t d_font[kReviewFontCount][8] = SWK_REVIEW_FONT_ROWS;
+#undef SWK_REVIEW_FONT_ROWS
+#undef NONE
+#undef G
 constexpr int kYR = 269484, kYG = 528482, kYB = 102760, kUR = -155188, kUG = -305135, kUB = 460324, kVR = 460324, kVG = -385875,
               kVB = -74448;
 
@@ -68,8 +108,10 @@ __device__ __forceinline__ void store_run4(uint8_t *p, uint32_t w, int n)
 
 }  // namespace
 
-template <bool DRAW>
-__global__ __launch_bounds__(256) void k_review(ReviewArgs a, int f0)
+struct NoLabels {};
+
+template <bool DRAW, bool TEXT>
+__global__ __launch_bounds__(256) void k_review(ReviewArgs a, int f0, typename std::conditional<TEXT, ReviewLabels, NoLabels>::type t)
 {
     __shared__ int32_t lds[kChunk * 6];
     const int f = f0 + (int)blockIdx.y;
@@ -188,6 +230,47 @@ __global__ __launch_bounds__(256) void k_review(ReviewArgs a, int f0)
                 }
             }
         }
+        // ---- 5. the frame's labels, in array order: LDS entries (r, c, scale, len, ink colour, ink alpha, plate colour, plate alpha,
+        // 8 words of font indices)
+        if constexpr (TEXT) {
+            __shared__ uint8_t font[64 * 8];                             // (a font index is taken & 63: no index leaves the table)
+            for (int k = threadIdx.x; k < 64 * 8; k += blockDim.x) font[k] = k < kReviewFontCount * 8 ? (&d_font[0][0])[k] : (uint8_t)0;
+            const int l_begin = t.label_start[f], l_end = t.label_start[f + 1];
+            for (int base = l_begin; base < l_end; base += kLabelChunk) {
+                const int cnt = l_end - base < kLabelChunk ? l_end - base : kLabelChunk;
+                __syncthreads();
+                for (int k = threadIdx.x; k < cnt * 16; k += blockDim.x) lds[k] = t.labels[(int64_t)base * 16 + k];
+                __syncthreads();
+                for (int l = 0; l < cnt; ++l) {
+                    const int32_t *e = &lds[16 * l];
+                    const int64_t lr = e[0], lc = e[1];
+                    const int s = e[2], len = e[3];
+                    const int64_t top = lr - s, bottom = lr + 8 * s, left = lc - s, right = lc + (int64_t)6 * s * len;
+                    if (!live || len <= 0 || top >= r0 + nrow || bottom <= r0 || left >= c0 + ncol || right <= c0) continue;
+                    const uint32_t ink_colour = (uint32_t)e[4], plate_colour = (uint32_t)e[6];
+                    const int ink_alpha = e[5], plate_alpha = e[7];
+                    // x / s as (x * inv) >> 16, inv = ceil(2^16 / s): exact for x < 2048 and s <= 8 (the error x (inv - 2^16 / s) / 2^16 is
+                    // below 1 / 32, the fraction of x / s at most 1 - 1 / 8); here x < 8 s <= 64 and x < 6 s len <= 1536
+                    const uint32_t inv = (65536u + (uint32_t)s - 1u) / (uint32_t)s;
+                    // the strip meets the rectangle, so its first pixel lies within 16 pixels of it: 32 bits from here on
+                    const int v0 = (int)(r0 - lr), u0 = (int)(c0 - lc), tall = 8 * s, wide = 6 * s * len;
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) {
+                        const int v = v0 + (k >> 3), u = u0 + (k & 7);
+                        if (v < -s || v >= tall || u < -s || u >= wide) continue;          // outside rows [r - s, r + 8 s) or columns [c - s, c + 6 s len)
+                        bool ink = false;
+                        if (v >= 0 && u >= 0) {
+                            const uint32_t vs = ((uint32_t)v * inv) >> 16, cell = ((uint32_t)u * inv) >> 16, ci = cell / 6u, col = cell - 6u * ci;
+                            if (vs < 7u && col < 5u) {
+                                const uint32_t ch = ((uint32_t)e[8 + (ci >> 2)] >> (8 * (ci & 3u))) & 63u;          // ci < len <= 32
+                                ink = ((font[8 * ch + vs] >> (4u - col)) & 1u) != 0;
+                            }
+                        }
+                        blend3(px[k], ink ? ink_colour : plate_colour, ink ? ink_alpha : plate_alpha);
+                    }
+                }
+            }
+        }
     }
     if (!live) return;
 
@@ -227,15 +310,22 @@ __global__ __launch_bounds__(256) void k_review(ReviewArgs a, int f0)
     }
 }
 
-void launch_review(hipStream_t s, const ReviewArgs &a, int F, bool draw)
+void review_font(uint8_t out[128][8])
+{
+    memset(out, 0, 128 * 8);
+    memcpy(out[kReviewFontFirst], h_font, sizeof(h_font));
+}
+
+void launch_review(hipStream_t s, const ReviewArgs &a, int F, bool draw, const ReviewLabels *text)
 {
     const int strips = ((a.Wc + 7) >> 3) * ((a.Hc + 1) >> 1);
     // grid.y is limited to 65535: split the frame range
     for (int f0 = 0; f0 < F; f0 += 32768) {
         const int fc = F - f0 < 32768 ? F - f0 : 32768;
         const dim3 grid((strips + 255) / 256, fc);
-        if (draw) hipLaunchKernelGGL(k_review<true>, grid, dim3(256), 0, s, a, f0);
-        else hipLaunchKernelGGL(k_review<false>, grid, dim3(256), 0, s, a, f0);
+        if (draw && text) hipLaunchKernelGGL((k_review<true, true>), grid, dim3(256), 0, s, a, f0, *text);
+        else if (draw) hipLaunchKernelGGL((k_review<true, false>), grid, dim3(256), 0, s, a, f0, NoLabels{});
+        else hipLaunchKernelGGL((k_review<false, false>), grid, dim3(256), 0, s, a, f0, NoLabels{});
         note_launch();
     }
 }

@@ -1489,7 +1489,7 @@ int download_rects(swk_ctx *ctx, uint8_t *dst, int64_t rs, int64_t fs, const uin
     return SWK_OK;
 }
 
-int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv420_dst *dst)
+int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels, int nlabels, swk_yuv420_dst *dst)
 {
     if (!in || !dst) return fail(ctx, SWK_ERR_ARG, "null argument");
     // ---- every refusal comes before anything is copied or launched
@@ -1509,7 +1509,7 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv
     if (!dst->y || !dst->u || (!nv12 && !dst->v)) return fail(ctx, SWK_ERR_ARG, "null YUV plane");
     if (dst->y_row_stride < Wc || dst->c_row_stride < (int64_t)cw * cbytes) return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
     std::vector<int32_t> meta;
-    size_t o_boxes = 0, o_bstart = 0, o_marks = 0, o_mstart = 0, o_border = 0, o_mask = 0;
+    size_t o_boxes = 0, o_bstart = 0, o_marks = 0, o_mstart = 0, o_border = 0, o_mask = 0, o_labels = 0, o_lstart = 0;
     uint32_t mask_colour = 0; int mask_alpha = 0;
     if (rv) {
         if (rv->nstyles < 0 || (rv->nstyles > 0 && !rv->styles)) return fail(ctx, SWK_ERR_ARG, "styles");
@@ -1541,6 +1541,21 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv
         if (rv->frame_style)
             for (int f = 0; f < F; ++f)
                 if (bad_style(rv->frame_style[f])) return fail(ctx, SWK_ERR_ARG, "a frame's border style outside 0..nstyles");
+        if (nlabels < 0 || (nlabels > 0 && !labels)) return fail(ctx, SWK_ERR_ARG, "a null label array with a non-zero count, or a negative count");
+        uint8_t font[128][8];
+        review_font(font);
+        prev = 0;
+        for (int k = 0; k < nlabels; ++k) {
+            const swk_review_label &l = labels[k];
+            if (l.frame < 0 || l.frame >= F) return fail(ctx, SWK_ERR_ARG, "a label's frame outside the call's frames");
+            if (l.frame < prev) return fail(ctx, SWK_ERR_ARG, "labels not in ascending frame order");
+            if (l.scale < 1 || l.scale > 8) return fail(ctx, SWK_ERR_ARG, "a label's scale outside 1..8");
+            if (l.len < 0 || l.len > 32) return fail(ctx, SWK_ERR_ARG, "a label's len outside 0..32");
+            if (bad_style(l.style) || bad_style(l.plate)) return fail(ctx, SWK_ERR_ARG, "a label's style or plate outside 0..nstyles");
+            for (int j = 0; j < l.len; ++j)
+                if (l.text[j] > 127 || !font[l.text[j]][7]) return fail(ctx, SWK_ERR_ARG, "a label's text holds a byte outside the character set");
+            prev = l.frame;
+        }
         // ---- the kernel's tables, styles resolved, in one block of int32 (launch_review, swk_internal.h)
         o_boxes = 0;
         meta.resize((size_t)rv->nboxes * 6);
@@ -1585,9 +1600,28 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv
             mask_colour = colour(rv->mask_style);
             mask_alpha = rv->styles[rv->mask_style - 1].fill_alpha;
         }
+        if (nlabels > 0) {
+            o_labels = meta.size();
+            meta.resize(o_labels + (size_t)nlabels * 16, 0);
+            for (int k = 0; k < nlabels; ++k) {
+                const swk_review_label &l = labels[k];
+                int32_t *e = &meta[o_labels + (size_t)k * 16];
+                e[0] = l.r; e[1] = l.c; e[2] = l.scale; e[3] = l.len;
+                e[4] = l.style ? (int32_t)colour(l.style) : 0;
+                e[5] = l.style ? rv->styles[l.style - 1].line_alpha : 0;          // (alpha 0 is the identity)
+                e[6] = l.plate ? (int32_t)colour(l.plate) : 0;
+                e[7] = l.plate ? rv->styles[l.plate - 1].fill_alpha : 0;
+                for (int j = 0; j < l.len; ++j) e[8 + (j >> 2)] |= (int32_t)((uint32_t)(l.text[j] - kReviewFontFirst) << (8 * (j & 3)));
+            }
+            o_lstart = meta.size();
+            meta.resize(o_lstart + F + 1, 0);
+            for (int k = 0; k < nlabels; ++k) meta[o_lstart + labels[k].frame + 1] += 1;
+            for (int f = 0; f < F; ++f) meta[o_lstart + f + 1] += meta[o_lstart + f];
+        }
     }
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ReviewArgs a{};
+    ReviewLabels text{};
     a.src = in->frames; a.fs = in->frame_stride; a.rs = in->row_stride; a.x0 = in->x0; a.y0 = in->y0;
     a.Hc = Hc; a.Wc = Wc; a.channels = in->channels; a.layout = dst->layout;
     if (in->mem == SWK_MEM_HOST) {
@@ -1619,10 +1653,11 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv
         a.mask = mask_alpha ? (const uint8_t *)(dmeta + o_mask) : nullptr;
         a.mask_colour = mask_colour; a.mask_alpha = mask_alpha;
         a.mark_arm = rv->mark_arm; a.border = rv->border;
+        if (nlabels > 0) { text.labels = dmeta + o_labels; text.label_start = dmeta + o_lstart; }
     }
     {
         Timed t(ctx, SWK_K_GRAY);
-        launch_review(ctx->stream, a, F, rv != nullptr);
+        launch_review(ctx->stream, a, F, rv != nullptr, rv != nullptr && nlabels > 0 ? &text : nullptr);
     }
     if (dst->mem == SWK_MEM_HOST) {
         int rc = download_rects(ctx, dst->y, dst->y_row_stride, dst->y_frame_stride, a.y, (size_t)Wc, (size_t)Hc, F);
@@ -1642,14 +1677,27 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv
 int32_t swk_bgr_to_yuv420(swk_ctx *ctx, const swk_input *in, swk_yuv420_dst *dst)
 {
     if (!ctx) return SWK_ERR_ARG;
-    return review_call(ctx, in, nullptr, dst);
+    return review_call(ctx, in, nullptr, nullptr, 0, dst);
 }
 
 int32_t swk_render_review(swk_ctx *ctx, const swk_input *in, const swk_review *rv, swk_yuv420_dst *dst)
 {
     if (!ctx) return SWK_ERR_ARG;
     if (!rv) return fail(ctx, SWK_ERR_ARG, "null argument");
-    return review_call(ctx, in, rv, dst);
+    return review_call(ctx, in, rv, nullptr, 0, dst);
+}
+
+int32_t swk_render_review_labels(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels, int32_t nlabels,
+                                 swk_yuv420_dst *dst)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!rv) return fail(ctx, SWK_ERR_ARG, "null argument");
+    return review_call(ctx, in, rv, labels, nlabels, dst);
+}
+
+void swk_review_font(uint8_t out[128][8])
+{
+    if (out) swk::review_font(out);
 }
 
 int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, double lmbda, double tol, int32_t maxiter,

@@ -174,7 +174,10 @@ void launch_yuv_to_bgr(hipStream_t s, int layout, int sx, int sy, int bits, int 
 // resolves styles: boxes [nboxes][6] = (r0, c0, r1, c1, colour b | g << 8 | r << 16, fill alpha | line alpha << 16) with
 // box_start [F + 1] the first box of every frame, marks [nmarks][4] = (r, c, colour, line alpha) with mark_start [F + 1],
 // frame_border [F][2] = (colour, line alpha or -1 for none) or null.  draw = false: the conversion alone (nothing but the source, the
-// geometry and the destination is read).
+// geometry and the destination is read).  text (with draw; null = no labels): labels [nlabels][16] = (r, c, scale, len, ink colour,
+// ink alpha, plate colour, plate alpha, 8 words of text as font indices = byte - kReviewFontFirst) with label_start [F + 1]; an alpha
+// of 0 stands for style 0 / plate 0 (the blend is then the identity).
+constexpr int kReviewFontFirst = 32, kReviewFontCount = 59;          // the font table covers bytes 32 (space) .. 90 ('Z')
 struct ReviewArgs {
     const uint8_t *src;
     int64_t fs, rs;
@@ -186,7 +189,11 @@ struct ReviewArgs {
     const int32_t *boxes, *box_start, *marks, *mark_start, *frame_border;
     int mark_arm, border;
 };
-void launch_review(hipStream_t s, const ReviewArgs &a, int F, bool draw);
+// the labels go to the kernel as an argument of their own, which only the instantiation with text has: the others keep their arguments
+struct ReviewLabels { const int32_t *labels, *label_start; };
+void launch_review(hipStream_t s, const ReviewArgs &a, int F, bool draw, const ReviewLabels *text = nullptr);
+// the font's rows of byte ch (0..127): rows[0..6], rows[7] = 1 where ch is in the character set (host)
+void review_font(uint8_t out[128][8]);
 
 // classify_input.hip
 void launch_classifier_input(hipStream_t s, const uint8_t *crops, const int64_t *offsets, const int32_t *hw, int nseg,

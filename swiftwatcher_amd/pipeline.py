@@ -13,7 +13,7 @@ from . import image_filtering as img
 
 def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size=21, classifier=None, min_seg_size=(24, 24),
                              device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None,
-                             track_by_window=True, review=None):
+                             track_by_window=True, review=None, review_text=False):
     """Same call order as __main__.py:62-100.  corners = ((x1, y1), (x2, y2)) of the chimney's top edge: crop region
     and ROI mask are then generated from the video's first frame (:62-63) instead of being passed in.  Returns the tracker's detected events (lists of Segment objects,
     the structure the reference hands to event classification).  windows_per_call > 1 reads that many queue-fuls
@@ -24,7 +24,8 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     diameter and sigmas, threshold, ...); None = the reference's values.  review: a path (a file's or a FIFO's) or a review.ReviewWriter:
     every window's frames are written there as a 4:2:0 video of the crop region with the segments, the boxes the classifier removed,
     the ROI mask and the events drawn in (review.py); a writer made here from a path is closed when the count ends.  Counts and
-    events are the same with and without it."""
+    events are the same with and without it.  review_text: a writer made here from a path also writes the status line and the event
+    numbers (ReviewWriter's text=True); a ReviewWriter handed in carries its own setting."""
     if corners is not None:
         first_frame = reader.read_frame(0, increment=False)                        # :62
         crop_region, roi_mask, _ = img.generate_regions(first_frame, corners)      # :63
@@ -36,7 +37,7 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     own_review = None
     if review is not None and not hasattr(review, "write_window"):
         from .review import ReviewWriter
-        review = own_review = ReviewWriter(review, crop_region, roi_mask, getattr(reader, "fps", 30.0), device=device)
+        review = own_review = ReviewWriter(review, crop_region, roi_mask, getattr(reader, "fps", 30.0), device=device, text=review_text)
     try:
         return _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_seg_size, device, keep_stages, windows_per_call,
                               export_dir, params, track_by_window, tracker, review)
@@ -138,19 +139,20 @@ def _track(tracker, popped, by_window):
             tracker.step(frame)
 
 
-def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, review=None, **kw):
+def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, review=None, review_text=False, **kw):
     """Decoded frames (oldest first) -> (swift count, events).  frames may also be a reader (get_n_frames / read_frame / total_frames,
     e.g. io_y4m.Y4MReader: its fps holds) or anything io_y4m.open_y4m opens: the path of a .y4m file (any format it reads), or a
     YUV4MPEG2 stream of unknown length -- "-" (standard input), a FIFO's path, a file descriptor, a binary file object (a pipe from a
-    decoder: proc.stdout).  Regions either explicit or from corners=...; params and review (a path or a
-    review.ReviewWriter: the review video of the count) as in swift_counting_algorithm."""
+    decoder: proc.stdout).  Regions either explicit or from corners=...; params, review (a path or a
+    review.ReviewWriter: the review video of the count) and review_text (text in a review made from a path) as in
+    swift_counting_algorithm."""
     opened = None
     if _is_video_source(frames):
         from .io_y4m import open_y4m
         frames = opened = open_y4m(frames)
     reader = frames if hasattr(frames, "get_n_frames") else ArrayReader(frames, fps=fps)
     try:
-        events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, review=review, **kw)
+        events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, review=review, review_text=review_text, **kw)
     finally:
         if opened is not None and hasattr(opened, "close"):
             opened.close()
@@ -228,7 +230,8 @@ def schedule_videos(readers, sizes, segment, consume, in_flight=4, windows_per_c
 
 
 def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows_per_call=1, classifier=None, queue_size=21,
-                        min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True, reviews=None):
+                        min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True, reviews=None,
+                        review_text=False):
     """count_swifts over a list of videos (the reference's loop over its video list, __main__.py:21), several videos at a time on one
     GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
     windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
@@ -237,21 +240,22 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
     videos: readers (read_frame / get_n_frames / total_frames), decoded frame arrays (oldest first) or what io_y4m.open_y4m opens (a
     .y4m path, "-", a FIFO, a descriptor, a binary file object); regions: per video
     (crop_region, roi_mask), or corners: per video the chimney's top edge (the regions then come from its first frame, :62-63).
-    reviews: per video a path, a review.ReviewWriter or None -- that video's review video (swift_counting_algorithm's review=).
+    reviews: per video a path, a review.ReviewWriter or None -- that video's review video (swift_counting_algorithm's review=);
+    review_text: the writers made here from paths also write text (its review_text=).
     Returns [(count, events), ...] in input order."""
     from .io_y4m import open_y4m
     readers = [open_y4m(v) if _is_video_source(v) else v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
     opened = [r for r, v in zip(readers, videos) if r is not v and hasattr(r, "close")]          # (closed again when the count is done)
     try:
         return _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device,
-                             pad_factor, params, track_by_window, reviews)
+                             pad_factor, params, track_by_window, reviews, review_text)
     finally:
         for r in opened:
             r.close()
 
 
 def _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device, pad_factor, params,
-                  track_by_window=True, reviews=None):
+                  track_by_window=True, reviews=None, review_text=False):
     """count_swifts_videos over readers."""
     if regions is None:
         if corners is None:
@@ -276,7 +280,7 @@ def _count_videos(readers, regions, corners, in_flight, windows_per_call, classi
         for v, rv in enumerate(reviews):
             if rv is not None and not hasattr(rv, "write_window"):
                 from .review import ReviewWriter
-                reviews[v] = ReviewWriter(rv, regions[v][0], regions[v][1], getattr(readers[v], "fps", 30.0), device=device)
+                reviews[v] = ReviewWriter(rv, regions[v][0], regions[v][1], getattr(readers[v], "fps", 30.0), device=device, text=review_text)
                 own_reviews.append(reviews[v])
         seen = [0] * len(readers)                    # events already handed to each video's review
         removed = {}                                 # id(frame) -> the boxes the classifier removed from it, until its window is written

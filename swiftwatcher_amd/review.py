@@ -2,7 +2,13 @@
 counted drawn in -- the segments, the segments the classifier threw away, the ROI mask, and the tracker's events.  The reference
 shows its users the same with `--export`, one overlay PNG per segment (data_structures.py:65-113); here a window's frames are
 composed and converted by one GPU call (swk_render_review, include/swk.h) and leave with one device-to-host copy and one file
-write.  pipeline.swift_counting_algorithm / count_swifts / count_swifts_videos feed a writer through review= / reviews=."""
+write.  pipeline.swift_counting_algorithm / count_swifts / count_swifts_videos feed a writer through review= / reviews=.
+
+With text=True (review_text=True there, --review-text on the command line) every frame also carries the keys of the count's tables
+as text, drawn by the same call (swk_render_review_labels, the library's 5 x 7 font: space, 0-9, A-Z and # : . - + / = %): a status
+line with the frame number, the timestamp and the segment, removed-box and event counts, and the number #k of every event shown --
+row k of the events table."""
+import bisect
 import math
 
 import numpy as np
@@ -10,12 +16,37 @@ import numpy as np
 from . import _lib
 from .io_y4m import FRAME_MARK, Y4MWriter
 
-STYLE_SEGMENT, STYLE_REJECTED, STYLE_EVENT, STYLE_MASK = 1, 2, 3, 4
+STYLE_SEGMENT, STYLE_REJECTED, STYLE_EVENT, STYLE_MASK, STYLE_TEXT, STYLE_PLATE = 1, 2, 3, 4, 5, 6
 # (b, g, r, fill_alpha, line_alpha), alphas 0..256
 DEFAULT_STYLES = ((0, 255, 0, 32, 256),          # 1 segments: green outline, faint green fill
                   (0, 0, 255, 0, 160),           # 2 segments the classifier removed: red outline, no fill
                   (0, 255, 255, 0, 256),         # 3 events: yellow frame border and plus signs
-                  (255, 128, 0, 40, 0))          # 4 ROI mask: light blue tint
+                  (255, 128, 0, 40, 0),          # 4 ROI mask: light blue tint
+                  (255, 255, 255, 0, 256),       # 5 text ink: white
+                  (0, 0, 0, 160, 0))             # 6 text plate: black, 160 / 256
+STATUS_CELLS = 33                                # the status line's length while no field has widened
+LABEL_BYTES = 32                                 # a label's text (swk_review_label)
+_CHARSET = frozenset(b" 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ#:.-+/=%")
+
+
+def stamp_text(timestamp):
+    """A frame's timestamp as the status line shows it: HH:MM:SS.mmm from strftime where the timestamp has it (milliseconds cut, not
+    rounded); else its string, upper-cased and cut to 12 bytes, with bytes outside the font's character set replaced by spaces."""
+    if hasattr(timestamp, "strftime"):
+        return timestamp.strftime("%H:%M:%S.%f")[:12]
+    raw = str(timestamp).upper().encode("ascii", "replace")[:12]
+    return bytes(b if b in _CHARSET else 0x20 for b in raw).decode("ascii")
+
+
+def status_text(frame_number, timestamp, segments, removed, events):
+    """The status line: "F%06d %s S%02d R%02d E%03d" (fields widen when the number needs it)."""
+    return "F%06d %s S%02d R%02d E%03d" % (frame_number, stamp_text(timestamp), segments, removed, events)
+
+
+def text_scale_for(width, height, border):
+    """The default text scale of a width x height review: the largest at which the status line fits between the borders and takes no
+    more than an eighth of the height, 1..4."""
+    return max(1, min(4, (width - 2 * border) // (6 * STATUS_CELLS + 1), (height // 8) // 9))
 
 
 def centroid_pixel(centroid):
@@ -43,12 +74,27 @@ class ReviewWriter:
       2 rejected         (0, 0, 255, 0, 160)       red outline
       3 event            (0, 255, 255, 0, 256)     yellow border and plus signs
       4 ROI mask         (255, 128, 0, 40, 0)      light blue tint
-    styles= replaces it (at least four rows).  Output is 8-bit 4:2:0 only, the crop region only, and carries no text."""
+      5 text ink         (255, 255, 255, 0, 256)   white
+      6 text plate       (0, 0, 0, 160, 0)         black, 160 / 256
+    styles= replaces it (at least four rows; six with text=True).  Output is 8-bit 4:2:0 only, the crop region only.
+
+    text=True adds labels (layer 5, after the border; include/swk.h), at scale text_scale (1..8; None: text_scale_for, 2 at 424 x 212):
+      * a status line, status_text: "F000123 00:00:04.104 S03 R01 E007" -- frame number, timestamp (stamp_text), S = len(frame.segments),
+        R = boxes the classifier removed on this frame, E = events handed to the writer so far whose first shown frame
+        (event[-1].parent_frame_number + 1) is at or before this frame number.  Style 5 on plate 6, ink origin at row
+        height - BORDER - 8 scale, column BORDER + scale: the bottom-left corner, over the chimney.  A line of more than 32 bytes is
+        split into consecutive labels on the same row, 6 scale 32 pixels apart (their plates overlap by one unit).
+      * for every event shown on the frame, after the status line and in the events' order: "#k" in style 3 on plate 6, k the event's
+        1-based ordinal in the order the writer received events (its index in tracker.detected_events plus 1), with its ink origin
+        MARK_ARM + 2 scale below and right of the event's last centroid pixel, then moved up / left and then down / right so that the
+        label's rectangle (rows [r - scale, r + 8 scale), columns [c - scale, c + 6 scale len)) lies inside the border; where the
+        frame is too small for that, its top / left side does.
+    The character set has no lower case, and the two positions are fixed."""
 
     MARK_ARM = 4
     BORDER = 3
 
-    def __init__(self, path, crop_region, roi_mask, fps, device=0, styles=None, event_hold=15):
+    def __init__(self, path, crop_region, roi_mask, fps, device=0, styles=None, event_hold=15, text=False, text_scale=None):
         (x0, y0), (x1, y1) = crop_region
         self.crop_region = [(int(x0), int(y0)), (int(x1), int(y1))]
         self.height, self.width = int(y1) - int(y0), int(x1) - int(x0)
@@ -60,9 +106,18 @@ class ReviewWriter:
             raise ValueError("styles holds at least four rows (b, g, r, fill_alpha, line_alpha)")
         if event_hold < 1:
             raise ValueError("event_hold is at least 1 frame")
+        self.text = bool(text)
+        if self.text and len(self.styles) < 6:
+            raise ValueError("text=True needs six styles (5: the text's ink, 6: its plate)")
+        self.text_scale = int(text_scale) if text_scale is not None else text_scale_for(self.width, self.height, self.BORDER)
+        if not 1 <= self.text_scale <= 8:
+            raise ValueError("text_scale is 1..8")
         self.device, self.event_hold = device, int(event_hold)
         self.frames = 0
-        self._pending = []               # events still to be shown: (first frame number, last frame number, ((row, column), ...))
+        self._pending = []               # events still to be shown: (first frame number, last frame number, ((row, column), ...), ordinal)
+        self._received = 0               # events received so far: the next event's ordinal is this + 1
+        self._firsts = []                # the first shown frame of every event received, ascending (the status line's E)
+        self._shown = []                 # of the last plan_window: per written frame (events counted so far, ((ordinal, last point), ...))
         self._dev = self._dev_bytes = 0
         self._host = None
         hc, wc = (self.height + 1) // 2, (self.width + 1) // 2
@@ -76,9 +131,12 @@ class ReviewWriter:
         swk_render_review takes it, `frame` counting the written frames.  Takes the new events in and forgets those that are over."""
         for event in new_events:
             first = int(event[-1].parent_frame_number) + 1
-            self._pending.append((first, first + self.event_hold - 1, tuple(centroid_pixel(s.centroid) for s in event)))
+            self._received += 1
+            self._pending.append((first, first + self.event_hold - 1, tuple(centroid_pixel(s.centroid) for s in event), self._received))
+            bisect.insort(self._firsts, first)
         rejected = rejected if rejected is not None else [()] * len(popped_frames)
         frames, boxes, marks, frame_style = [], [], [], []
+        self._shown = []
         for frame, gone in zip(popped_frames, rejected):
             if frame.frame_number < 0:
                 continue
@@ -86,20 +144,43 @@ class ReviewWriter:
             frames.append(frame)
             boxes.extend((k,) + tuple(int(v) for v in s.bbox) + (STYLE_SEGMENT,) for s in frame.segments)
             boxes.extend((k,) + tuple(int(v) for v in bbox) + (STYLE_REJECTED,) for bbox in (gone or ()))
-            style = 0
-            for first, last, points in self._pending:
+            style, shown = 0, []
+            for first, last, points, ordinal in self._pending:
                 if first <= frame.frame_number <= last:
                     style = STYLE_EVENT
                     marks.extend((k, r, c, STYLE_EVENT) for r, c in points)
+                    shown.append((ordinal, points[-1]))
             frame_style.append(style)
+            self._shown.append((bisect.bisect_right(self._firsts, frame.frame_number), tuple(shown)))
         if frames:
             newest = max(f.frame_number for f in frames)
             self._pending = [ev for ev in self._pending if ev[1] > newest]
         return frames, boxes, marks, frame_style
 
-    def _render(self, frames, boxes, marks, frame_style):
+    def plan_labels(self, plan):
+        """The labels of the window plan_window has just planned (plan = its four-tuple), as swk_render_review_labels takes them:
+        tuples (frame, r, c, style, plate, scale, text), per written frame the status line's labels, then the shown events' numbers."""
+        frames, boxes = plan[0], plan[1]
+        removed = [0] * len(frames)
+        for box in boxes:
+            if box[5] == STYLE_REJECTED:
+                removed[box[0]] += 1
+        s, labels = self.text_scale, []
+        for k, (frame, (counted, shown)) in enumerate(zip(frames, self._shown)):
+            line = status_text(frame.frame_number, getattr(frame, "timestamp", ""), len(frame.segments), removed[k], counted)
+            for at in range(0, len(line), LABEL_BYTES):
+                labels.append((k, self.height - self.BORDER - 8 * s, self.BORDER + s + 6 * s * at, STYLE_TEXT, STYLE_PLATE, s,
+                               line[at:at + LABEL_BYTES]))
+            for ordinal, (row, col) in shown:
+                text = "#%d" % ordinal
+                r = max(min(row + self.MARK_ARM + 2 * s, self.height - self.BORDER - 8 * s), self.BORDER + s)
+                c = max(min(col + self.MARK_ARM + 2 * s, self.width - self.BORDER - 6 * s * len(text)), self.BORDER + s)
+                labels.append((k, r, c, STYLE_EVENT, STYLE_PLATE, s, text))
+        return labels
+
+    def _render(self, frames, boxes, marks, frame_style, labels=None):
         """The window's frames composed and converted on the GPU: a uint8 array of len(frames) * frame bytes, every frame as the file
-        holds it (the FRAME mark, then the Y, U and V planes), in page-locked memory."""
+        holds it (the FRAME mark, then the Y, U and V planes), in page-locked memory.  labels: None, or the window's labels."""
         from .data_structures import stack_frames
         ctx = _lib.default_context(self.device)
         stack, (rx, ry), (Hc, Wc), backwards = stack_frames([f.frame for f in frames], self.crop_region, (0, 0), ctx.staging, self.device)
@@ -116,8 +197,9 @@ class ReviewWriter:
         dst = _lib.Yuv420Dst(y=base + mark, u=base + mark + self._luma, v=base + mark + self._luma + self._chroma,
                              mem=_lib.MEM_DEVICE, layout=_lib.YUV_I420, y_row_stride=self.width, y_frame_stride=fb,
                              c_row_stride=(self.width + 1) // 2, c_frame_stride=fb)
+        extra = {} if labels is None else {"labels": labels}          # (without text: the call as it always was)
         ctx.render_review(stack, boxes=boxes, marks=marks, frame_style=frame_style, mask=self.roi_mask, styles=self.styles,
-                          mask_style=STYLE_MASK, mark_arm=self.MARK_ARM, border=self.BORDER, rect=(rx, ry, Wc, Hc), dst=dst)
+                          mask_style=STYLE_MASK, mark_arm=self.MARK_ARM, border=self.BORDER, rect=(rx, ry, Wc, Hc), dst=dst, **extra)
         out = self._host[:F * fb]
         ctx._check(ctx._lib.swk_device_read(ctx._h, base, out.ctypes.data, F * fb))          # one device -> host copy
         out.reshape(F, fb)[:, :mark] = np.frombuffer(FRAME_MARK, np.uint8)
@@ -126,10 +208,14 @@ class ReviewWriter:
     def write_window(self, popped_frames, rejected=None, new_events=()):
         """One window's popped Frame objects, oldest first; rejected: per frame the boxes (r0, c0, r1, c1) the classifier removed, or
         None; new_events: the events the tracker found in this window (lists of Segment objects)."""
-        frames, boxes, marks, frame_style = self.plan_window(popped_frames, rejected, new_events)
+        frames, boxes, marks, frame_style = plan = self.plan_window(popped_frames, rejected, new_events)
         if not frames:
             return
-        self._writer._fh.write(self._render(frames, boxes, marks, frame_style))          # one file write
+        if self.text:
+            out = self._render(frames, boxes, marks, frame_style, labels=self.plan_labels(plan))
+        else:
+            out = self._render(frames, boxes, marks, frame_style)
+        self._writer._fh.write(out)          # one file write
         self._writer.frames += len(frames)
         self.frames = self._writer.frames
 

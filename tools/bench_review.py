@@ -6,7 +6,10 @@
 2. The counting loop: pipeline.count_swifts over a seeded synthetic clip (crop region 424 x 212) with and without review=, alternating
    round by round, the review written to --out (a file on the local disk).  Reports frames/s of each, their ratio, and what the
    review's frames weigh, so the loop's extra time can be set against the device-to-host copy plus the file write.
-    python tools/bench_review.py [--reps 50] [--rounds 5] [--frames 210] [--windows-per-call 2] [--out /tmp/review_bench.y4m]"""
+--text adds the review's text (swk_render_review_labels): a kernel row "render_text" -- the same overlay plus a status line (two labels)
+and two event numbers on every frame, at the writer's default scale for the size -- and, in the loop, a review with review_text=True
+beside the one without, in the same alternation.
+    python tools/bench_review.py [--text] [--reps 50] [--rounds 5] [--frames 210] [--windows-per-call 2] [--out /tmp/review_bench.y4m]"""
 import argparse
 import json
 import os
@@ -21,9 +24,22 @@ from swiftwatcher_amd import _lib          # noqa: E402
 
 PEAK = 8.0e12
 STYLES = [(0, 255, 0, 32, 256), (0, 0, 255, 0, 160), (0, 255, 255, 0, 256), (255, 128, 0, 40, 0)]
+TEXT_STYLES = STYLES + [(255, 255, 255, 0, 256), (0, 0, 0, 160, 0)]
 
 
-def kernel_rows(ctx, reps):
+def text_labels(F, Hc, Wc, rng):
+    """Per frame what ReviewWriter(text=True) draws on an event frame: the status line (33 bytes: two labels) and two event numbers."""
+    from swiftwatcher_amd.review import ReviewWriter, status_text, text_scale_for
+    s, B = text_scale_for(Wc, Hc, ReviewWriter.BORDER), ReviewWriter.BORDER
+    labels = []
+    for f in range(F):
+        line = status_text(f, "00:00:%02d.%03d" % (f // 30, f % 30 * 33), 12, 1, f // 5)
+        labels += [(f, Hc - B - 8 * s, B + s + 6 * s * at, 5, 6, s, line[at:at + 32]) for at in range(0, len(line), 32)]
+        labels += [(f, int(rng.integers(B + s, Hc - B - 8 * s)), int(rng.integers(B + s, Wc - B - 18 * s)), 3, 6, s, "#%d" % (f + k)) for k in (1, 2)]
+    return labels
+
+
+def kernel_rows(ctx, reps, text=False):
     import torch
     g = torch.Generator(device="cuda:0")
     g.manual_seed(1)
@@ -41,6 +57,10 @@ def kernel_rows(ctx, reps):
         calls = {"convert": lambda: ctx.bgr_to_yuv420(frames, device_out=True),
                  "render": lambda: ctx.render_review(frames, boxes=boxes, marks=marks, frame_style=frame_style, mask=mask, styles=STYLES,
                                                      mask_style=4, mark_arm=4, border=3, device_out=True)}
+        if text:
+            labels = _lib.label_records(text_labels(F, Hc, Wc, rng))
+            calls["render_text"] = lambda: ctx.render_review(frames, boxes=boxes, marks=marks, frame_style=frame_style, mask=mask, styles=TEXT_STYLES,
+                                                             mask_style=4, mark_arm=4, border=3, device_out=True, labels=labels)
         moved = F * Hc * Wc * 4.5
         for name, call in calls.items():
             for _ in range(3):
@@ -57,7 +77,7 @@ def kernel_rows(ctx, reps):
     return out
 
 
-def loop_rows(frames_n, rounds, wpc, path):
+def loop_rows(frames_n, rounds, wpc, path, text=False):
     from swiftwatcher_amd import pipeline, synthetic
     crop = [(28, 29), (28 + 424, 29 + 212)]
     frames = synthetic.full_frames(500, frames_n, crop, frame_hw=(270, 480))[::-1].copy()
@@ -66,16 +86,23 @@ def loop_rows(frames_n, rounds, wpc, path):
     kw = dict(crop_region=crop, roi_mask=roi_mask, windows_per_call=wpc)
     want = pipeline.count_swifts(frames, **kw)                                   # warm-up, and the count both variants must give
     pipeline.count_swifts(frames, review=path, **kw)
-    times = {"plain": [], "review": []}
+    names = ("plain", "review", "text") if text else ("plain", "review")
+    if text:
+        pipeline.count_swifts(frames, review=path, review_text=True, **kw)
+    times = {name: [] for name in names}
     for _ in range(rounds):
-        for name in ("plain", "review"):
+        for name in names:
             t0 = time.perf_counter()
-            got = pipeline.count_swifts(frames, review=path if name == "review" else None, **kw)
+            got = pipeline.count_swifts(frames, review=None if name == "plain" else path, review_text=name == "text", **kw)
             times[name].append(time.perf_counter() - t0)
             assert got[0] == want[0] and len(got[1]) == len(want[1])
     size = os.path.getsize(path)
     med = {k: float(np.median(v)) for k, v in times.items()}
-    return [{"bench": "review_loop", "frames": frames_n, "windows_per_call": wpc, "crop": [424, 212], "events": len(want[1]),
+    more = {}
+    if text:
+        more = {"text_fps": round(frames_n / med["text"], 1), "text_s": [round(t, 4) for t in times["text"]],
+                "text_over_review": round(med["text"] / med["review"], 4), "text_extra_ms_per_frame": round((med["text"] - med["review"]) / frames_n * 1e3, 4)}
+    return [{**more, "bench": "review_loop", "frames": frames_n, "windows_per_call": wpc, "crop": [424, 212], "events": len(want[1]),
              "plain_fps": round(frames_n / med["plain"], 1), "review_fps": round(frames_n / med["review"], 1),
              "plain_s": [round(t, 4) for t in times["plain"]], "review_s": [round(t, 4) for t in times["review"]],
              "review_over_plain": round(med["review"] / med["plain"], 4), "review_extra_ms_per_frame": round((med["review"] - med["plain"]) / frames_n * 1e3, 4),
@@ -84,6 +111,7 @@ def loop_rows(frames_n, rounds, wpc, path):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--text", action="store_true", help="also measure the review with text (labels)")
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--frames", type=int, default=210)
@@ -91,10 +119,10 @@ def main():
     ap.add_argument("--out", default=os.path.join("/tmp", "review_bench.y4m"))
     a = ap.parse_args()
     ctx = _lib.default_context(0)
-    for row in kernel_rows(ctx, a.reps):
+    for row in kernel_rows(ctx, a.reps, a.text):
         print(json.dumps(row), flush=True)
     for wpc in sorted({1, a.windows_per_call}):
-        for row in loop_rows(a.frames, a.rounds, wpc, a.out):
+        for row in loop_rows(a.frames, a.rounds, wpc, a.out, a.text):
             print(json.dumps(row), flush=True)
 
 
