@@ -141,9 +141,11 @@ int32_t swk_debug_tracker_force_assignment(swk_tracker *t, int32_t skip_frames, 
 
 /* ---- classifier kernels: A/B switches ---- */
 /* Measurement knobs of the classifier kernels (A/B runs).  knob 0: workgroup layout of the 1 x 1 kernel (0 = 16-wave workgroups, the
- * default; 1 = 8 waves with the deepest activation ring that fits; results do not depend on it).  knob 1: 1 = the Fire modules' expand1x1
- * shapes run on the split-bf16 kernel (float32 products as six bf16 MFMA products of three-way split operands: float32-accurate, another
- * summation order); 0 = the default, the float32 kernel.  knob 2: workgroup layout of the split-bf16 Winograd 3 x 3 expands (results do
+ * default; 1 = 8 waves with the deepest activation ring that fits; results do not depend on it).  knob 1, the Fire modules' expand1x1
+ * shapes: 0 = the float32 kernel; 1 = the split-bf16 kernel with its weights in LDS (float32 products as six bf16 MFMA products of
+ * three-way split operands: float32-accurate, another summation order than the float32 kernel's); 2 = the split-bf16 kernel with its
+ * weights in registers (the same results as 1, bit for bit); 3 = the default: each shape's own choice of these, the same at every batch
+ * size (today 2 for all four shapes).  knob 2: workgroup layout of the split-bf16 Winograd 3 x 3 expands (results do
  * not depend on it, bit for bit): 0 = each shape's default, 1 = one column block and two tile groups of 32 tiles per wave for every
  * shape, 2 = two waves per column block sharing one filter slice (48 -> 192 as 12 waves, 64 -> 256 as 16, 32 -> 128 as 8 waves over 128
  * tiles) for every shape that has such a layout.  Any other knob or value: SWK_ERR_ARG. */

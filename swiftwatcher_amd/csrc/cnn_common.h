@@ -33,7 +33,12 @@ inline bool place_ok(const Place &p, int h, int w, int c, bool quads, const Crop
 // expand1x1 of the Fire shapes with float32 products formed from split bf16 operands (cnn_expand_bf16.hip); SWK_ERR_ARG for other shapes
 int launch_expand1x1_split_bf16(hipStream_t s, const float *src, int64_t rows, const Crop &cr, int cin, int h, int w, const float *wgt,
                                 const float *bias, int cout, const Place &pl);
-extern int g_expand_split_bf16;          // A/B switch (swk_set_cnn_tuning knob 1): 1 = the split-bf16 kernel for the expand1x1 shapes
+// the same products, bit for bit, with the split weights held in registers and the split activations shared through LDS
+int launch_expand1x1_split_bf16_ws(hipStream_t s, const float *src, int64_t rows, const Crop &cr, int cin, int h, int w, const float *wgt,
+                                   const float *bias, int cout, const Place &pl);
+// A/B switch (swk_set_cnn_tuning knob 1) for the expand1x1 shapes: 0 = the float32 kernel, 1 = the split-bf16 kernel with its weights in
+// LDS, 2 = the split-bf16 kernel with its weights in registers, 3 = each shape's default (swk_nhwc_conv1x1_bias_relu_place)
+extern int g_expand_split_bf16;
 extern int g_wino_bf16s_layout;          // A/B switch (swk_set_cnn_tuning knob 2): workgroup layout of the split-bf16 Winograd expands
 
 // The fused epilogue: register quad g of an accumulator = four consecutive output channels of the lane's pixel; bias, ReLU, one

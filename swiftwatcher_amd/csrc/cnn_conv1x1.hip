@@ -159,9 +159,15 @@ static int launch_conv1x1_d(hipStream_t s, const float *src, int64_t rows, const
     return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
 }
 
-int g_expand_split_bf16 = getenv("SWK_EXPAND_SPLIT_BF16") ? atoi(getenv("SWK_EXPAND_SPLIT_BF16")) : 0;
+int g_expand_split_bf16 = getenv("SWK_EXPAND_SPLIT_BF16") ? atoi(getenv("SWK_EXPAND_SPLIT_BF16")) : 3;
 int g_conv1x1_ring = 0;          // A/B knob: 0 = 16-wave workgroups, column blocks of the wide expands split over two waves; 1 = the
                                  // first layout (8 waves, every wave all column blocks, activation ring as deep as fits)
+
+// knob 1 = 3 (the default): the kernel each Fire expand1x1 shape takes, as a value of the knob
+static int expand1x1_default_route(int cin)
+{
+    return cin == 16 || cin == 32 || cin == 48 || cin == 64 ? 2 : 0;
+}
 
 #define SWK_C1_ARGS s, src, rows, cr, cin, h, w, wgt, bias, cout, pl
 template <int NBLK>
@@ -221,7 +227,11 @@ int32_t swk_nhwc_conv1x1_bias_relu_place(void *stream, const float *src, int32_t
     const int64_t rows = (int64_t)n * h * w;
     hipStream_t s = (hipStream_t)stream;
     if (g_expand_split_bf16 && cout == 4 * cin) {          // the Fire modules' expand1x1 shapes: float32 products from split bf16 operands
-        const int rc = launch_expand1x1_split_bf16(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
+        // The default is a choice per shape and never per size: the split products sum in another order than the float32 kernel's, and a
+        // segment's scores must not depend on the batch it is scored in.  The two split kernels give the same bits.
+        const int route = g_expand_split_bf16 == 3 ? expand1x1_default_route(cin) : g_expand_split_bf16;
+        const int rc = route == 2 ? launch_expand1x1_split_bf16_ws(s, src, rows, cr, cin, h, w, weight, bias, cout, pl)
+                     : route == 1 ? launch_expand1x1_split_bf16(s, src, rows, cr, cin, h, w, weight, bias, cout, pl) : SWK_ERR_ARG;
         if (rc != SWK_ERR_ARG) return rc;
     }
     switch ((cout + 31) / 32) {
@@ -236,14 +246,15 @@ int32_t swk_nhwc_conv1x1_bias_relu_place(void *stream, const float *src, int32_t
 }
 
 // Measurement knobs of the classifier kernels (A/B runs).  knob 0: activation ring of the 1x1 kernel (0 = deepest that fits, 1 = one chunk
-// in flight; results do not depend on it).  knob 1: 1 = expand1x1 shapes on the split-bf16 kernel (cnn_expand_bf16.hip: float32-accurate,
-// another summation order than the float32 kernel's, so scores move in the last bits); 0, the default: every 1x1 on the float32 kernel.
+// in flight; results do not depend on it).  knob 1, the expand1x1 shapes: 0 = every 1x1 on the float32 kernel; 1 = the split-bf16 kernel with
+// its weights in LDS (cnn_expand_bf16.hip: float32-accurate, another summation order than the float32 kernel's, so scores move in the last
+// bits); 2 = the split-bf16 kernel with its weights in registers (the same bits as 1); 3, the default: each shape's own choice of these.
 // knob 2: workgroup layout of the split-bf16 Winograd expands (cnn_wino3x3_bf16s.hip; results do not depend on it): 0 = each shape's default,
 // 1 = one column block and two tile groups per wave for every shape, 2 = the shared-filter layout for every shape that has one.
 int32_t swk_set_cnn_tuning(int32_t knob, int32_t value)
 {
     if (knob == 0 && (value == 0 || value == 1)) { swk::g_conv1x1_ring = value; return SWK_OK; }
-    if (knob == 1 && (value == 0 || value == 1)) { swk::g_expand_split_bf16 = value; return SWK_OK; }
+    if (knob == 1 && value >= 0 && value <= 3) { swk::g_expand_split_bf16 = value; return SWK_OK; }
     if (knob == 2 && value >= 0 && value <= 2) { swk::g_wino_bf16s_layout = value; return SWK_OK; }
     return SWK_ERR_ARG;
 }
