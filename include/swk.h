@@ -358,6 +358,51 @@ void swk_review_font(uint8_t out[128][8]);
 int32_t swk_render_review_labels(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels,
                                  int32_t nlabels, swk_yuv420_dst *dst);
 
+/* ---- review video, stage images: a mosaic of panels beside the composed frame -------------------------------------
+ * A review frame shows what was counted; a stage image (swk_output's gray, rpca, bilateral, thresh, opened, labels: u8 planes)
+ * shows why.  swk_render_review_panels writes both into one 4:2:0 frame, a grid of equal cells.
+ *
+ * Geometry: Hp = Hc + (Hc & 1), Wp = Wc + (Wc & 1), cells = 1 + npanels, rows = ceil(cells / cols).  dst describes frames of
+ * rows * Hp by cols * Wp luma pixels, their chroma planes exactly half of that per side.  Cell k has its origin at luma
+ * ((k / cols) * Hp, (k % cols) * Wp): always even, so no chroma sample belongs to two cells.
+ *
+ * Cell 0 holds what swk_render_review_labels(ctx, in, rv, labels, nlabels, ...) writes for an Hc x Wc destination.  Cell k >= 1
+ * holds what swk_render_review_labels would write for a 3-channel source whose pixel (r, c) of frame f is the mapped value v of
+ * panels[k - 1]'s plane: SWK_PANEL_GRAY B = G = R = min(255, v * gain); SWK_PANEL_LABELS (B, G, R) = palette[v].  It is composed
+ * with those of rv's layers 1..4 (mask, boxes, marks, border) whose bit (0..3) is set in `layers`, frame indices being the same f,
+ * and with the panel's caption as its only label (layer 5; .frame is ignored, it is drawn on every frame; len 0: none).  Same
+ * blend, same conversion, same top-left chroma sampling.  Every other luma sample is 16 and every other chroma sample 128: the pad
+ * row / column of an odd Hc / Wc in every cell (cell 0's too) and the cells of the last row after `cells`.  Bytes of dst outside
+ * the mosaic (row strides above the row) are not written.
+ *
+ * The palette is the library's own (csrc/review.hip): palette[0] = (0, 0, 0); for v >= 1 hue (v - 1) % 12 of
+ *   (0,0,255) (0,255,0) (255,0,0) (0,255,255) (255,0,255) (255,255,0) (0,128,255) (128,255,0) (255,0,128) (255,128,0) (128,0,255)
+ *   (0,255,128)                                                                                       (B, G, R)
+ * with every channel scaled (x * s) >> 8, s = 256, 176, 112 for ((v - 1) / 12) % 3 = 0, 1, 2: no entry above 0 is black and
+ * palette[v] != palette[v + 1].  swk_review_label_palette (host only, no context) copies it out. */
+#define SWK_PANEL_GRAY   0   /* B = G = R = min(255, v * gain) */
+#define SWK_PANEL_LABELS 1   /* B, G, R = palette[v]; palette[0] = black */
+typedef struct swk_review_panel {
+    const uint8_t *plane;            /* u8; frame f, pixel (r, c) at plane + f * frame_stride + r * row_stride + c */
+    int32_t mem, kind;               /* SWK_MEM_HOST / SWK_MEM_DEVICE; SWK_PANEL_* */
+    int64_t frame_stride, row_stride;/* bytes; frame_stride may be negative (as swk_input), row_stride >= Wc */
+    int32_t gain;                    /* GRAY: 1..255; LABELS: ignored */
+    int32_t layers;                  /* bit 0..3: layers 1..4 of swk_render_review (mask, boxes, marks, border) drawn on this panel */
+    swk_review_label caption;        /* .frame ignored; len 0: none; drawn on every frame of the panel as its only label */
+} swk_review_panel;
+
+void swk_review_label_palette(uint8_t out[256][3]);   /* host only, no context: B, G, R per label value */
+
+/* rv must not be null.  Device planes are read where they lie; of a host plane the Hc x Wc pixels of every frame are copied up.
+ * With npanels == 0, cols == 1 and even Hc and Wc the call equals swk_render_review_labels bit for bit.  SWK_ERR_ARG, before
+ * anything is copied or launched and with dst untouched, besides swk_render_review_labels' list: npanels outside 0..15, cols
+ * outside 1..16, null panels with npanels > 0, a null plane, an unknown kind or mem, gain outside 1..255 on a GRAY panel,
+ * row_stride < Wc, layers outside 0..15, a caption that swk_render_review_labels would refuse (scale, len, style, plate, a byte
+ * outside the font's set), a dst row stride below the mosaic's row.  SWK_ERR_CAPACITY: a mosaic side above 32768. */
+int32_t swk_render_review_panels(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels,
+                                 int32_t nlabels, const swk_review_panel *panels, int32_t npanels, int32_t cols,
+                                 swk_yuv420_dst *dst);
+
 /* ---- stage-level entry points (host buffers; used by the parity tests and by the
  *      image_filtering.* drop-in functions) ------------------------------------- */
 /* convert_grayscale (image_filtering.py:188-196): [count][H][W][3] -> [count][H][W] */

@@ -1,5 +1,5 @@
 """python -m swiftwatcher_amd SOURCE [SOURCE ...] (--corners X1,Y1,X2,Y2 | --attributes FILE) [--start N] [--end N]
-       [--classify WEIGHTS] [--out DIR] [--review PATH [--review-text]] [--windows-per-call K] [--device D]
+       [--classify WEIGHTS] [--out DIR] [--review PATH [--review-text] [--review-stages LIST]] [--windows-per-call K] [--device D]
 
 The reference's main() (__main__.py:13-53) without its UI: every SOURCE -- a .y4m file, or "-" for a YUV4MPEG2 stream on standard
 input (`ffmpeg -i evening.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners 812,640,1105,642`) -- is counted by
@@ -11,7 +11,8 @@ count (review.py: the crop region as a 4:2:0 .y4m with segments, removed segment
 several sources are given).  PATH may be a FIFO (`--review fifo & ffmpeg -i fifo out.mp4`), not "-": standard output carries the
 JSON lines.  --review-text (with --review only) writes the tables' keys into every frame of the review: a status line "F000123
 00:00:04.104 S03 R01 E007" (frame number, timestamp, segments, boxes the classifier removed, events so far) and the number #k of
-every event shown, k its row in the events table."""
+every event shown, k its row in the events table.  --review-stages rpca,thresh,labels (with --review only; combines with
+--review-text) puts those stage images of every frame beside it as captioned panels: keys gray rpca bilateral thresh opened labels."""
 import argparse
 import json
 import os
@@ -46,6 +47,14 @@ def _review_path(text):
     return text
 
 
+def _stage_list(text):
+    from .review import stage_keys
+    try:
+        return stage_keys(text)
+    except ValueError as exc:
+        raise argparse.ArgumentTypeError(str(exc))
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m swiftwatcher_amd", description="Count chimney swifts in YUV4MPEG2 videos on the MI355X.")
     p.add_argument("sources", nargs="+", metavar="SOURCE", help="a .y4m file, or - for a YUV4MPEG2 stream on standard input")
@@ -58,6 +67,8 @@ def build_parser():
     p.add_argument("--out", metavar="DIR", help="write the result tables (CSV) here")
     p.add_argument("--review", type=_review_path, metavar="PATH", help="write a review video (.y4m) of the count here")
     p.add_argument("--review-text", action="store_true", help="with --review: draw frame number, time, counts and event numbers into it")
+    p.add_argument("--review-stages", type=_stage_list, default=(), metavar="LIST",
+                   help="with --review: stage images shown as panels beside every frame, e.g. rpca,thresh,labels")
     p.add_argument("--windows-per-call", type=int, default=1, metavar="K", help="queue-fuls segmented per GPU call")
     p.add_argument("--device", type=int, default=0, metavar="D", help="GPU index")
     return p
@@ -73,6 +84,8 @@ def plan(argv):
         parser.error("--start and --end are frame numbers, --windows-per-call is at least 1")
     if args.review_text and not args.review:
         parser.error("--review-text needs --review PATH")
+    if args.review_stages and not args.review:
+        parser.error("--review-stages needs --review PATH")
     shared = None
     try:
         if args.corners is not None:
@@ -121,7 +134,8 @@ def main(argv=None):
             review = os.path.join(review, stem + ".y4m")
         try:
             count, events = pipeline.count_swifts(reader, corners=corners, classifier=classifier, device=args.device,
-                                                  windows_per_call=args.windows_per_call, review=review or None, review_text=args.review_text)
+                                                  windows_per_call=args.windows_per_call, review=review or None, review_text=args.review_text,
+                                                  review_stages=args.review_stages)
             frames, fps, first, last = reader.total_frames, reader.fps, reader.start_frame, reader.end_frame
         except (OSError, ValueError) as exc:
             print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)

@@ -111,6 +111,29 @@ REVIEW_LABEL_DTYPE = np.dtype([("frame", "<i4"), ("r", "<i4"), ("c", "<i4"), ("s
 assert REVIEW_LABEL_DTYPE.itemsize == 64
 
 
+class ReviewLabel(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int32) for name in ("frame", "r", "c", "style", "plate", "scale", "len", "reserved_")] + [("text", ctypes.c_uint8 * 32)]
+
+
+class ReviewPanel(ctypes.Structure):
+    _fields_ = [("plane", ctypes.c_void_p), ("mem", ctypes.c_int32), ("kind", ctypes.c_int32), ("frame_stride", ctypes.c_int64),
+                ("row_stride", ctypes.c_int64), ("gain", ctypes.c_int32), ("layers", ctypes.c_int32), ("caption", ReviewLabel)]
+
+
+assert ctypes.sizeof(ReviewLabel) == 64 and ctypes.sizeof(ReviewPanel) == 104
+PANEL_GRAY, PANEL_LABELS = 0, 1
+MAX_PANELS, MAX_PANEL_COLS = 15, 16
+
+
+def panel_layout(Hc, Wc, cells, cols):
+    """The mosaic of swk_render_review_panels: (height, width, origins) -- `cells` cells of Hp x Wp luma pixels (Hc, Wc made even) in
+    rows of `cols`; origins[k] = (row, column) of cell k's first luma pixel, always even."""
+    if Hc < 1 or Wc < 1 or cells < 1 or cols < 1:
+        raise ValueError("a mosaic has at least one cell of at least one pixel, in at least one column")
+    Hp, Wp = Hc + (Hc & 1), Wc + (Wc & 1)
+    rows = (cells + cols - 1) // cols
+    return rows * Hp, cols * Wp, [((k // cols) * Hp, (k % cols) * Wp) for k in range(cells)]
+
 
 def label_records(labels):
     """REVIEW_LABEL_DTYPE records of tuples (frame, r, c, style, plate, scale, text), text a str (ASCII) or bytes of at most 32 bytes;
@@ -129,6 +152,13 @@ def label_records(labels):
         out[name] = rows[:, k]
     out["len"] = [len(raw) for raw in texts]
     out["text"] = np.frombuffer(b"".join(raw.ljust(32, b"\0") for raw in texts), np.uint8).reshape(-1, 32)
+    return out
+
+
+def review_label_palette():
+    """swk_review_label_palette: uint8 (256, 3) -- (b, g, r) of label value v in a SWK_PANEL_LABELS panel; row 0 is black."""
+    out = np.zeros((256, 3), np.uint8)
+    load().swk_review_label_palette(out.ctypes.data)
     return out
 
 
@@ -159,6 +189,9 @@ _SIGS = {
     "swk_render_review_labels": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Review), ctypes.c_void_p, ctypes.c_int32,
                                                   ctypes.POINTER(Yuv420Dst)]),
     "swk_review_font": (None, [ctypes.c_void_p]),
+    "swk_render_review_panels": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Review), ctypes.c_void_p, ctypes.c_int32,
+                                                  ctypes.POINTER(ReviewPanel), ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(Yuv420Dst)]),
+    "swk_review_label_palette": (None, [ctypes.c_void_p]),
     "swk_bgr2gray": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "swk_ialm": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_rpca_epilogue": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
@@ -613,12 +646,13 @@ class Context:
         res["generation"] = self.batch_run_raw(inp, params or default_params(), out)          # for swk_segment_inputs_last
         return res
 
-    def batch_run_groups(self, groups, params=None, stages=STAGES, want_A=False, want_E=False, seg_cap=255):
+    def batch_run_groups(self, groups, params=None, stages=STAGES, want_A=False, want_E=False, seg_cap=255, device_stages=False):
         """swk_batch_run_groups: several groups of windows (one video's windows each, each with its own geometry) in ONE call.
         groups: dicts with batch_run's per-batch arguments -- frames, nwin, n, and optionally crop, reverse_frames, seg_cap.
         frames may also be a device tensor (torch, on this context's GPU, C-contiguous along rows / columns / channels): it is
         read in place (SWK_MEM_DEVICE).  Returns one dict per group, in the shape batch_run returns; every dict carries the
-        call's 'generation' (swk_segment_inputs_last then serves all groups' segments, group order, then frame order)."""
+        call's 'generation' (swk_segment_inputs_last then serves all groups' segments, group order, then frame order).
+        device_stages=True: every group's stage stacks stay on the GPU (res['planes'], as batch_run's)."""
         params = params or default_params()
         G = len(groups)
         if G < 1:
@@ -629,7 +663,7 @@ class Context:
         for g, grp in enumerate(groups):
             ins[g], outs[g], res = self._group_io(grp["frames"], int(grp["nwin"]), int(grp["n"]), grp.get("crop"),
                                                   bool(grp.get("reverse_frames", False)), int(grp.get("seg_cap", seg_cap)), stages,
-                                                  want_A, want_E)
+                                                  want_A, want_E, device_stages)
             results.append(res)
         with self._lock:
             self.generation += 1
@@ -765,10 +799,11 @@ class Context:
         return out[0] if single else out
 
     # ---- review video ----
-    def _review_io(self, frames, rect, layout, device_out, dst):
+    def _review_io(self, frames, rect, layout, device_out, dst, out_hw=None):
         """(Input, Yuv420Dst, result planes) of bgr_to_yuv420 / render_review.  frames: uint8 (F, H, W, 3) BGR or (F, H, W) gray, a
         numpy array or a torch tensor on this context's GPU (read in place), contiguous along columns / channels, any row pitch and
-        frame stride.  dst: a ready Yuv420Dst (the planes are then the caller's business) or None."""
+        frame stride.  dst: a ready Yuv420Dst (the planes are then the caller's business) or None.  out_hw: Input -> the size of the
+        result's frames where it is not the rectangle's (a mosaic)."""
         on_device = hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False)
         shape = tuple(frames.shape)
         if str(frames.dtype) != ("torch.uint8" if on_device else "uint8") or len(shape) not in (3, 4):
@@ -791,6 +826,8 @@ class Context:
         if layout not in ("i420", "nv12"):
             raise ValueError('layout is "i420" or "nv12"')
         Fa, Ha, Wa = max(F, 1), max(Hc, 1), max(Wc, 1)               # (the library refuses empty ones)
+        if out_hw is not None:
+            Ha, Wa = out_hw(inp)
         hc, wc = (Ha + 1) // 2, (Wa + 1) // 2
         cshape = (Fa, hc, wc) if layout == "i420" else (Fa, hc, wc, 2)
         nplanes = 3 if layout == "i420" else 2
@@ -819,7 +856,7 @@ class Context:
         return planes
 
     def render_review(self, frames, boxes=None, marks=None, frame_style=None, mask=None, styles=None, mask_style=0, mark_arm=0, border=0,
-                      rect=None, layout="i420", device_out=False, dst=None, labels=None):
+                      rect=None, layout="i420", device_out=False, dst=None, labels=None, _panels=None):
         """swk_render_review: bgr_to_yuv420 of the frames composed with an overlay (include/swk.h): boxes -- REVIEW_BOX_DTYPE records
         or rows (frame, r0, c0, r1, c1, style), ascending frame --, marks -- REVIEW_MARK_DTYPE records or rows (frame, r, c, style),
         ascending frame --, frame_style (F,) int32 border style per frame, mask (Hr, Wr) uint8 tinted in mask_style where != 0, styles
@@ -847,7 +884,11 @@ class Context:
             styles = np.zeros(len(rows), REVIEW_STYLE_DTYPE)
             for k, name in enumerate(("b", "g", "r", "fill_alpha", "line_alpha")):
                 styles[name] = rows[:, k]
-        inp, dst, planes = self._review_io(frames, rect, layout, device_out, dst)
+        out_hw = None
+        if _panels is not None:
+            specs, cols = _panels
+            out_hw = lambda inp: panel_layout(max(inp.Hc, 1), max(inp.Wc, 1), 1 + len(specs), max(cols, 1))[:2]          # noqa: E731
+        inp, dst, planes = self._review_io(frames, rect, layout, device_out, dst, out_hw)
         if frame_style is not None:
             frame_style = np.ascontiguousarray(frame_style, np.int32)
             if frame_style.shape != (inp.n,):
@@ -861,13 +902,63 @@ class Context:
                     marks=marks.ctypes.data if len(marks) else None, nmarks=len(marks), mark_arm=int(mark_arm),
                     frame_style=frame_style.ctypes.data if frame_style is not None else None, border=int(border),
                     styles=styles.ctypes.data if len(styles) else None, nstyles=len(styles))
-        if labels is None:
+        if labels is None and _panels is None:
             self._check(self._lib.swk_render_review(self._h, ctypes.byref(inp), ctypes.byref(rv), ctypes.byref(dst)))
             return planes
-        labels = label_records(labels)
+        labels = label_records(labels if labels is not None else ())
+        if _panels is not None:
+            structs, keep = self._panel_structs(specs, inp)
+            self._check(self._lib.swk_render_review_panels(self._h, ctypes.byref(inp), ctypes.byref(rv), labels.ctypes.data if len(labels) else None,
+                                                           len(labels), structs, len(specs), int(cols), ctypes.byref(dst)))
+            del keep
+            return planes
         self._check(self._lib.swk_render_review_labels(self._h, ctypes.byref(inp), ctypes.byref(rv), labels.ctypes.data if len(labels) else None,
                                                        len(labels), ctypes.byref(dst)))
         return planes
+
+    def _panel_structs(self, specs, inp):
+        """(ReviewPanel array or None, the arrays it points into) of render_review_panels' panel dicts."""
+        if not specs:
+            return None, ()
+        F = inp.nwin * inp.n
+        structs, keep = (ReviewPanel * len(specs))(), []
+        for k, spec in enumerate(specs):
+            spec = dict(spec)
+            plane, kind = spec.pop("plane"), spec.pop("kind", "gray")
+            if kind not in ("gray", "labels", PANEL_GRAY, PANEL_LABELS):
+                raise ValueError('a panel\'s kind is "gray" or "labels"')
+            p = structs[k]
+            p.kind = PANEL_LABELS if kind in ("labels", PANEL_LABELS) else PANEL_GRAY
+            p.gain, p.layers = int(spec.pop("gain", 1)), int(spec.pop("layers", 0))
+            if isinstance(plane, dict):                               # a raw plane: ptr, frame_stride, row_stride, mem
+                p.plane, p.mem = plane["ptr"], plane.get("mem", MEM_DEVICE)
+                p.frame_stride, p.row_stride = plane["frame_stride"], plane["row_stride"]
+            else:
+                on_device = hasattr(plane, "data_ptr") and getattr(plane, "is_cuda", False)
+                shape = tuple(plane.shape)
+                if str(plane.dtype) != ("torch.uint8" if on_device else "uint8") or shape != (F, inp.Hc, inp.Wc):
+                    raise ValueError("a panel's plane is uint8 (F, Hr, Wr)")
+                strides = tuple(int(x) for x in plane.stride()) if on_device else plane.strides
+                if strides[2] != 1:
+                    raise ValueError("a panel's plane must be contiguous along columns")
+                p.plane, p.mem = (plane.data_ptr() if on_device else plane.ctypes.data), (MEM_DEVICE if on_device else MEM_HOST)
+                p.frame_stride, p.row_stride = strides[0], strides[1]
+                keep.append(plane)
+            caption = spec.pop("caption", None)
+            if spec:
+                raise ValueError("unknown panel entries: %s" % ", ".join(sorted(spec)))
+            rec = label_records([(0,) + tuple(caption) if caption is not None else (0, 0, 0, 0, 0, 1, b"")])          # (none: len 0 at a valid scale)
+            ctypes.memmove(ctypes.addressof(p.caption), rec.ctypes.data, 64)
+        return structs, keep
+
+    def render_review_panels(self, frames, panels=(), cols=1, **kw):
+        """swk_render_review_panels: render_review's frames (its remaining arguments; labels=None: none) as cell 0 of a mosaic whose
+        further cells are stage images of the same frames (include/swk.h; panel_layout gives the geometry).  panels: dicts with
+        plane -- uint8 (F, Hr, Wr), a numpy array (any frame and row strides) or a torch tensor on this context's GPU, or a dict
+        (ptr, frame_stride, row_stride[, mem]) naming device memory --, kind "gray" (default) or "labels", gain (gray, 1..255,
+        default 1), layers (bits 0..3: mask, boxes, marks, border drawn on the panel; default 0) and caption -- None or
+        (r, c, style, plate, scale, text).  cols: cells per mosaic row.  Returns render_review's planes at the mosaic's size."""
+        return self.render_review(frames, _panels=(list(panels), int(cols)), **kw)
 
     # ---- stage-level entry points ----
     def bgr2gray(self, bgr, gray_mode=GRAY_Q14):

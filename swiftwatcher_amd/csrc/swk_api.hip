@@ -1489,7 +1489,20 @@ int download_rects(swk_ctx *ctx, uint8_t *dst, int64_t rs, int64_t fs, const uin
     return SWK_OK;
 }
 
-int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels, int nlabels, swk_yuv420_dst *dst)
+// a label's own fields, as swk_render_review_labels and a panel's caption are held to them; null = fine
+const char *label_fault(const swk_review_label &l, int nstyles, const uint8_t (*font)[8])
+{
+    if (l.scale < 1 || l.scale > 8) return "a label's scale outside 1..8";
+    if (l.len < 0 || l.len > 32) return "a label's len outside 0..32";
+    if (l.style < 0 || l.style > nstyles || l.plate < 0 || l.plate > nstyles) return "a label's style or plate outside 0..nstyles";
+    for (int j = 0; j < l.len; ++j)
+        if (l.text[j] > 127 || !font[l.text[j]][7]) return "a label's text holds a byte outside the character set";
+    return nullptr;
+}
+
+// cols == 0: the ROI's frames alone (dst holds Hc x Wc frames); cols >= 1: swk_render_review_panels' mosaic
+int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels, int nlabels, swk_yuv420_dst *dst,
+                const swk_review_panel *panels = nullptr, int npanels = 0, int cols = 0)
 {
     if (!in || !dst) return fail(ctx, SWK_ERR_ARG, "null argument");
     // ---- every refusal comes before anything is copied or launched
@@ -1501,15 +1514,32 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const s
     if (in->x0 < 0 || in->y0 < 0) return fail(ctx, SWK_ERR_ARG, "negative ROI origin");
     if ((int64_t)in->nwin * in->n > (1 << 24)) return fail(ctx, SWK_ERR_CAPACITY, "too many frames in one call (2^24 at most)");
     if (in->Hc > 32768 || in->Wc > 32768) return fail(ctx, SWK_ERR_CAPACITY, "ROI side above 32768");
-    const int F = in->nwin * in->n, Hc = in->Hc, Wc = in->Wc, ch = (Hc + 1) / 2, cw = (Wc + 1) / 2;
+    const int F = in->nwin * in->n, Hc = in->Hc, Wc = in->Wc;
+    // the destination's frames: the ROI, or the mosaic of rows x cols cells of Hp x Wp
+    const bool mosaic = cols != 0;
+    if (mosaic && (npanels < 0 || npanels > kReviewMaxPanels || cols < 1 || cols > 16))
+        return fail(ctx, SWK_ERR_ARG, "npanels outside 0..15 or cols outside 1..16");
+    if (mosaic && npanels > 0 && !panels) return fail(ctx, SWK_ERR_ARG, "null panels with a non-zero count");
+    const int Hp = Hc + (Hc & 1), Wp = Wc + (Wc & 1), rows = mosaic ? (1 + npanels + cols - 1) / cols : 1;
+    if (mosaic && ((int64_t)rows * Hp > 32768 || (int64_t)cols * Wp > 32768)) return fail(ctx, SWK_ERR_CAPACITY, "mosaic side above 32768");
+    const int Hd = mosaic ? rows * Hp : Hc, Wd = mosaic ? cols * Wp : Wc, ch = (Hd + 1) / 2, cw = (Wd + 1) / 2;
     if (in->row_stride < ((int64_t)in->x0 + Wc) * in->channels) return fail(ctx, SWK_ERR_ARG, "source row stride smaller than the ROI's row");
     if (dst->layout != SWK_YUV_I420 && dst->layout != SWK_YUV_NV12) return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_I420 or SWK_YUV_NV12)");
     const bool nv12 = dst->layout == SWK_YUV_NV12;
     const int cbytes = nv12 ? 2 : 1;
     if (!dst->y || !dst->u || (!nv12 && !dst->v)) return fail(ctx, SWK_ERR_ARG, "null YUV plane");
-    if (dst->y_row_stride < Wc || dst->c_row_stride < (int64_t)cw * cbytes) return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
+    if (dst->y_row_stride < Wd || dst->c_row_stride < (int64_t)cw * cbytes) return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
+    for (int k = 0; k < npanels; ++k) {
+        const swk_review_panel &p = panels[k];
+        if (!p.plane) return fail(ctx, SWK_ERR_ARG, "a panel's plane is null");
+        if (p.mem != SWK_MEM_HOST && p.mem != SWK_MEM_DEVICE) return fail(ctx, SWK_ERR_ARG, "a panel's mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
+        if (p.kind != SWK_PANEL_GRAY && p.kind != SWK_PANEL_LABELS) return fail(ctx, SWK_ERR_ARG, "a panel's kind is SWK_PANEL_GRAY or SWK_PANEL_LABELS");
+        if (p.kind == SWK_PANEL_GRAY && (p.gain < 1 || p.gain > 255)) return fail(ctx, SWK_ERR_ARG, "a gray panel's gain outside 1..255");
+        if (p.row_stride < Wc) return fail(ctx, SWK_ERR_ARG, "a panel's row stride smaller than the ROI's row");
+        if (p.layers < 0 || p.layers > 15) return fail(ctx, SWK_ERR_ARG, "a panel's layers outside 0..15");
+    }
     std::vector<int32_t> meta;
-    size_t o_boxes = 0, o_bstart = 0, o_marks = 0, o_mstart = 0, o_border = 0, o_mask = 0, o_labels = 0, o_lstart = 0;
+    size_t o_boxes = 0, o_bstart = 0, o_marks = 0, o_mstart = 0, o_border = 0, o_mask = 0, o_labels = 0, o_lstart = 0, o_captions = 0, o_palette = 0;
     uint32_t mask_colour = 0; int mask_alpha = 0;
     if (rv) {
         if (rv->nstyles < 0 || (rv->nstyles > 0 && !rv->styles)) return fail(ctx, SWK_ERR_ARG, "styles");
@@ -1549,13 +1579,11 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const s
             const swk_review_label &l = labels[k];
             if (l.frame < 0 || l.frame >= F) return fail(ctx, SWK_ERR_ARG, "a label's frame outside the call's frames");
             if (l.frame < prev) return fail(ctx, SWK_ERR_ARG, "labels not in ascending frame order");
-            if (l.scale < 1 || l.scale > 8) return fail(ctx, SWK_ERR_ARG, "a label's scale outside 1..8");
-            if (l.len < 0 || l.len > 32) return fail(ctx, SWK_ERR_ARG, "a label's len outside 0..32");
-            if (bad_style(l.style) || bad_style(l.plate)) return fail(ctx, SWK_ERR_ARG, "a label's style or plate outside 0..nstyles");
-            for (int j = 0; j < l.len; ++j)
-                if (l.text[j] > 127 || !font[l.text[j]][7]) return fail(ctx, SWK_ERR_ARG, "a label's text holds a byte outside the character set");
+            if (const char *why = label_fault(l, rv->nstyles, font)) return fail(ctx, SWK_ERR_ARG, why);
             prev = l.frame;
         }
+        for (int k = 0; k < npanels; ++k)
+            if (const char *why = label_fault(panels[k].caption, rv->nstyles, font)) return fail(ctx, SWK_ERR_ARG, why);
         // ---- the kernel's tables, styles resolved, in one block of int32 (launch_review, swk_internal.h)
         o_boxes = 0;
         meta.resize((size_t)rv->nboxes * 6);
@@ -1600,19 +1628,29 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const s
             mask_colour = colour(rv->mask_style);
             mask_alpha = rv->styles[rv->mask_style - 1].fill_alpha;
         }
+        auto label_record = [&](const swk_review_label &l, int32_t *e) {
+            e[0] = l.r; e[1] = l.c; e[2] = l.scale; e[3] = l.len;
+            e[4] = l.style ? (int32_t)colour(l.style) : 0;
+            e[5] = l.style ? rv->styles[l.style - 1].line_alpha : 0;          // (alpha 0 is the identity)
+            e[6] = l.plate ? (int32_t)colour(l.plate) : 0;
+            e[7] = l.plate ? rv->styles[l.plate - 1].fill_alpha : 0;
+            for (int j = 0; j < l.len; ++j) e[8 + (j >> 2)] |= (int32_t)((uint32_t)(l.text[j] - kReviewFontFirst) << (8 * (j & 3)));
+        };
+        if (npanels > 0) {
+            // the panels' captions, then the palette as b | g << 8 | r << 16
+            o_captions = meta.size();
+            meta.resize(o_captions + (size_t)npanels * 16, 0);
+            for (int k = 0; k < npanels; ++k) label_record(panels[k].caption, &meta[o_captions + (size_t)k * 16]);
+            o_palette = meta.size();
+            meta.resize(o_palette + 256);
+            uint8_t pal[256][3];
+            review_label_palette(pal);
+            for (int v = 0; v < 256; ++v) meta[o_palette + v] = (int32_t)((uint32_t)pal[v][0] | ((uint32_t)pal[v][1] << 8) | ((uint32_t)pal[v][2] << 16));
+        }
         if (nlabels > 0) {
             o_labels = meta.size();
             meta.resize(o_labels + (size_t)nlabels * 16, 0);
-            for (int k = 0; k < nlabels; ++k) {
-                const swk_review_label &l = labels[k];
-                int32_t *e = &meta[o_labels + (size_t)k * 16];
-                e[0] = l.r; e[1] = l.c; e[2] = l.scale; e[3] = l.len;
-                e[4] = l.style ? (int32_t)colour(l.style) : 0;
-                e[5] = l.style ? rv->styles[l.style - 1].line_alpha : 0;          // (alpha 0 is the identity)
-                e[6] = l.plate ? (int32_t)colour(l.plate) : 0;
-                e[7] = l.plate ? rv->styles[l.plate - 1].fill_alpha : 0;
-                for (int j = 0; j < l.len; ++j) e[8 + (j >> 2)] |= (int32_t)((uint32_t)(l.text[j] - kReviewFontFirst) << (8 * (j & 3)));
-            }
+            for (int k = 0; k < nlabels; ++k) label_record(labels[k], &meta[o_labels + (size_t)k * 16]);
             o_lstart = meta.size();
             meta.resize(o_lstart + F + 1, 0);
             for (int k = 0; k < nlabels; ++k) meta[o_lstart + labels[k].frame + 1] += 1;
@@ -1634,12 +1672,32 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const s
         if (rc) return rc;
         a.src = din; a.fs = (int64_t)Hc * rowb; a.rs = (int64_t)rowb; a.x0 = a.y0 = 0;
     }
-    const size_t yb = ((size_t)F * Hc * Wc + 15) & ~(size_t)15, cb = ((size_t)F * ch * cw * cbytes + 15) & ~(size_t)15;
+    ReviewPanels q{};
+    q.npanels = npanels; q.ncells = rows * (mosaic ? cols : 1); q.cols = mosaic ? cols : 1;
+    {
+        // device planes are read where they lie; host planes go up densely, one after the other
+        const size_t per = ((size_t)F * Hc * Wc + 15) & ~(size_t)15;
+        size_t host_planes = 0;
+        for (int k = 0; k < npanels; ++k) host_planes += panels[k].mem == SWK_MEM_HOST;
+        uint8_t *dpl = nullptr;
+        if (host_planes) NEED(ctx, SL_TMP_AUX, host_planes * per, dpl);
+        for (int k = 0; k < npanels; ++k) {
+            const swk_review_panel &p = panels[k];
+            q.panel[k] = ReviewPanel{p.plane, p.frame_stride, p.row_stride, p.kind, p.gain, p.layers, 0};
+            if (p.mem == SWK_MEM_HOST) {
+                const int rc = upload_rects(ctx, dpl, p.plane, p.row_stride, p.frame_stride, (size_t)Wc, (size_t)Hc, F);
+                if (rc) return rc;
+                q.panel[k].plane = dpl; q.panel[k].fs = (int64_t)Hc * Wc; q.panel[k].rs = Wc;
+                dpl += per;
+            }
+        }
+    }
+    const size_t yb = ((size_t)F * Hd * Wd + 15) & ~(size_t)15, cb = ((size_t)F * ch * cw * cbytes + 15) & ~(size_t)15;
     if (dst->mem == SWK_MEM_HOST) {
         uint8_t *dout;
         NEED(ctx, SL_TMP_OUT, yb + cb * (nv12 ? 1 : 2), dout);
         a.y = dout; a.u = dout + yb; a.v = nv12 ? nullptr : dout + yb + cb;
-        a.y_rs = Wc; a.y_fs = (int64_t)Hc * Wc; a.c_rs = (int64_t)cw * cbytes; a.c_fs = (int64_t)ch * a.c_rs;
+        a.y_rs = Wd; a.y_fs = (int64_t)Hd * Wd; a.c_rs = (int64_t)cw * cbytes; a.c_fs = (int64_t)ch * a.c_rs;
     } else {
         a.y = dst->y; a.u = dst->u; a.v = nv12 ? nullptr : dst->v;
         a.y_rs = dst->y_row_stride; a.y_fs = dst->y_frame_stride; a.c_rs = dst->c_row_stride; a.c_fs = dst->c_frame_stride;
@@ -1654,13 +1712,15 @@ int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const s
         a.mask_colour = mask_colour; a.mask_alpha = mask_alpha;
         a.mark_arm = rv->mark_arm; a.border = rv->border;
         if (nlabels > 0) { text.labels = dmeta + o_labels; text.label_start = dmeta + o_lstart; }
+        if (npanels > 0) { q.captions = dmeta + o_captions; q.palette = (const uint32_t *)(dmeta + o_palette); }
     }
     {
         Timed t(ctx, SWK_K_GRAY);
         launch_review(ctx->stream, a, F, rv != nullptr, rv != nullptr && nlabels > 0 ? &text : nullptr);
+        if (mosaic) launch_review_panels(ctx->stream, a, F, q);
     }
     if (dst->mem == SWK_MEM_HOST) {
-        int rc = download_rects(ctx, dst->y, dst->y_row_stride, dst->y_frame_stride, a.y, (size_t)Wc, (size_t)Hc, F);
+        int rc = download_rects(ctx, dst->y, dst->y_row_stride, dst->y_frame_stride, a.y, (size_t)Wd, (size_t)Hd, F);
         if (rc) return rc;
         rc = download_rects(ctx, dst->u, dst->c_row_stride, dst->c_frame_stride, a.u, (size_t)cw * cbytes, (size_t)ch, F);
         if (rc) return rc;
@@ -1698,6 +1758,20 @@ int32_t swk_render_review_labels(swk_ctx *ctx, const swk_input *in, const swk_re
 void swk_review_font(uint8_t out[128][8])
 {
     if (out) swk::review_font(out);
+}
+
+int32_t swk_render_review_panels(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels, int32_t nlabels,
+                                 const swk_review_panel *panels, int32_t npanels, int32_t cols, swk_yuv420_dst *dst)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!rv) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (cols < 1) return fail(ctx, SWK_ERR_ARG, "npanels outside 0..15 or cols outside 1..16");
+    return review_call(ctx, in, rv, labels, nlabels, dst, panels, npanels, cols);
+}
+
+void swk_review_label_palette(uint8_t out[256][3])
+{
+    if (out) swk::review_label_palette(out);
 }
 
 int32_t swk_ialm(swk_ctx *ctx, const uint8_t *planes, int32_t n, int32_t P, double lmbda, double tol, int32_t maxiter,

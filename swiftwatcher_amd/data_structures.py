@@ -194,6 +194,7 @@ class Frame:
         self.processed_frames = _LazyStages()
         self.segments = []
         self.null = frame_number < 0
+        self.stage_planes = None          # (_lib.DevicePlanes, frame index in it) where the window's stage images were kept on the GPU
 
     def get_frame(self):
         return self.frame
@@ -454,10 +455,20 @@ class FrameQueue(deque):
             batch.launch(hint)
         planes = res.get("planes")
         if planes is not None:
-            for key, name in STAGE_KEYS.items():
-                for i, slot in enumerate(self):
-                    slot.processed_frames[name] = (lambda k=key, i=i, p=planes: p.read(k, i))
+            _attach_planes(planes, list(self))
         window_segments(res["segs"], nseg, list(self), tuple(min_seg_size), crop_region, batch)
+
+
+def _attach_planes(planes, slots):
+    """The stage images a batch kept on the GPU (planes: _lib.DevicePlanes, frame i of it = slots[i]) as the frames'
+    processed_frames -- one image is copied to the host when it is first read -- and as Frame.stage_planes, for readers that take
+    them where they lie (review.ReviewWriter)."""
+    for key in planes.stages:
+        name = STAGE_KEYS[key]
+        for i, slot in enumerate(slots):
+            slot.processed_frames[name] = (lambda k=key, i=i, p=planes: p.read(k, i))
+    for i, slot in enumerate(slots):
+        slot.stage_planes = (planes, i)
 
 
 def _stages_on_request(frames, crop_region, min_seg_size, params, device):
@@ -593,7 +604,7 @@ def _margin_rect(frame_shape, crop_region, min_seg_size):
     return (max(y0 - my, 0), min(y1 + my, Hf), max(x0 - mx, 0), min(x1 + mx, Wf)), (x0, y0, x1, y1)
 
 
-def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, params=None, classifier=None, owner=None, info=None):
+def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, params=None, classifier=None, owner=None, info=None, stages=()):
     """Several FrameQueue-fuls in ONE library call.  windows: list of (frames, frame_numbers, timestamps) triples as
     FrameReader.get_n_frames returns them (oldest frame first), all of the same length n.  Returns one list of Frame
     objects per window in POP order (oldest first, the order __main__.py:81-92 consumes them), segments attached
@@ -601,7 +612,8 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
     the reference too (the queue is emptied between them), so batching changes nothing but the launch count.
     classifier: its scoring of the batch's segments is started on the GPU before the Python objects are made.  owner: an object whose
     _classifier_hint the batch sets when a classifier asks for its scores (a reader that segments ahead).  info: a dict that receives
-    'iters' (IALM iterations per window)."""
+    'iters' (IALM iterations per window).  stages: the stage images (keys of STAGE_KEYS) to keep on the GPU -- they become the
+    frames' processed_frames entries and Frame.stage_planes; none are produced by default."""
     if not windows:
         return []
     n = len(windows[0][0])
@@ -623,7 +635,8 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
     for w in order:
         ordered.extend(windows[w][0][::-1])                  # queue index 0 = newest = last frame read (:134)
     stack, (rx, ry), (Hc, Wc), backwards = stack_frames(ordered, crop_region, min_seg_size, ctx.staging, device)
-    res = ctx.batch_run(stack, len(windows), n, crop=(rx, ry, Wc, Hc), params=params, stages=(), reverse_frames=backwards)
+    res = ctx.batch_run(stack, len(windows), n, crop=(rx, ry, Wc, Hc), params=params, stages=tuple(stages), device_stages=True,
+                        reverse_frames=backwards)
     nseg = res["nseg"]
     if np.any(nseg > res["segs"].shape[1]):
         raise _lib.SwkError("more regions in a frame than seg_cap")
@@ -643,6 +656,8 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
         for k, fr in enumerate(popped):
             slots[pos[w] * n + (n - 1 - k)] = fr
         out.append(popped)
+    if res.get("planes") is not None:
+        _attach_planes(res["planes"], slots)
     window_segments(res["segs"], nseg, slots, tuple(min_seg_size), crop_region, batch)
     return out
 
@@ -661,11 +676,12 @@ def _group_staging(ctx, slot, shape):
     return arr
 
 
-def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, classifier=None):
+def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, classifier=None, stages=()):
     """segment_windows for several videos in ONE library call (swk_batch_run_groups).  groups: list of (windows, crop_region), windows
     as segment_windows takes them; every window of every group has the same length n, the crop regions differ.  Returns, per group,
     what segment_windows(windows, crop_region, ...) returns.  The classifier's scoring of all groups' segments starts once, over the
-    whole call: its head is batch-independent, so every score equals the one of a per-group batch."""
+    whole call: its head is batch-independent, so every score equals the one of a per-group batch.  stages: as
+    segment_windows' -- the stage images every group keeps on the GPU."""
     groups = [(list(w), cr) for w, cr in groups]
     live = [i for i, (w, _) in enumerate(groups) if w]
     if not live:
@@ -682,7 +698,7 @@ def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, 
         stack, (rx, ry), (Hc, Wc), backwards = stack_frames(ordered, crop_region, min_seg_size,
                                                             lambda shape, s=slot: _group_staging(ctx, s, shape), device)
         specs.append(dict(frames=stack, nwin=len(windows), n=n, crop=(rx, ry, Wc, Hc), reverse_frames=backwards))
-    results = ctx.batch_run_groups(specs, params=params, stages=())
+    results = ctx.batch_run_groups(specs, params=params, stages=tuple(stages), device_stages=True)
     for r in results:
         if np.any(r["nseg"] > r["segs"].shape[1]):
             raise _lib.SwkError("more regions in a frame than seg_cap")
@@ -706,6 +722,8 @@ def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, 
             popped = [Frame(frames[k], numbers[k], stamps[k]) for k in range(n)]          # oldest first
             slots.extend(popped[::-1])                                                   # the batch's frame order: newest first
             out[i].append(popped)
+        if res.get("planes") is not None:
+            _attach_planes(res["planes"], slots)
         window_segments(res["segs"], res["nseg"], slots, tuple(min_seg_size), crop_region, batch, first)
         first += int(res["nseg"].sum())
     return out

@@ -13,7 +13,7 @@ from . import image_filtering as img
 
 def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size=21, classifier=None, min_seg_size=(24, 24),
                              device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None,
-                             track_by_window=True, review=None, review_text=False):
+                             track_by_window=True, review=None, review_text=False, review_stages=()):
     """Same call order as __main__.py:62-100.  corners = ((x1, y1), (x2, y2)) of the chimney's top edge: crop region
     and ROI mask are then generated from the video's first frame (:62-63) instead of being passed in.  Returns the tracker's detected events (lists of Segment objects,
     the structure the reference hands to event classification).  windows_per_call > 1 reads that many queue-fuls
@@ -25,7 +25,9 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     every window's frames are written there as a 4:2:0 video of the crop region with the segments, the boxes the classifier removed,
     the ROI mask and the events drawn in (review.py); a writer made here from a path is closed when the count ends.  Counts and
     events are the same with and without it.  review_text: a writer made here from a path also writes the status line and the event
-    numbers (ReviewWriter's text=True); a ReviewWriter handed in carries its own setting."""
+    numbers (ReviewWriter's text=True); a ReviewWriter handed in carries its own setting.  review_stages: names of stage images
+    (rpca, thresh, labels, ...: ReviewWriter's stages=) that a writer made here from a path shows as panels beside every frame; the
+    segment path then keeps those images on the GPU, where the writer reads them."""
     if corners is not None:
         first_frame = reader.read_frame(0, increment=False)                        # :62
         crop_region, roi_mask, _ = img.generate_regions(first_frame, corners)      # :63
@@ -37,7 +39,8 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     own_review = None
     if review is not None and not hasattr(review, "write_window"):
         from .review import ReviewWriter
-        review = own_review = ReviewWriter(review, crop_region, roi_mask, getattr(reader, "fps", 30.0), device=device, text=review_text)
+        review = own_review = ReviewWriter(review, crop_region, roi_mask, getattr(reader, "fps", 30.0), device=device, text=review_text,
+                                           stages=review_stages)
     try:
         return _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_seg_size, device, keep_stages, windows_per_call,
                               export_dir, params, track_by_window, tracker, review)
@@ -50,6 +53,8 @@ def _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_se
                    params, track_by_window, tracker, review):
     """swift_counting_algorithm once the regions, the tracker and the review writer exist."""
     seen = 0                                         # events already handed to the review
+    stages = _review_stages([review])                # the stage images the review shows: kept on the GPU by the segment path
+    keep = {"stages": stages} if stages else {}      # (without them the segmenters are called as they always were)
     if classifier is not None and getattr(reader, "_classifier_hint", False) is None:
         import weakref
         reader._classifier_hint = weakref.ref(classifier)          # a reader that segments ahead scores every batch for this classifier
@@ -71,7 +76,7 @@ def _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_se
                         triple = reader.get_n_frames(n=queue_size)                  # :73 (pads with null frames)
                         windows.append(triple)
                         ahead += sum(1 for k in triple[1] if k >= 0)                # null frames are not counted (:146-147)
-                    ready.put(segment_windows(windows, crop_region, min_seg_size, device=device, params=params, classifier=classifier))
+                    ready.put(segment_windows(windows, crop_region, min_seg_size, device=device, params=params, classifier=classifier, **keep))
                 ready.put(None)
             except BaseException as exc:                                            # surfaces in the consumer
                 ready.put(exc)
@@ -99,7 +104,7 @@ def _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_se
                     seen = len(tracker.detected_events)
         worker.join()
         return tracker.detected_events
-    queue = FrameQueue(queue_size, device=device, params=params, keep_stages=keep_stages)
+    queue = FrameQueue(queue_size, device=device, params=params, keep_stages=keep_stages or bool(stages))
     while queue.frames_processed < reader.total_frames:
         frames, numbers, stamps = reader.get_n_frames(n=queue.maxlen)          # :73 (pads with null frames)
         queue.push_list_of_frames(frames, numbers, stamps)                     # :74
@@ -129,6 +134,11 @@ def _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_se
     return tracker.detected_events
 
 
+def _review_stages(reviews):
+    """The stage keys that the given review writers (or None) show, each once."""
+    return tuple(dict.fromkeys(key for rv in reviews if rv is not None for key in getattr(rv, "stages", ())))
+
+
 def _track(tracker, popped, by_window):
     """One window's popped frames (oldest first) to the tracker: in one call where it is asked for and the tracker has one (anything
     with the reference's step() alone is stepped per frame)."""
@@ -139,20 +149,21 @@ def _track(tracker, popped, by_window):
             tracker.step(frame)
 
 
-def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, review=None, review_text=False, **kw):
+def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None, review=None, review_text=False, review_stages=(), **kw):
     """Decoded frames (oldest first) -> (swift count, events).  frames may also be a reader (get_n_frames / read_frame / total_frames,
     e.g. io_y4m.Y4MReader: its fps holds) or anything io_y4m.open_y4m opens: the path of a .y4m file (any format it reads), or a
     YUV4MPEG2 stream of unknown length -- "-" (standard input), a FIFO's path, a file descriptor, a binary file object (a pipe from a
     decoder: proc.stdout).  Regions either explicit or from corners=...; params, review (a path or a
-    review.ReviewWriter: the review video of the count) and review_text (text in a review made from a path) as in
-    swift_counting_algorithm."""
+    review.ReviewWriter: the review video of the count), review_text (text in a review made from a path) and review_stages (stage
+    images as panels in it) as in swift_counting_algorithm."""
     opened = None
     if _is_video_source(frames):
         from .io_y4m import open_y4m
         frames = opened = open_y4m(frames)
     reader = frames if hasattr(frames, "get_n_frames") else ArrayReader(frames, fps=fps)
     try:
-        events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, review=review, review_text=review_text, **kw)
+        events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, review=review, review_text=review_text,
+                                          review_stages=review_stages, **kw)
     finally:
         if opened is not None and hasattr(opened, "close"):
             opened.close()
@@ -231,7 +242,7 @@ def schedule_videos(readers, sizes, segment, consume, in_flight=4, windows_per_c
 
 def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows_per_call=1, classifier=None, queue_size=21,
                         min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True, reviews=None,
-                        review_text=False):
+                        review_text=False, review_stages=()):
     """count_swifts over a list of videos (the reference's loop over its video list, __main__.py:21), several videos at a time on one
     GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
     windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
@@ -241,21 +252,22 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
     .y4m path, "-", a FIFO, a descriptor, a binary file object); regions: per video
     (crop_region, roi_mask), or corners: per video the chimney's top edge (the regions then come from its first frame, :62-63).
     reviews: per video a path, a review.ReviewWriter or None -- that video's review video (swift_counting_algorithm's review=);
-    review_text: the writers made here from paths also write text (its review_text=).
+    review_text: the writers made here from paths also write text (its review_text=); review_stages: and show these stage images as
+    panels (its review_stages=).
     Returns [(count, events), ...] in input order."""
     from .io_y4m import open_y4m
     readers = [open_y4m(v) if _is_video_source(v) else v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
     opened = [r for r, v in zip(readers, videos) if r is not v and hasattr(r, "close")]          # (closed again when the count is done)
     try:
         return _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device,
-                             pad_factor, params, track_by_window, reviews, review_text)
+                             pad_factor, params, track_by_window, reviews, review_text, review_stages)
     finally:
         for r in opened:
             r.close()
 
 
 def _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device, pad_factor, params,
-                  track_by_window=True, reviews=None, review_text=False):
+                  track_by_window=True, reviews=None, review_text=False, review_stages=()):
     """count_swifts_videos over readers."""
     if regions is None:
         if corners is None:
@@ -280,14 +292,18 @@ def _count_videos(readers, regions, corners, in_flight, windows_per_call, classi
         for v, rv in enumerate(reviews):
             if rv is not None and not hasattr(rv, "write_window"):
                 from .review import ReviewWriter
-                reviews[v] = ReviewWriter(rv, regions[v][0], regions[v][1], getattr(readers[v], "fps", 30.0), device=device, text=review_text)
+                reviews[v] = ReviewWriter(rv, regions[v][0], regions[v][1], getattr(readers[v], "fps", 30.0), device=device, text=review_text,
+                                          stages=review_stages)
                 own_reviews.append(reviews[v])
         seen = [0] * len(readers)                    # events already handed to each video's review
         removed = {}                                 # id(frame) -> the boxes the classifier removed from it, until its window is written
 
+        stages = _review_stages(reviews)             # the stage images the reviews show: kept on the GPU by the segment path
+        keep = {"stages": stages} if stages else {}  # (without them the segmenter is called as it always was)
+
         def segment(groups):
             out = segment_window_groups([(w, regions[v][0]) for v, w in groups], min_seg_size, device=device, params=params,
-                                        classifier=classifier)
+                                        classifier=classifier, **keep)
             if classifier is not None:
                 flat = [fr for per in out for popped in per for fr in popped]
                 watched = [fr for (v, _), per in zip(groups, out) if reviews[v] is not None for popped in per for fr in popped]

@@ -7,13 +7,19 @@ write.  pipeline.swift_counting_algorithm / count_swifts / count_swifts_videos f
 With text=True (review_text=True there, --review-text on the command line) every frame also carries the keys of the count's tables
 as text, drawn by the same call (swk_render_review_labels, the library's 5 x 7 font: space, 0-9, A-Z and # : . - + / = %): a status
 line with the frame number, the timestamp and the segment, removed-box and event counts, and the number #k of every event shown --
-row k of the events table."""
+row k of the events table.
+
+With stages=("rpca", "thresh", "labels") (review_stages= there, --review-stages on the command line) every frame becomes a mosaic:
+the composed frame, then one panel per stage image of the same video frame -- the u8 planes swk_batch_run writes -- each with a
+caption, converted by the same GPU call (swk_render_review_panels) from where the planes lie on the GPU."""
 import bisect
 import math
 
 import numpy as np
 
 from . import _lib
+from ._lib import panel_layout
+from .data_structures import STAGE_KEYS
 from .io_y4m import FRAME_MARK, Y4MWriter
 
 STYLE_SEGMENT, STYLE_REJECTED, STYLE_EVENT, STYLE_MASK, STYLE_TEXT, STYLE_PLATE = 1, 2, 3, 4, 5, 6
@@ -26,6 +32,8 @@ DEFAULT_STYLES = ((0, 255, 0, 32, 256),          # 1 segments: green outline, fa
                   (0, 0, 0, 160, 0))             # 6 text plate: black, 160 / 256
 STATUS_CELLS = 33                                # the status line's length while no field has widened
 LABEL_BYTES = 32                                 # a label's text (swk_review_label)
+DEFAULT_STAGE_GAIN = {"gray": 1, "rpca": 4, "bilateral": 4, "thresh": 4, "opened": 4, "labels": 1}          # (labels: a palette, no gain)
+_STAGE_OF_NAME = {name: key for key, name in STAGE_KEYS.items()}
 _CHARSET = frozenset(b" 0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ#:.-+/=%")
 
 
@@ -47,6 +55,33 @@ def text_scale_for(width, height, border):
     """The default text scale of a width x height review: the largest at which the status line fits between the borders and takes no
     more than an eighth of the height, 1..4."""
     return max(1, min(4, (width - 2 * border) // (6 * STATUS_CELLS + 1), (height // 8) // 9))
+
+
+def stage_keys(stages):
+    """The stage keys (gray rpca bilateral thresh opened labels) of names given as keys or as Frame.processed_frames names
+    (grayscale RPCA bilateral thresh_15 opened cc_labeling), in the order given; repeats stay.  An unknown name is a ValueError."""
+    if isinstance(stages, str):
+        stages = [part for part in stages.replace(" ", "").split(",") if part]
+    out = []
+    for name in stages:
+        if name in STAGE_KEYS:
+            out.append(name)
+        elif name in _STAGE_OF_NAME:
+            out.append(_STAGE_OF_NAME[name])
+        else:
+            raise ValueError("unknown stage %r (one of %s)" % (name, " ".join(STAGE_KEYS)))
+    return tuple(out)
+
+
+def stage_caption(key, gain):
+    """A stage panel's caption: the key in capitals, with the gain where it is not 1 -- "RPCA X4", "LABELS"."""
+    return key.upper() if key == "labels" or gain == 1 else "%s X%d" % (key.upper(), gain)
+
+
+def default_stage_cols(height, width, cells):
+    """Cells per mosaic row: a crop wider than high (chimney crops are about 2:1) stacks its cells vertically, any other lays them
+    side by side."""
+    return 1 if width > height else cells
 
 
 def centroid_pixel(centroid):
@@ -89,12 +124,26 @@ class ReviewWriter:
         MARK_ARM + 2 scale below and right of the event's last centroid pixel, then moved up / left and then down / right so that the
         label's rectangle (rows [r - scale, r + 8 scale), columns [c - scale, c + 6 scale len)) lies inside the border; where the
         frame is too small for that, its top / left side does.
-    The character set has no lower case, and the two positions are fixed."""
+    The character set has no lower case, and the two positions are fixed.
+
+    stages=(names) makes every output frame a mosaic (_lib.panel_layout): cell 0 is the frame above, unchanged; cell k the k-th
+    named stage image of the same video frame -- names are stage keys (gray rpca bilateral thresh opened labels) or
+    Frame.processed_frames names, in any order, repeats allowed.  A gray stage is shown as min(255, v * gain), gain from stage_gain
+    (a dict by key) over DEFAULT_STAGE_GAIN (gray 1, the others 4: the rpca image is dark by construction, the threshold that
+    follows it is 15); labels in the library's palette (_lib.review_label_palette, 0 = black).  stage_layers picks the layers drawn
+    on the panels too (bit 0..3: mask, boxes, marks, border; default 14: all but the mask's tint).  Every panel carries a caption
+    (stage_caption: "RPCA X4", "LABELS") in style 5 on plate 6 at text_scale, ink origin at row and column BORDER + scale -- so
+    stages needs six styles.  stage_cols: cells per row (None: default_stage_cols -- 1 for a crop wider than high, else all cells
+    in one row).  height / width stay the crop's; frame_height / frame_width are the written frames'.  The planes come from the
+    frames: where a window's written frames carry one _lib.DevicePlanes (Frame.stage_planes; FrameQueue(keep_stages=True),
+    segment_windows(stages=...)) they are read on the GPU where they lie, else Frame.processed_frames[name] is stacked on the host
+    and uploaded.  The grid is fixed, the stages are the u8 ones only (no A / E float planes)."""
 
     MARK_ARM = 4
     BORDER = 3
 
-    def __init__(self, path, crop_region, roi_mask, fps, device=0, styles=None, event_hold=15, text=False, text_scale=None):
+    def __init__(self, path, crop_region, roi_mask, fps, device=0, styles=None, event_hold=15, text=False, text_scale=None, stages=(),
+                 stage_gain=None, stage_cols=None, stage_layers=14):
         (x0, y0), (x1, y1) = crop_region
         self.crop_region = [(int(x0), int(y0)), (int(x1), int(y1))]
         self.height, self.width = int(y1) - int(y0), int(x1) - int(x0)
@@ -112,6 +161,27 @@ class ReviewWriter:
         self.text_scale = int(text_scale) if text_scale is not None else text_scale_for(self.width, self.height, self.BORDER)
         if not 1 <= self.text_scale <= 8:
             raise ValueError("text_scale is 1..8")
+        self.stages = stage_keys(stages)
+        if self.stages and len(self.styles) < 6:
+            raise ValueError("stages need six styles (5: the captions' ink, 6: their plate)")
+        if len(self.stages) > _lib.MAX_PANELS:
+            raise ValueError("at most %d stage panels" % _lib.MAX_PANELS)
+        unknown = set(stage_gain or ()) - set(STAGE_KEYS)
+        if unknown:
+            raise ValueError("stage_gain is a dict by stage key (unknown: %s)" % ", ".join(sorted(unknown)))
+        self.stage_gain = dict(DEFAULT_STAGE_GAIN, **{k: int(v) for k, v in (stage_gain or {}).items()})
+        if any(not 1 <= g <= 255 for g in self.stage_gain.values()):
+            raise ValueError("a stage gain is 1..255")
+        self.stage_layers = int(stage_layers)
+        if not 0 <= self.stage_layers <= 15:
+            raise ValueError("stage_layers is 0..15 (bit 0..3: mask, boxes, marks, border)")
+        cells = 1 + len(self.stages)
+        self.stage_cols = int(stage_cols) if stage_cols is not None else default_stage_cols(self.height, self.width, cells)
+        if not 1 <= self.stage_cols <= _lib.MAX_PANEL_COLS:
+            raise ValueError("stage_cols is 1..%d" % _lib.MAX_PANEL_COLS)
+        self.frame_height, self.frame_width = self.height, self.width
+        if self.stages:
+            self.frame_height, self.frame_width, self.cell_origins = panel_layout(self.height, self.width, cells, self.stage_cols)
         self.device, self.event_hold = device, int(event_hold)
         self.frames = 0
         self._pending = []               # events still to be shown: (first frame number, last frame number, ((row, column), ...), ordinal)
@@ -120,10 +190,10 @@ class ReviewWriter:
         self._shown = []                 # of the last plan_window: per written frame (events counted so far, ((ordinal, last point), ...))
         self._dev = self._dev_bytes = 0
         self._host = None
-        hc, wc = (self.height + 1) // 2, (self.width + 1) // 2
-        self._luma, self._chroma = self.height * self.width, hc * wc
+        hc, wc = (self.frame_height + 1) // 2, (self.frame_width + 1) // 2
+        self._luma, self._chroma = self.frame_height * self.frame_width, hc * wc
         self._frame_bytes = len(FRAME_MARK) + self._luma + 2 * self._chroma
-        self._writer = Y4MWriter(path, self.width, self.height, fps)
+        self._writer = Y4MWriter(path, self.frame_width, self.frame_height, fps)
 
     # ---- what is drawn (no GPU): the render call's arguments for one window ----
     def plan_window(self, popped_frames, rejected=None, new_events=()):
@@ -178,6 +248,33 @@ class ReviewWriter:
                 labels.append((k, r, c, STYLE_EVENT, STYLE_PLATE, s, text))
         return labels
 
+    def plan_panels(self, frames):
+        """The panels of a window's written frames, as _lib.Context.render_review_panels takes them.  Device path: all frames carry
+        the same DevicePlanes (Frame.stage_planes = (planes, index)), it holds every stage asked for and the indices step by a
+        constant -- the panels then name that memory (the k-th popped frame of a queue of n has index n - 1 - k: a negative frame
+        stride from the oldest frame's plane).  Host path: processed_frames[name] of every frame, stacked."""
+        s, at = self.text_scale, self.BORDER + self.text_scale
+        held = [getattr(f, "stage_planes", None) for f in frames]
+        device = None
+        if all(h is not None for h in held):
+            planes, first = held[0]
+            step = held[1][1] - first if len(held) > 1 else 0
+            if (all(h[0] is planes and h[1] == first + k * step for k, h in enumerate(held)) and (planes.Hc, planes.Wc) == (self.height, self.width)
+                    and all(key in planes.stages for key in self.stages)):
+                device = (planes, first, step)
+        panels = []
+        for key in self.stages:
+            gain = self.stage_gain[key]
+            if device is not None:
+                planes, first, step = device
+                image = planes.Hc * planes.Wc
+                plane = {"ptr": planes.pointer(key) + first * image, "frame_stride": step * image, "row_stride": planes.Wc, "mem": _lib.MEM_DEVICE}
+            else:
+                plane = np.stack([np.asarray(f.processed_frames[STAGE_KEYS[key]], np.uint8) for f in frames])
+            panels.append({"plane": plane, "kind": "labels" if key == "labels" else "gray", "gain": gain, "layers": self.stage_layers,
+                           "caption": (at, at, STYLE_TEXT, STYLE_PLATE, s, stage_caption(key, gain))})
+        return panels, (device[0] if device is not None else None)
+
     def _render(self, frames, boxes, marks, frame_style, labels=None):
         """The window's frames composed and converted on the GPU: a uint8 array of len(frames) * frame bytes, every frame as the file
         holds it (the FRAME mark, then the Y, U and V planes), in page-locked memory.  labels: None, or the window's labels."""
@@ -195,11 +292,15 @@ class ReviewWriter:
             self._host = _lib.pinned_empty((F * fb,), np.uint8, device=self.device)
         base = self._dev + 8 - mark          # the first luma row on an 8-byte boundary: rows of a width that is a multiple of 8 leave as 8-byte stores
         dst = _lib.Yuv420Dst(y=base + mark, u=base + mark + self._luma, v=base + mark + self._luma + self._chroma,
-                             mem=_lib.MEM_DEVICE, layout=_lib.YUV_I420, y_row_stride=self.width, y_frame_stride=fb,
-                             c_row_stride=(self.width + 1) // 2, c_frame_stride=fb)
+                             mem=_lib.MEM_DEVICE, layout=_lib.YUV_I420, y_row_stride=self.frame_width, y_frame_stride=fb,
+                             c_row_stride=(self.frame_width + 1) // 2, c_frame_stride=fb)
         extra = {} if labels is None else {"labels": labels}          # (without text: the call as it always was)
-        ctx.render_review(stack, boxes=boxes, marks=marks, frame_style=frame_style, mask=self.roi_mask, styles=self.styles,
-                          mask_style=STYLE_MASK, mark_arm=self.MARK_ARM, border=self.BORDER, rect=(rx, ry, Wc, Hc), dst=dst, **extra)
+        render = ctx.render_review
+        if self.stages:
+            panels, held = self.plan_panels(frames)                   # (held: the planes stay alive until the call has returned)
+            render, extra["panels"], extra["cols"] = ctx.render_review_panels, panels, self.stage_cols
+        render(stack, boxes=boxes, marks=marks, frame_style=frame_style, mask=self.roi_mask, styles=self.styles,
+               mask_style=STYLE_MASK, mark_arm=self.MARK_ARM, border=self.BORDER, rect=(rx, ry, Wc, Hc), dst=dst, **extra)
         out = self._host[:F * fb]
         ctx._check(ctx._lib.swk_device_read(ctx._h, base, out.ctypes.data, F * fb))          # one device -> host copy
         out.reshape(F, fb)[:, :mark] = np.frombuffer(FRAME_MARK, np.uint8)
