@@ -133,6 +133,30 @@ int32_t swk_prof_refined_windows(swk_ctx *ctx, int64_t *refined, int64_t *unrefi
  * Pillow, integer for integer: a fused multiply-add or another summation order in the device code would show here. */
 int32_t swk_debug_resize_table(swk_ctx *ctx, int32_t first, int32_t count, int32_t route, int32_t *bounds, int32_t *coeffs);
 
+/* Diagnostic: the fused filter kernel of the batch calls (csrc/filters.hip, k_filter_fused<GEOM, R>: bilateral filter, to-zero
+ * threshold, 3 x 3 grey opening) alone, on u8 planes the CALLER chooses -- in a batch call it only ever reads what the RPCA left.  The
+ * planes go to the device and through the launcher swk_batch_run takes (planes == NULL: count planes of H x W pixels, densely packed,
+ * src and every output count * H * W bytes) or the one swk_batch_run_groups takes (planes[count] = size of every plane and its byte
+ * offset in src, a buffer of `total` bytes; the outputs are `total` bytes with the same layout, bytes that belong to no plane come back
+ * 0), with p's bil_d, bil_sigma_color, bil_sigma_space, bil_fma and thresh.  bilateral and thresh may be NULL: the launcher is then
+ * handed a null pointer for that stage, as in a batch call that does not ask for it.  Before the launch every device output and
+ * SWK_DEBUG_GUARD_BYTES behind it are filled with SWK_DEBUG_FILL; guard (may be NULL) receives 3 x SWK_DEBUG_GUARD_BYTES: the bytes
+ * behind the opened, the bilateral and the thresholded planes as the launch left them (SWK_DEBUG_FILL where the output is NULL).
+ * SWK_ERR_ARG, before any buffer or launch, by the batch calls' own rules: a plane below 4 x 4, a radius above 4, an opening window
+ * other than (3, 3), planes that overlap or leave the buffer. */
+#define SWK_DEBUG_GUARD_BYTES 64
+#define SWK_DEBUG_FILL 0xA5
+typedef struct swk_debug_plane { int32_t H, W; int64_t off; } swk_debug_plane;
+int32_t swk_debug_filter_fused(swk_ctx *ctx, const uint8_t *src, int32_t count, int32_t H, int32_t W, const swk_debug_plane *planes,
+                               int64_t total, const swk_params *p, uint8_t *bilateral, uint8_t *thresh, uint8_t *opened, uint8_t *guard);
+/* Diagnostic: the one-workgroup-per-frame labeller with region records (csrc/ccl.hip, k_ccl_frame<VEC, true>) alone, on count opened
+ * planes of H x W pixels the caller chooses, through the launcher swk_batch_run takes: labels [count][H][W] (u8, label & 255),
+ * segs [count][seg_cap] (zeros behind a frame's last record), nseg [count] (every live label value, also above seg_cap).
+ * SWK_ERR_ARG for a frame size the kernel does not take (no fall-back to the multi-kernel path), connectivity other than 4 or 8,
+ * seg_cap outside 1..255. */
+int32_t swk_debug_ccl_frame_props(swk_ctx *ctx, const uint8_t *opened, int32_t count, int32_t H, int32_t W, int32_t connectivity,
+                                  int32_t label_order, int32_t seg_cap, uint8_t *labels, swk_segment *segs, int32_t *nseg);
+
 /* White-box hook of the window tracker's tests: after skip_frames more frames, the next frame that swk_track_window steps takes
  * col4row[n] (n = its previous plus its current segments, each entry in [0, n)) instead of the solver's assignment -- the one way to an
  * assignment that leaves a current segment without a status (SWK_ERR_TRACK_STATUS), which no optimal solver returns.  Used up by that

@@ -53,6 +53,8 @@ class Segment(ctypes.Structure):
 SEGMENT_DTYPE = np.dtype([("label", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("r1", "<i4"), ("c1", "<i4"),
                           ("reserved_", "<i4"), ("area", "<i8"), ("sum_r", "<i8"), ("sum_c", "<i8")])
 assert SEGMENT_DTYPE.itemsize == ctypes.sizeof(Segment) == 48
+DEBUG_GUARD_BYTES, DEBUG_FILL = 64, 0xA5          # swk_debug_filter_fused (include/swk_debug.h)
+DEBUG_PLANE_DTYPE = np.dtype([("H", "<i4"), ("W", "<i4"), ("off", "<i8")])
 
 
 class Input(ctypes.Structure):
@@ -210,6 +212,9 @@ _SIGS = {
     "swk_debug_ialm_first_step": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double] + [ctypes.c_void_p] * 7),
     "swk_last_host_stage": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "swk_debug_resize_table": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "swk_debug_filter_fused": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                ctypes.c_int64, ctypes.POINTER(Params)] + [ctypes.c_void_p] * 4),
+    "swk_debug_ccl_frame_props": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 6 + [ctypes.c_void_p] * 3),
     "swk_last_eig_sweeps": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "swk_set_norm_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
     "swk_set_norm_guard": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
@@ -1103,6 +1108,43 @@ class Context:
         coeffs = np.empty((count, 24, 343), np.int32)
         self._check(self._lib.swk_debug_resize_table(self._h, int(first), int(count), int(route), _ptr(bounds), _ptr(coeffs)))
         return bounds, coeffs
+
+    def debug_filter_fused(self, src, params=None, geom=None, bilateral=True, thresh=True):
+        """swk_debug_filter_fused: the batch calls' fused filter kernel alone, on planes of the caller's choosing.  src: (count, H, W)
+        u8 planes (the uniform launcher), or with geom = [(H, W, byte offset), ...] a flat u8 buffer that holds the planes (the
+        per-frame-geometry launcher).  bilateral / thresh = False hand the launcher a null pointer for that stage.  Returns a dict
+        of the stages asked for and "opened", shaped like src, and "guard": (3, DEBUG_GUARD_BYTES) u8, the bytes behind the device's
+        opened, bilateral and thresholded outputs (DEBUG_FILL where untouched)."""
+        s = np.ascontiguousarray(src, np.uint8)
+        p = params if params is not None else default_params()
+        if geom is None:
+            if s.ndim != 3:
+                raise ValueError("planes must be (count, H, W)")
+            count, H, W, tab, total = s.shape[0], s.shape[1], s.shape[2], None, s.size
+        else:
+            if s.ndim != 1:
+                raise ValueError("with geom the planes lie in a flat buffer")
+            tab = np.array([tuple(int(v) for v in g) for g in geom], DEBUG_PLANE_DTYPE)
+            count, H, W, total = len(tab), 0, 0, s.size
+        out = {k: np.empty_like(s) for k, on in (("bilateral", bilateral), ("thresh", thresh), ("opened", True)) if on}
+        guard = np.zeros((3, DEBUG_GUARD_BYTES), np.uint8)
+        self._check(self._lib.swk_debug_filter_fused(self._h, _ptr(s), count, H, W, _ptr(tab), total, ctypes.byref(p),
+                                                     _ptr(out.get("bilateral")), _ptr(out.get("thresh")), _ptr(out["opened"]), _ptr(guard)))
+        out["guard"] = guard
+        return out
+
+    def debug_ccl_frame_props(self, opened, connectivity=8, label_order=ORDER_BLOCK2X2, seg_cap=255):
+        """swk_debug_ccl_frame_props: the batch calls' one-workgroup labeller with region records alone, on (count, H, W) u8 planes of
+        the caller's choosing.  Returns (labels (count, H, W) u8, segs (count, seg_cap), nseg (count,))."""
+        s = np.ascontiguousarray(opened, np.uint8)
+        if s.ndim != 3:
+            raise ValueError("planes must be (count, H, W)")
+        lab = np.empty_like(s)
+        segs = np.zeros((s.shape[0], seg_cap), SEGMENT_DTYPE)
+        nseg = np.zeros(s.shape[0], np.int32)
+        self._check(self._lib.swk_debug_ccl_frame_props(self._h, _ptr(s), s.shape[0], s.shape[1], s.shape[2], int(connectivity),
+                                                        int(label_order), int(seg_cap), _ptr(lab), _ptr(segs), _ptr(nseg)))
+        return lab, segs, nseg
 
     def regionprops_u8(self, labels, seg_cap=255):
         s, single = self._planes(labels)

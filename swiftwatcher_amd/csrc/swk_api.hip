@@ -2050,6 +2050,95 @@ int32_t swk_regionprops_u8(swk_ctx *ctx, const uint8_t *labels, int32_t count, i
     return sync(ctx);
 }
 
+int32_t swk_debug_filter_fused(swk_ctx *ctx, const uint8_t *src, int32_t count, int32_t H, int32_t W, const swk_debug_plane *planes,
+                               int64_t total, const swk_params *p, uint8_t *bilateral, uint8_t *thresh, uint8_t *opened, uint8_t *guard)
+{
+    if (!ctx || !src || !p || !opened || count < 1 || count > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "bad argument");
+    // the batch path's rules (run_batch), before any buffer or launch
+    if (p->open_kh != 3 || p->open_kw != 3) return fail(ctx, SWK_ERR_ARG, "only the (3,3) opening window is implemented");
+    if (bilateral_radius(p->bil_d, p->bil_sigma_space) > 4) return fail(ctx, SWK_ERR_ARG, "bilateral diameter > 9 is not supported");
+    std::vector<FrameGeom> hg;
+    int Hmax = 0, Wmax = 0;
+    if (planes) {
+        if (total < 1 || total >= (1ll << 40)) return fail(ctx, SWK_ERR_ARG, "bad buffer size");
+        hg.resize(count);
+        std::vector<std::pair<int64_t, int64_t>> span(count);          // [first, end) of every plane
+        for (int f = 0; f < count; ++f) {
+            if (planes[f].H < 4 || planes[f].W < 4 || planes[f].H > 32768 || planes[f].W > 32768)
+                return fail(ctx, SWK_ERR_ARG, "plane sides must be in 4..32768");
+            const int64_t px = (int64_t)planes[f].H * planes[f].W;
+            if (planes[f].off < 0 || planes[f].off > total - px) return fail(ctx, SWK_ERR_ARG, "a plane leaves the buffer");
+            hg[f] = {planes[f].H, planes[f].W, planes[f].off};
+            span[f] = {planes[f].off, planes[f].off + px};
+            Hmax = std::max(Hmax, planes[f].H);
+            Wmax = std::max(Wmax, planes[f].W);
+        }
+        std::sort(span.begin(), span.end());
+        for (int f = 1; f < count; ++f)
+            if (span[f].first < span[f - 1].second) return fail(ctx, SWK_ERR_ARG, "planes overlap");
+    } else {
+        if (H < 4 || W < 4 || H > 32768 || W > 32768) return fail(ctx, SWK_ERR_ARG, "plane sides must be in 4..32768");
+        total = (int64_t)count * H * W;
+        if (total >= (1ll << 40)) return fail(ctx, SWK_ERR_ARG, "bad buffer size");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t nb = (size_t)total, gb = SWK_DEBUG_GUARD_BYTES;
+    uint8_t *din, *dout[3] = {nullptr, nullptr, nullptr};          // opened, bilateral, thresholded
+    uint8_t *const host[3] = {opened, bilateral, thresh};
+    const Slot slot[3] = {SL_OPEN, SL_BIL, SL_THR};
+    FrameGeom *dgeom = nullptr;
+    NEED(ctx, SL_TMP_IN, nb, din);
+    for (int i = 0; i < 3; ++i)
+        if (host[i]) NEED(ctx, slot[i], nb + gb, dout[i]);
+    if (planes) NEED(ctx, SL_TMP_AUX, hg.size() * sizeof(FrameGeom), dgeom);
+    int rc = ensure_bilateral(ctx, p->bil_d, p->bil_sigma_color, p->bil_sigma_space);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(din, src, nb, hipMemcpyHostToDevice, s));
+    if (planes) HIPCHK(ctx, hipMemcpyAsync(dgeom, hg.data(), hg.size() * sizeof(FrameGeom), hipMemcpyHostToDevice, s));
+    // outputs and the guard behind them start from a non-zero byte: the launcher's clear is part of what is tested
+    for (int i = 0; i < 3; ++i)
+        if (dout[i]) HIPCHK(ctx, hipMemsetAsync(dout[i], SWK_DEBUG_FILL, nb + gb, s));
+    if (planes) launch_filter_fused_geom(s, din, count, Hmax, Wmax, dgeom, nb, ctx->bil, p->bil_fma, p->thresh, dout[1], dout[2], dout[0]);
+    else launch_filter_fused(s, din, count, H, W, ctx->bil, p->bil_fma, p->thresh, dout[1], dout[2], dout[0]);
+    for (int i = 0; i < 3; ++i) {
+        if (dout[i]) {
+            HIPCHK(ctx, hipMemcpyAsync(host[i], dout[i], nb, hipMemcpyDeviceToHost, s));
+            if (guard) HIPCHK(ctx, hipMemcpyAsync(guard + i * gb, dout[i] + nb, gb, hipMemcpyDeviceToHost, s));
+        } else if (guard) {
+            memset(guard + i * gb, SWK_DEBUG_FILL, gb);
+        }
+    }
+    return sync(ctx);          // (synchronous: hg lives on this stack frame)
+}
+
+int32_t swk_debug_ccl_frame_props(swk_ctx *ctx, const uint8_t *opened, int32_t count, int32_t H, int32_t W, int32_t connectivity,
+                                  int32_t label_order, int32_t seg_cap, uint8_t *labels, swk_segment *segs, int32_t *nseg)
+{
+    if (!ctx || !opened || !labels || !segs || !nseg || count < 1 || count > (1 << 24) || H < 1 || W < 1 || seg_cap < 1 || seg_cap > 255)
+        return fail(ctx, SWK_ERR_ARG, "bad argument");
+    if (connectivity != 4 && connectivity != 8) return fail(ctx, SWK_ERR_ARG, "connectivity must be 4 or 8");
+    if (!ccl_frame_supported(H, W)) return fail(ctx, SWK_ERR_ARG, "the one-workgroup labeller does not take this frame size");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->last.valid = false;          // SL_SEGS / SL_NSEG are about to be reused
+    const size_t px = (size_t)count * H * W, rec = (size_t)count * seg_cap * sizeof(swk_segment);
+    uint8_t *din, *dlab; swk_segment *dsegs; int32_t *dnseg;
+    NEED(ctx, SL_TMP_IN, px, din);
+    NEED(ctx, SL_LAB8, px, dlab);
+    NEED(ctx, SL_SEGS, rec, dsegs);
+    NEED(ctx, SL_NSEG, (size_t)count * 4, dnseg);
+    CclBuffers cb{};
+    int rc = ensure_ccl(ctx, count, H, W, &cb);
+    if (rc) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(din, opened, px, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(dsegs, 0, rec, ctx->stream));
+    launch_ccl_frame(ctx->stream, din, count, H, W, connectivity, label_order, cb, nullptr, dlab, true, seg_cap, dsegs, dnseg);
+    HIPCHK(ctx, hipMemcpyAsync(labels, dlab, px, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(segs, dsegs, rec, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(nseg, dnseg, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
 int32_t swk_classifier_input_window(swk_ctx *ctx, const uint8_t *crops, int64_t crops_bytes, const int64_t *offsets,
                                     const int32_t *hw, int32_t nseg, const float mean[3], const float std_[3],
                                     int32_t pad, int32_t channels_last, uint8_t *patches, float *net, int32_t net_mem)

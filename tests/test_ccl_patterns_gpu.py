@@ -5,8 +5,9 @@ and batches that put per-pixel-path frames between run-path ones -- at all four 
 CPU oracle; the multi-kernel path on frames too large for one workgroup; swk_regionprops_u8 on the u8-cast labels, seg_cap below the
 live label count included.  tests/test_ccl_patterns_cpu.py holds the oracle to scipy and numpy on the same frames.
 
-Batch level: k_ccl_frame<VEC, true[, GEOM]> (u8 labels + region records) cannot be handed its input: it reads the pipeline's opened
-image.  The windows of ccl_patterns.SCENES are built so that the OPENED frames have the wanted structure; every case asserts that
+Batch level: k_ccl_frame<VEC, true[, GEOM]> (u8 labels + region records) reads the pipeline's opened image (handed frames of the
+test's choosing it runs in tests/test_ccl_props_planes_gpu.py, through swk_debug_ccl_frame_props; the GEOM instantiation only here).
+The windows of ccl_patterns.SCENES are built so that the OPENED frames have the wanted structure; every case asserts that
 structure -- run counts, component counts, which branch of the kernel the frame takes -- on the CPU oracle's output before the GPU
 result is looked at, then compares all six stage planes, nseg and every region record with the oracle, and the labels / records
 with swk_ccl_u8 / swk_regionprops_u8 run on the call's own opened frames."""
