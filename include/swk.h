@@ -442,6 +442,34 @@ int32_t swk_ccl_u8(swk_ctx *ctx, const uint8_t *src, int32_t count, int32_t H, i
 int32_t swk_regionprops_u8(swk_ctx *ctx, const uint8_t *labels, int32_t count, int32_t H, int32_t W,
                            int32_t seg_cap, swk_segment *segs, int32_t *nseg);
 
+/* ---- shape sums of regions ---------------------------------------------------------------------------------
+ * The integer sums every other regionprops attribute (central, normalized and Hu moments, inertia tensor, axis lengths,
+ * eccentricity, orientation, perimeter, Euler number) is a function of; the floats are derived on the host
+ * (swiftwatcher_amd/image_filtering.py, ShapeMeasures).  All sums are integers, so a record does not depend on scheduling. */
+typedef struct swk_segment_shape {
+    int32_t label, reserved_;
+    int64_t m[10];     /* sum of r^p c^q over the region's pixels, ABSOLUTE plane coordinates, (p,q) in the order
+                          (0,0) (1,0) (0,1) (2,0) (1,1) (0,2) (3,0) (2,1) (1,2) (0,3) */
+    int64_t border;    /* border pixels: pixels of the region with a 4-neighbour that is not of the region (outside the plane counts) */
+    int64_t perim[3];  /* border pixels by skimage's perimeter weight: 1, sqrt(2), (1 + sqrt(2)) / 2 */
+    int64_t quads[3];  /* 2x2 windows of the zero-padded plane with exactly one, exactly three, and two diagonal pixels of the region */
+} swk_segment_shape;
+
+/* labels: u8 planes, frame f, pixel (r, c) at labels + f * frame_stride + r * row_stride + c (bytes; row_stride >= W, frame_stride
+ * of either sign).  mem = SWK_MEM_DEVICE: read where they lie; SWK_MEM_HOST: the H x W pixels of every frame are copied up.
+ * A region is the set of pixels with one non-zero value, as in swk_regionprops_u8: record k of frame f describes the same region
+ * as its segs[f][k] (ascending value), m[0], m[1], m[2] = that record's area, sum_r, sum_c.  nseg[f] = values present (may exceed
+ * seg_cap); slots past it are zero.  shapes: host [count][seg_cap]; nseg: host [count].
+ * Perimeter classes (skimage.measure.perimeter(image, 4) of scikit-image 0.15.0 restated): for a border pixel of value v, with
+ * a / b = how many of its four edge / four diagonal neighbours are border pixels of v, code = 1 + 2 a + 10 b; codes 5 7 15 17 25 27
+ * count in perim[0], 21 33 in perim[1], 13 23 in perim[2], every other code in border alone.
+ * 8-connected Euler number = (quads[0] - quads[1] - 2 * quads[2]) / 4; a window holding several values counts once for each.
+ * SWK_ERR_ARG, before anything is copied or launched and with the outputs untouched: a null pointer, count < 1, H or W outside
+ * 1..32768, seg_cap outside 1..255, row_stride < W, an unknown mem, H * W * max(H - 1, W - 1)^3 >= 2^63 (below it no degree-3
+ * sum overflows; 4096 x 4096 passes).  SWK_ERR_CAPACITY: more than 2^24 frames. */
+int32_t swk_segment_shapes_u8(swk_ctx *ctx, const uint8_t *labels, int32_t mem, int32_t count, int32_t H, int32_t W,
+                              int64_t frame_stride, int64_t row_stride, int32_t seg_cap, swk_segment_shape *shapes, int32_t *nseg);
+
 /* ---- classifier input (segment_classification.py:18-24) -------------------------------------------------
  * ToPILImage -> Resize((24,24)) (Pillow's antialiased bilinear resampling, 8-bit fixed point, restated
  * exactly) -> Pad(100) -> ToTensor -> Normalize(mean, std) for nseg segment crops.

@@ -1,5 +1,6 @@
 """python -m swiftwatcher_amd SOURCE [SOURCE ...] (--corners X1,Y1,X2,Y2 | --attributes FILE) [--start N] [--end N]
-       [--classify WEIGHTS] [--out DIR] [--review PATH [--review-text] [--review-stages LIST]] [--windows-per-call K] [--device D]
+       [--classify WEIGHTS] [--out DIR] [--shape-props] [--review PATH [--review-text] [--review-stages LIST]] [--windows-per-call K]
+       [--device D]
 
 The reference's main() (__main__.py:13-53) without its UI: every SOURCE -- a .y4m file, or "-" for a YUV4MPEG2 stream on standard
 input (`ffmpeg -i evening.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners 812,640,1105,642`) -- is counted by
@@ -12,7 +13,9 @@ several sources are given).  PATH may be a FIFO (`--review fifo & ffmpeg -i fifo
 JSON lines.  --review-text (with --review only) writes the tables' keys into every frame of the review: a status line "F000123
 00:00:04.104 S03 R01 E007" (frame number, timestamp, segments, boxes the classifier removed, events so far) and the number #k of
 every event shown, k its row in the events table.  --review-stages rpca,thresh,labels (with --review only; combines with
---review-text) puts those stage images of every frame beside it as captioned panels: keys gray rpca bilateral thresh opened labels."""
+--review-text) puts those stage images of every frame beside it as captioned panels: keys gray rpca bilateral thresh opened labels.
+--shape-props measures every segment's shape on the GPU (pipeline.count_swifts' shape_props=True) and, with --out DIR, also writes
+DIR/segments_shape.csv: one row per segment of every event (SHAPE_CSV_COLUMNS)."""
 import argparse
 import json
 import os
@@ -65,6 +68,7 @@ def build_parser():
     p.add_argument("--end", type=int, default=0, metavar="N", help="frame count to stop at (0: the whole video)")
     p.add_argument("--classify", metavar="WEIGHTS", help="filter segments with the classifier of this state_dict file")
     p.add_argument("--out", metavar="DIR", help="write the result tables (CSV) here")
+    p.add_argument("--shape-props", action="store_true", help="measure the segments' shapes; with --out also write segments_shape.csv")
     p.add_argument("--review", type=_review_path, metavar="PATH", help="write a review video (.y4m) of the count here")
     p.add_argument("--review-text", action="store_true", help="with --review: draw frame number, time, counts and event numbers into it")
     p.add_argument("--review-stages", type=_stage_list, default=(), metavar="LIST",
@@ -111,6 +115,30 @@ def plan(argv):
     return args, jobs
 
 
+SHAPE_CSV_COLUMNS = ("event", "frame_number", "label", "area", "centroid_r", "centroid_c", "orientation", "eccentricity",
+                     "major_axis_length", "minor_axis_length", "perimeter", "extent", "euler_number")
+
+
+def shape_rows(events):
+    """One row (SHAPE_CSV_COLUMNS) per segment of every event; event = the event's index in the list, as in the events table."""
+    rows = []
+    for k, event in enumerate(events):
+        for s in event:
+            rows.append((k, s.parent_frame_number, s.label, s.area, s.centroid[0], s.centroid[1], s.orientation, s.eccentricity,
+                         s.major_axis_length, s.minor_axis_length, s.perimeter, s.extent, s.euler_number))
+    return rows
+
+
+def write_shape_csv(path, events):
+    """segments_shape.csv: floats written with repr, so that reading them back gives the attributes bit for bit."""
+    import csv
+    with open(path, "w", newline="") as fh:
+        w = csv.writer(fh)
+        w.writerow(SHAPE_CSV_COLUMNS)
+        for row in shape_rows(events):
+            w.writerow([repr(float(x)) if isinstance(x, float) else int(x) for x in row])
+
+
 def main(argv=None):
     args, jobs = plan(argv)
     from . import event_classification as ec
@@ -135,7 +163,7 @@ def main(argv=None):
         try:
             count, events = pipeline.count_swifts(reader, corners=corners, classifier=classifier, device=args.device,
                                                   windows_per_call=args.windows_per_call, review=review or None, review_text=args.review_text,
-                                                  review_stages=args.review_stages)
+                                                  review_stages=args.review_stages, **({"shape_props": True} if args.shape_props else {}))
             frames, fps, first, last = reader.total_frames, reader.fps, reader.start_frame, reader.end_frame
         except (OSError, ValueError) as exc:
             print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)
@@ -147,6 +175,8 @@ def main(argv=None):
             out_dir = args.out if len(jobs) == 1 else os.path.join(args.out, stem)
             with _stdout_to_stderr():                                              # (export_results prints its progress line)
                 export_results(out_dir, ec.classify_events(events), fps, first, last)
+            if args.shape_props:
+                write_shape_csv(os.path.join(out_dir, "segments_shape.csv"), events)
         print(json.dumps({"source": source, "frames": int(frames), "events": len(events), "count": int(count)}), flush=True)
     return 0
 

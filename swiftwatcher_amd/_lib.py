@@ -53,6 +53,11 @@ class Segment(ctypes.Structure):
 SEGMENT_DTYPE = np.dtype([("label", "<i4"), ("r0", "<i4"), ("c0", "<i4"), ("r1", "<i4"), ("c1", "<i4"),
                           ("reserved_", "<i4"), ("area", "<i8"), ("sum_r", "<i8"), ("sum_c", "<i8")])
 assert SEGMENT_DTYPE.itemsize == ctypes.sizeof(Segment) == 48
+# swk_segment_shape: m = sums of r^p c^q in the order of SHAPE_MOMENT_ORDER
+SHAPE_DTYPE = np.dtype([("label", "<i4"), ("reserved_", "<i4"), ("m", "<i8", (10,)), ("border", "<i8"), ("perim", "<i8", (3,)),
+                        ("quads", "<i8", (3,))])
+assert SHAPE_DTYPE.itemsize == 144
+SHAPE_MOMENT_ORDER = ((0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (3, 0), (2, 1), (1, 2), (0, 3))
 DEBUG_GUARD_BYTES, DEBUG_FILL = 64, 0xA5          # swk_debug_filter_fused (include/swk_debug.h)
 DEBUG_PLANE_DTYPE = np.dtype([("H", "<i4"), ("W", "<i4"), ("off", "<i8")])
 
@@ -204,6 +209,7 @@ _SIGS = {
     "swk_resize_linear_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 6 + [ctypes.c_void_p]),
     "swk_ccl_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_regionprops_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "swk_segment_shapes_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_int64] * 2 + [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_classifier_input": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "swk_set_sparse_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
     "swk_set_integer_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
@@ -1153,6 +1159,50 @@ class Context:
         self._check(self._lib.swk_regionprops_u8(self._h, _ptr(s), s.shape[0], s.shape[1], s.shape[2], seg_cap,
                                                  _ptr(segs), _ptr(nseg)))
         return (segs[0, :nseg[0]], int(nseg[0])) if single else (segs, nseg)
+
+    def segment_shapes_raw(self, ptr, mem, count, H, W, frame_stride, row_stride, seg_cap, shapes, nseg):
+        """swk_segment_shapes_u8 on a raw plane pointer; shapes / nseg: the arrays it fills (or None, to probe its refusals)."""
+        self._check(self._lib.swk_segment_shapes_u8(self._h, ptr, int(mem), int(count), int(H), int(W), int(frame_stride), int(row_stride),
+                                                    int(seg_cap), _ptr(shapes), _ptr(nseg)))
+
+    def segment_shapes_u8(self, labels, seg_cap=255):
+        """swk_segment_shapes_u8: the shape sums (SHAPE_DTYPE records, ascending label: record k of frame f is the region of
+        regionprops_u8's segs[f][k]) of u8 label planes.  labels: a host array (F, H, W) or (H, W) of any frame and row strides
+        (copied up), or planes that are on the GPU and are read where they lie -- a DevicePlanes with a "labels" stage, a torch
+        uint8 tensor (F, H, W) on this context's GPU, or a dict (ptr, shape=(F, H, W)[, frame_stride, row_stride]) naming device
+        memory.  Returns (records (F, seg_cap), nseg (F,)); for one (H, W) plane (records[:nseg], nseg)."""
+        single = False
+        keep = labels
+        if isinstance(labels, DevicePlanes):
+            F, H, W = labels.F, labels.Hc, labels.Wc
+            ptr, mem, fs, rs = labels.pointer("labels"), MEM_DEVICE, H * W, W
+        elif isinstance(labels, dict):
+            F, H, W = (int(x) for x in labels["shape"])
+            ptr, mem = labels["ptr"], labels.get("mem", MEM_DEVICE)
+            rs = int(labels.get("row_stride", W))
+            fs = int(labels.get("frame_stride", H * rs))
+        elif hasattr(labels, "data_ptr") and getattr(labels, "is_cuda", False):
+            if str(labels.dtype) != "torch.uint8" or labels.dim() != 3 or labels.stride(2) != 1:
+                raise ValueError("device label planes are uint8 (F, H, W), contiguous along columns")
+            F, H, W = (int(x) for x in labels.shape)
+            ptr, mem, fs, rs = labels.data_ptr(), MEM_DEVICE, int(labels.stride(0)), int(labels.stride(1))
+        else:
+            s = np.asarray(labels)
+            if s.dtype != np.uint8 or s.ndim not in (2, 3):
+                raise ValueError("label planes are uint8 (F, H, W) or (H, W)")
+            single = s.ndim == 2
+            if single:
+                s = s[None]
+            if s.strides[2] != 1 or s.strides[1] < s.shape[2]:
+                s = np.ascontiguousarray(s)
+            keep = s
+            F, H, W = s.shape
+            ptr, mem, fs, rs = s.ctypes.data, MEM_HOST, s.strides[0], s.strides[1]
+        shapes = np.zeros((F, seg_cap), SHAPE_DTYPE)
+        nseg = np.zeros(F, np.int32)
+        self.segment_shapes_raw(ptr, mem, F, H, W, fs, rs, seg_cap, shapes, nseg)
+        del keep
+        return (shapes[0, :nseg[0]], int(nseg[0])) if single else (shapes, nseg)
 
 
 def stage_frames(frames, y0, y1, x0, x1, dst, threads=4):

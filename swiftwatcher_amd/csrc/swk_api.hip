@@ -23,7 +23,7 @@ enum Slot {
     SL_ROI = 0, SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8, SL_LAB32, SL_A, SL_Y, SL_E, SL_PN,
     SL_BM, SL_VPREV, SL_GPART, SL_ZZPART, SL_WIN, SL_ACTIVE, SL_PARENT, SL_ROOTBITS, SL_WORDPREFIX,
     SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_TMP_IN, SL_TMP_OUT, SL_TMP_AUX, SL_COLORW, SL_SPACEW,
-    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_SEGLARGE, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_REVIEW, SL_COUNT
+    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_SEGLARGE, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_REVIEW, SL_SHAPE_TAB, SL_SHAPE_REC, SL_SHAPE_NSEG, SL_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int fam; };
@@ -2046,6 +2046,43 @@ int32_t swk_regionprops_u8(swk_ctx *ctx, const uint8_t *labels, int32_t count, i
     HIPCHK(ctx, hipMemsetAsync(dsegs, 0, (size_t)count * seg_cap * sizeof(swk_segment), ctx->stream));
     launch_regionprops(ctx->stream, din, count, H, W, cb, seg_cap, dsegs, dnseg);
     HIPCHK(ctx, hipMemcpyAsync(segs, dsegs, (size_t)count * seg_cap * sizeof(swk_segment), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(nseg, dnseg, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
+int32_t swk_segment_shapes_u8(swk_ctx *ctx, const uint8_t *labels, int32_t mem, int32_t count, int32_t H, int32_t W, int64_t frame_stride,
+                              int64_t row_stride, int32_t seg_cap, swk_segment_shape *shapes, int32_t *nseg)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!labels || !shapes || !nseg) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (count < 1) return fail(ctx, SWK_ERR_ARG, "count must be at least 1");
+    if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(ctx, SWK_ERR_ARG, "plane size must be 1..32768 on each side");
+    if (seg_cap < 1 || seg_cap > 255) return fail(ctx, SWK_ERR_ARG, "seg_cap must be in 1..255");
+    if (row_stride < W) return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
+    if (mem != SWK_MEM_HOST && mem != SWK_MEM_DEVICE) return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
+    {
+        const unsigned __int128 side = (unsigned)((H > W ? H : W) - 1);
+        if ((unsigned __int128)H * (unsigned)W * side * side * side >= ((unsigned __int128)1 << 63))
+            return fail(ctx, SWK_ERR_ARG, "plane too large: H * W * max(H - 1, W - 1)^3 must stay below 2^63");
+    }
+    if (count > (1 << 24)) return fail(ctx, SWK_ERR_CAPACITY, "too many frames in one call");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint8_t *planes = labels;
+    int64_t fs = frame_stride, rs = row_stride;
+    if (mem == SWK_MEM_HOST) {
+        uint8_t *din;
+        NEED(ctx, SL_TMP_IN, (size_t)count * H * W, din);
+        const int rc = upload_rects(ctx, din, labels, row_stride, frame_stride, (size_t)W, (size_t)H, count);
+        if (rc) return rc;
+        planes = din; fs = (int64_t)H * W; rs = W;
+    }
+    void *table; swk_segment_shape *drec; int32_t *dnseg;
+    const size_t rec_b = (size_t)count * seg_cap * sizeof(swk_segment_shape);
+    NEED(ctx, SL_SHAPE_TAB, shape_table_bytes(count), table);
+    NEED(ctx, SL_SHAPE_REC, rec_b, drec);
+    NEED(ctx, SL_SHAPE_NSEG, (size_t)count * 4, dnseg);
+    launch_segment_shapes(ctx->stream, planes, count, H, W, fs, rs, table, seg_cap, drec, dnseg);
+    HIPCHK(ctx, hipMemcpyAsync(shapes, drec, rec_b, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(nseg, dnseg, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
 }

@@ -249,6 +249,12 @@ void launch_ccl_frame(hipStream_t s, const uint8_t *src, int F, int H, int W, in
 size_t ccl_words(int H, int W);
 size_t ccl_padded(int H, int W);
 
+// shape_props.hip: the shape sums of every label value of F u8 planes (device memory; frame f, pixel (r, c) at labels + f * fs +
+// r * rs + c) as ascending-label records; table: shape_table_bytes(F) bytes of scratch; shapes [F][seg_cap] and nseg [F] on the device
+size_t shape_table_bytes(int F);
+void launch_segment_shapes(hipStream_t s, const uint8_t *labels, int F, int H, int W, int64_t fs, int64_t rs, void *table, int seg_cap,
+                           swk_segment_shape *shapes, int32_t *nseg);
+
 
 // ---- several groups of windows in one call ---------------------------------------------------------------
 // swk_batch_run and swk_batch_run_groups share one driver (run_batch, swk_api.hip).  A call of one group takes the uniform

@@ -75,11 +75,27 @@ def batch_keys(segs, nseg, frame_numbers):
     return segment_keys(np.repeat(np.asarray(frame_numbers, dtype=np.int64), np.minimum(nseg, cap)), live["label"])
 
 
-def window_segments(segs, nseg, slots, min_seg_size, crop_region, batch=None, first=0):
+def window_shapes(ctx, planes, segs, nseg):
+    """The shape records (image_filtering.shape_records' tuples) of a batch_run's segments in batch order, by ONE
+    swk_segment_shapes_u8 call over its label planes where they lie on the GPU (planes: the batch's _lib.DevicePlanes with a
+    "labels" stage); segs / nseg: the batch's region records, which the shape records must match label for label."""
+    cap = max(int(nseg.max()), 1) if len(nseg) else 1          # (the batch has counted the regions: no more slots than it found)
+    recs, count = ctx.segment_shapes_u8(planes, seg_cap=cap)
+    live = recs[np.arange(cap)[None, :] < nseg[:, None]]
+    known = segs[np.arange(segs.shape[1])[None, :] < nseg[:, None]]
+    if not np.array_equal(count, nseg) or not np.array_equal(live["label"], known["label"]) \
+            or not np.array_equal(live["m"][:, 0], known["area"]):
+        raise _lib.SwkError("the shape records do not describe the batch's regions")
+    return img.shape_records(live)
+
+
+def window_segments(segs, nseg, slots, min_seg_size, crop_region, batch=None, first=0, shapes=None):
     """Segment objects of a whole batch_run at once: slots = the Frame objects in the batch's frame order; segs / nseg = its
     region records.  The same attributes Segment.__init__ sets (label, bbox, centroid = sum / area in float64, area), made
     from whole-batch arrays instead of one record at a time; segment images are cut when first read.  first: the batch index of
-    the first of these segments."""
+    the first of these segments.  shapes: window_shapes' records, one per segment in this order -- each is bound to its segment,
+    whose shape properties (image_filtering.ShapeMeasures) are derived from it when first read."""
+    shapes = iter(shapes) if shapes is not None else None
     F, cap = segs.shape
     live = segs[np.arange(cap)[None, :] < nseg[:, None]]              # frame order, ascending label
     area = live["area"]
@@ -106,6 +122,8 @@ def window_segments(segs, nseg, slots, min_seg_size, crop_region, batch=None, fi
                           "_batch": batch, "_index": k}
             if batch is None:
                 del s.__dict__["_batch"], s.__dict__["_index"]
+            if shapes is not None:
+                s.__dict__["_shape"] = next(shapes)
             out.append(s)
             k += 1
         slot.segments = out
@@ -115,7 +133,10 @@ class Segment:
     """data_structures.py:16-30.  The reference copies every public regionprops attribute
     (about 9 ms per segment); only label/bbox/centroid/area are ever read downstream
     (segment_tracking.py:139-222, segment_classification.py:30,42), so only those exist here.
-    segment_image may be handed in as a zero-argument callable: it is then cut when first read."""
+    segment_image may be handed in as a zero-argument callable: it is then cut when first read.
+    A segment of a window that was segmented with shape_props=True is bound to its shape record (swk_segment_shape) and also
+    answers image_filtering.SHAPE_PROPERTIES (moments, orientation, eccentricity, perimeter, ...): the floats are made when one
+    is first read (image_filtering.ShapeMeasures, which documents the formulas and the deviations)."""
 
     def __init__(self, regionprops, frame_number, timestamp, segment_image):
         self.parent_frame_number = frame_number
@@ -127,6 +148,20 @@ class Segment:
         self.bbox = regionprops.bbox
         self.centroid = regionprops.centroid
         self.area = regionprops.area
+
+    def __getattr__(self, name):
+        # (reached only for names the instance does not have: the shape properties, or a mistake)
+        if name in img.SHAPE_PROPERTIES:
+            d = self.__dict__
+            if d.get("_shape") is None:
+                raise AttributeError("%s: this segment has no shape record (segment with shape_props=True)" % name)
+            measures = d.get("_measures")
+            if measures is None:
+                measures = d["_measures"] = img.ShapeMeasures(d["bbox"], d["_shape"])
+            return getattr(measures, name)
+        if name in img.SHAPE_NOT_PROVIDED:
+            raise img._not_provided(name)
+        raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
 
     @property
     def segment_image(self):
@@ -148,7 +183,7 @@ class Segment:
 
     def __deepcopy__(self, memo):
         """copy.deepcopy(tracker.detected_events) (__main__.py:100): plain data only -- the image is resolved, the link to the
-        window's device-side state is dropped."""
+        window's device-side state is dropped.  The shape record (and what was derived from it) is plain data and is kept."""
         import copy
         new = Segment.__new__(Segment)
         memo[id(self)] = new
@@ -252,11 +287,12 @@ class Presegmented:
     """One window that a reader segmented ahead of the counting loop (io_frames.PresegmentingReader): the frames as get_n_frames handed
     them out (oldest first) and, per frame, the Segment objects segment_queue would have made.  Registered under the oldest frame's
     identity; FrameQueue.segment_queue takes it when its queue holds exactly these frames and was asked for the same regions."""
-    __slots__ = ("frames", "segments", "crop_region", "min_seg_size", "params", "iters", "device")
+    __slots__ = ("frames", "segments", "crop_region", "min_seg_size", "params", "iters", "device", "shape_props")
 
-    def __init__(self, frames, segments, crop_region, min_seg_size, params, iters, device):
+    def __init__(self, frames, segments, crop_region, min_seg_size, params, iters, device, shape_props=False):
         self.frames, self.segments, self.crop_region = frames, segments, [tuple(crop_region[0]), tuple(crop_region[1])]
         self.min_seg_size, self.params, self.iters, self.device = tuple(min_seg_size), params, iters, device
+        self.shape_props = bool(shape_props)          # the segments carry shape records
 
 
 PRESEGMENTED = {}          # id(oldest frame of the window) -> Presegmented
@@ -331,10 +367,14 @@ class FrameQueue(deque):
     is queue index j (image_filtering.py:234-237).
 
     keep_stages=True (the default, like the reference) makes the six stage images available under
-    Frame.processed_frames; they stay on the GPU until read.  keep_stages=False does not produce them at all."""
+    Frame.processed_frames; they stay on the GPU until read.  keep_stages=False does not produce them at all.
+    shape_props=True: the window's label planes are kept on the GPU (also with keep_stages=False, when they are the only stage
+    produced), one swk_segment_shapes_u8 call reads them there, and every Segment of the window answers the shape properties
+    (Segment, image_filtering.ShapeMeasures).  Off, nothing is different: no labels plane, no extra call."""
 
-    def __init__(self, queue_size=21, device=0, params=None, keep_stages=True):
+    def __init__(self, queue_size=21, device=0, params=None, keep_stages=True, shape_props=False):
         deque.__init__(self, maxlen=queue_size)
+        self.shape_props = bool(shape_props)
         self.frames_read = 0
         self.frames_processed = 0
         self.device = device
@@ -397,7 +437,7 @@ class FrameQueue(deque):
         if pre is None or len(pre.frames) != n or any(pre.frames[k] is not self[n - 1 - k].frame for k in range(n)):
             return False
         if (pre.crop_region != [tuple(crop_region[0]), tuple(crop_region[1])] or pre.min_seg_size != tuple(min_seg_size)
-                or pre.params is not self.params or pre.device != self.device):
+                or pre.params is not self.params or pre.device != self.device or (self.shape_props and not pre.shape_props)):
             return False
         del PRESEGMENTED[id(self[-1].frame)]
         for k in range(n):
@@ -432,7 +472,7 @@ class FrameQueue(deque):
         stack, (rx, ry), (Hc, Wc), backwards = self._stage_window(min_seg_size, crop_region)
         n = stack.shape[0]
         ctx = _lib.default_context(self.device)
-        stages = tuple(STAGE_KEYS) if self.keep_stages else ()
+        stages = tuple(STAGE_KEYS) if self.keep_stages else ("labels",) if self.shape_props else ()
         res = ctx.batch_run(stack, 1, n, crop=(rx, ry, Wc, Hc), params=self.params, stages=stages, device_stages=True,
                             reverse_frames=backwards)
         generation = res["generation"]
@@ -454,9 +494,10 @@ class FrameQueue(deque):
         if hint is not None and batch is not None:
             batch.launch(hint)
         planes = res.get("planes")
-        if planes is not None:
+        shapes = window_shapes(ctx, planes, res["segs"], nseg) if self.shape_props else None
+        if planes is not None and self.keep_stages:
             _attach_planes(planes, list(self))
-        window_segments(res["segs"], nseg, list(self), tuple(min_seg_size), crop_region, batch)
+        window_segments(res["segs"], nseg, list(self), tuple(min_seg_size), crop_region, batch, shapes=shapes)
 
 
 def _attach_planes(planes, slots):
@@ -604,7 +645,14 @@ def _margin_rect(frame_shape, crop_region, min_seg_size):
     return (max(y0 - my, 0), min(y1 + my, Hf), max(x0 - mx, 0), min(x1 + mx, Wf)), (x0, y0, x1, y1)
 
 
-def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, params=None, classifier=None, owner=None, info=None, stages=()):
+def _with_labels(stages, shape_props):
+    """The stage keys a batch is run with: the caller's, plus the label planes when shape records are wanted."""
+    stages = tuple(stages)
+    return stages + ("labels",) if shape_props and "labels" not in stages else stages
+
+
+def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, params=None, classifier=None, owner=None, info=None, stages=(),
+                    shape_props=False):
     """Several FrameQueue-fuls in ONE library call.  windows: list of (frames, frame_numbers, timestamps) triples as
     FrameReader.get_n_frames returns them (oldest frame first), all of the same length n.  Returns one list of Frame
     objects per window in POP order (oldest first, the order __main__.py:81-92 consumes them), segments attached
@@ -613,7 +661,8 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
     classifier: its scoring of the batch's segments is started on the GPU before the Python objects are made.  owner: an object whose
     _classifier_hint the batch sets when a classifier asks for its scores (a reader that segments ahead).  info: a dict that receives
     'iters' (IALM iterations per window).  stages: the stage images (keys of STAGE_KEYS) to keep on the GPU -- they become the
-    frames' processed_frames entries and Frame.stage_planes; none are produced by default."""
+    frames' processed_frames entries and Frame.stage_planes; none are produced by default.  shape_props: every segment is bound to
+    its shape record (one swk_segment_shapes_u8 call over the batch's label planes, which are then produced on the GPU too)."""
     if not windows:
         return []
     n = len(windows[0][0])
@@ -635,8 +684,8 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
     for w in order:
         ordered.extend(windows[w][0][::-1])                  # queue index 0 = newest = last frame read (:134)
     stack, (rx, ry), (Hc, Wc), backwards = stack_frames(ordered, crop_region, min_seg_size, ctx.staging, device)
-    res = ctx.batch_run(stack, len(windows), n, crop=(rx, ry, Wc, Hc), params=params, stages=tuple(stages), device_stages=True,
-                        reverse_frames=backwards)
+    res = ctx.batch_run(stack, len(windows), n, crop=(rx, ry, Wc, Hc), params=params, stages=_with_labels(stages, shape_props),
+                        device_stages=True, reverse_frames=backwards)
     nseg = res["nseg"]
     if np.any(nseg > res["segs"].shape[1]):
         raise _lib.SwkError("more regions in a frame than seg_cap")
@@ -656,9 +705,10 @@ def segment_windows(windows, crop_region, min_seg_size=(24, 24), device=0, param
         for k, fr in enumerate(popped):
             slots[pos[w] * n + (n - 1 - k)] = fr
         out.append(popped)
-    if res.get("planes") is not None:
+    shapes = window_shapes(ctx, res["planes"], res["segs"], nseg) if shape_props else None
+    if res.get("planes") is not None and tuple(stages):
         _attach_planes(res["planes"], slots)
-    window_segments(res["segs"], nseg, slots, tuple(min_seg_size), crop_region, batch)
+    window_segments(res["segs"], nseg, slots, tuple(min_seg_size), crop_region, batch, shapes=shapes)
     return out
 
 
@@ -676,12 +726,13 @@ def _group_staging(ctx, slot, shape):
     return arr
 
 
-def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, classifier=None, stages=()):
+def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, classifier=None, stages=(), shape_props=False):
     """segment_windows for several videos in ONE library call (swk_batch_run_groups).  groups: list of (windows, crop_region), windows
     as segment_windows takes them; every window of every group has the same length n, the crop regions differ.  Returns, per group,
     what segment_windows(windows, crop_region, ...) returns.  The classifier's scoring of all groups' segments starts once, over the
     whole call: its head is batch-independent, so every score equals the one of a per-group batch.  stages: as
-    segment_windows' -- the stage images every group keeps on the GPU."""
+    segment_windows' -- the stage images every group keeps on the GPU.  shape_props: as segment_windows', with one
+    swk_segment_shapes_u8 call per group (the groups' geometries differ)."""
     groups = [(list(w), cr) for w, cr in groups]
     live = [i for i, (w, _) in enumerate(groups) if w]
     if not live:
@@ -698,7 +749,7 @@ def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, 
         stack, (rx, ry), (Hc, Wc), backwards = stack_frames(ordered, crop_region, min_seg_size,
                                                             lambda shape, s=slot: _group_staging(ctx, s, shape), device)
         specs.append(dict(frames=stack, nwin=len(windows), n=n, crop=(rx, ry, Wc, Hc), reverse_frames=backwards))
-    results = ctx.batch_run_groups(specs, params=params, stages=tuple(stages), device_stages=True)
+    results = ctx.batch_run_groups(specs, params=params, stages=_with_labels(stages, shape_props), device_stages=True)
     for r in results:
         if np.any(r["nseg"] > r["segs"].shape[1]):
             raise _lib.SwkError("more regions in a frame than seg_cap")
@@ -722,8 +773,9 @@ def segment_window_groups(groups, min_seg_size=(24, 24), device=0, params=None, 
             popped = [Frame(frames[k], numbers[k], stamps[k]) for k in range(n)]          # oldest first
             slots.extend(popped[::-1])                                                   # the batch's frame order: newest first
             out[i].append(popped)
-        if res.get("planes") is not None:
+        shapes = window_shapes(ctx, res["planes"], res["segs"], res["nseg"]) if shape_props else None
+        if res.get("planes") is not None and tuple(stages):
             _attach_planes(res["planes"], slots)
-        window_segments(res["segs"], res["nseg"], slots, tuple(min_seg_size), crop_region, batch, first)
+        window_segments(res["segs"], res["nseg"], slots, tuple(min_seg_size), crop_region, batch, first, shapes=shapes)
         first += int(res["nseg"].sum())
     return out

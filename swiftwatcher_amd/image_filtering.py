@@ -200,10 +200,227 @@ def regionprops_from_records(records):
                                                      cr, cc)]
 
 
-def get_segment_properties(frame):
-    """image_filtering.py:332-335: one RegionProps per distinct nonzero label, ascending."""
+def get_segment_properties(frame, shape=False):
+    """image_filtering.py:332-335: one RegionProps per distinct nonzero label, ascending.  shape=True: ShapeRegionProps, which
+    also carry the shape properties of ShapeMeasures (one more library call, swk_segment_shapes_u8)."""
     segs, _ = _ctx().regionprops_u8(frame)
-    return regionprops_from_records(segs)
+    props = regionprops_from_records(segs)
+    if not shape:
+        return props
+    recs, _ = _ctx().segment_shapes_u8(np.ascontiguousarray(frame, np.uint8))
+    return [ShapeRegionProps(p.label, p.bbox, p.centroid, p.area, ShapeMeasures(p.bbox, rec)) for p, rec in zip(props, shape_records(recs))]
+
+
+###############################################################################
+# shape properties -- derived on the host from the exact integer sums of swk_segment_shapes_u8
+###############################################################################
+
+SHAPE_PROPERTIES = ("moments", "local_centroid", "moments_central", "moments_normalized", "moments_hu", "inertia_tensor",
+                    "inertia_tensor_eigvals", "major_axis_length", "minor_axis_length", "eccentricity", "orientation", "bbox_area",
+                    "extent", "equivalent_diameter", "perimeter", "euler_number")
+SHAPE_NOT_PROVIDED = ("convex_area", "convex_image", "solidity", "filled_area", "filled_image", "image", "coords", "intensity_image",
+                      "max_intensity", "mean_intensity", "min_intensity", "weighted_centroid", "weighted_local_centroid",
+                      "weighted_moments", "weighted_moments_central", "weighted_moments_hu", "weighted_moments_normalized")
+_MOMENT_INDEX = {pq: k for k, pq in enumerate(_lib.SHAPE_MOMENT_ORDER)}
+_BINOM = ((1,), (1, 1), (1, 2, 1), (1, 3, 3, 1))
+
+
+def shape_records(records):
+    """SHAPE_DTYPE records -> per record the plain tuple ShapeMeasures takes: (m (10 ints), border, perim (3), quads (3))."""
+    return [(tuple(m), b, tuple(p), tuple(q)) for m, b, p, q in zip(records["m"].tolist(), records["border"].tolist(),
+                                                                      records["perim"].tolist(), records["quads"].tolist())]
+
+
+def _not_provided(name):
+    return AttributeError("%s is not provided: the shape properties are functions of a region's integer sums (%s); not provided are %s"
+                          % (name, ", ".join(SHAPE_PROPERTIES), ", ".join(SHAPE_NOT_PROVIDED)))
+
+
+def _translated(m, dr, dc, order=3):
+    """Power sums about another origin: sum (r - dr)^p (c - dc)^q for p + q <= order from the sums m about 0, by the binomial
+    expansion; exact for int and Fraction shifts.  {(p, q): value}."""
+    out = {}
+    for p in range(order + 1):
+        for q in range(order + 1 - p):
+            total = 0
+            for i in range(p + 1):
+                for j in range(q + 1):
+                    total += _BINOM[p][i] * _BINOM[q][j] * (-dr) ** (p - i) * (-dc) ** (q - j) * m[_MOMENT_INDEX[(i, j)]]
+            out[(p, q)] = total
+    return out
+
+
+def _sqrt_fraction(x, bits=160):
+    """sqrt of a non-negative Fraction as a Fraction, to `bits` bits below one (exact when x is a rational square)."""
+    from fractions import Fraction
+    return Fraction(math.isqrt((x.numerator * x.denominator) << (2 * bits)), x.denominator << bits)
+
+
+class ShapeMeasures:
+    """The regionprops attributes that are functions of one region's integer sums (a swk_segment_shape record: m = sums of r^p c^q
+    in absolute plane coordinates, border, perim, quads) and its bbox, each computed when first read and kept.  Every value is
+    carried in exact Python integers / Fractions up to the one point where a float is formed.
+
+    PARITY UNPINNED: scikit-image is not installed where this project is built and tested; the formulas below (skimage's, in
+    row / column coordinates) are the specification.
+      moments             4x4 float64, M[p, q] = sum (r - r0)^p (c - c0)^q (bbox-local raw moments), from the absolute sums by the
+                          binomial expansion in integers.  DEVIATION: entries with p + q > 3 are nan (none of the derived
+                          properties reads them; they would need 128-bit sums)
+      local_centroid      (M10 / M00, M01 / M00)
+      moments_central     mu[p, q] about the centroid, formed as exact rationals (mu20 = (m20 m00 - m10^2) / m00, ...) and rounded
+                          once; nan for p + q > 3.  exact_central gives the rationals
+      moments_normalized  nu[p, q] = mu[p, q] / mu00^((p + q) / 2 + 1) for p + q >= 2, nan below (and above 3)
+      moments_hu          the seven invariants of nu
+      inertia_tensor      [[mu02, -mu11], [-mu11, mu20]] / mu00
+      inertia_tensor_eigvals  descending, clipped at 0: (T +- sqrt(D)) / 2 of the exact tensor, T its trace, D = (a - c)^2 + 4 b^2,
+                          the square root taken to 160 bits and the value rounded once
+      major_axis_length, minor_axis_length  4 sqrt(l1), 4 sqrt(l2)
+      eccentricity        sqrt(1 - l2 / l1), 0 when l1 == 0
+      orientation         with a, b, b, c = inertia_tensor.flat: 0.5 atan2(-2 b, c - a); when a == c, -pi / 4 for b < 0 and pi / 4
+                          otherwise.  a == c is decided and -2 b and c - a are formed on the exact tensor
+      bbox_area, extent   extent = area / bbox_area
+      equivalent_diameter sqrt(4 area / pi)
+      perimeter           perim[0] + perim[1] sqrt(2) + perim[2] (1 + sqrt(2)) / 2 (skimage.measure.perimeter(image, 4) of 0.15.0)
+      euler_number        (quads[0] - quads[1] - 2 quads[2]) / 4, the 8-connected Euler number.  DEVIATION: skimage 0.15 counts holes
+                          with an 8-neighbourhood; the two differ only where two holes touch diagonally
+    Not provided (reading one raises AttributeError): SHAPE_NOT_PROVIDED."""
+
+    def __init__(self, bbox, record):
+        self.bbox = tuple(int(x) for x in bbox)
+        m, border, perim, quads = record
+        self.m, self.border, self.perim, self.quads = tuple(int(x) for x in m), int(border), tuple(perim), tuple(quads)
+        self.area = self.m[0]
+        self._cache = {}
+
+    def __getattr__(self, name):
+        if name in SHAPE_PROPERTIES or name in ("exact_central", "exact_tensor"):
+            cache = self.__dict__["_cache"]
+            if name not in cache:
+                cache[name] = getattr(self, "_" + name)()
+            return cache[name]
+        if name in SHAPE_NOT_PROVIDED:
+            raise _not_provided(name)
+        raise AttributeError(name)
+
+    @staticmethod
+    def _matrix(values):
+        out = np.full((4, 4), np.nan)
+        for (p, q), v in values.items():
+            out[p, q] = v if isinstance(v, float) else v.numerator / v.denominator
+        return out
+
+    def _moments(self):
+        return self._matrix(_translated(self.m, self.bbox[0], self.bbox[1]))
+
+    def _local_centroid(self):
+        M = _translated(self.m, self.bbox[0], self.bbox[1], 1)
+        return (M[(1, 0)] / M[(0, 0)], M[(0, 1)] / M[(0, 0)])
+
+    def _exact_central(self):
+        """{(p, q): Fraction} for p + q <= 3"""
+        from fractions import Fraction
+        # in integers: with N = m00, sum (N r - m10)^p (N c - m01)^q = N^(p + q) mu[p, q], and the sums of (N r)^i (N c)^j are N^(i + j) m[i, j]
+        n = self.m[0]
+        scaled = [v * n ** (i + j) for (i, j), v in zip(_lib.SHAPE_MOMENT_ORDER, self.m)]
+        return {pq: Fraction(v, n ** (pq[0] + pq[1])) for pq, v in _translated(scaled, self.m[1], self.m[2]).items()}
+
+    def _moments_central(self):
+        return self._matrix(self.exact_central)
+
+    def _moments_normalized(self):
+        mu = self.moments_central
+        nu = np.full((4, 4), np.nan)
+        for p in range(4):
+            for q in range(4 - p):
+                if p + q >= 2:
+                    nu[p, q] = mu[p, q] / mu[0, 0] ** ((p + q) / 2 + 1)
+        return nu
+
+    def _moments_hu(self):
+        nu = self.moments_normalized
+        n20, n02, n11, n30, n03, n21, n12 = nu[2, 0], nu[0, 2], nu[1, 1], nu[3, 0], nu[0, 3], nu[2, 1], nu[1, 2]
+        t0, t1 = n30 + n12, n21 + n03
+        q0, q1 = t0 * t0, t1 * t1
+        n4 = 4 * n11
+        s, d = n20 + n02, n20 - n02
+        hu = np.zeros(7)
+        hu[0] = s
+        hu[1] = d * d + n4 * n11
+        hu[3] = q0 + q1
+        hu[5] = d * (q0 - q1) + n4 * t0 * t1
+        t0, t1 = t0 * (q0 - 3 * q1), t1 * (3 * q0 - q1)
+        q0, q1 = n30 - 3 * n12, 3 * n21 - n03
+        hu[2] = q0 * q0 + q1 * q1
+        hu[4] = q0 * t0 + q1 * t1
+        hu[6] = q1 * t0 - q0 * t1
+        return hu
+
+    def _exact_tensor(self):
+        """(a, b, c) of [[a, b], [b, c]] as Fractions"""
+        mu = self.exact_central
+        n = mu[(0, 0)]
+        return mu[(0, 2)] / n, -mu[(1, 1)] / n, mu[(2, 0)] / n
+
+    def _inertia_tensor(self):
+        a, b, c = (x.numerator / x.denominator for x in self.exact_tensor)
+        return np.array([[a, b], [b, c]])
+
+    def _inertia_tensor_eigvals(self):
+        a, b, c = self.exact_tensor
+        root = _sqrt_fraction((a - c) ** 2 + 4 * b * b)
+        l1, l2 = (a + c + root) / 2, (a + c - root) / 2
+        return [max(l1.numerator / l1.denominator, 0.0), max(l2.numerator / l2.denominator, 0.0)]
+
+    def _major_axis_length(self):
+        return 4 * math.sqrt(self.inertia_tensor_eigvals[0])
+
+    def _minor_axis_length(self):
+        return 4 * math.sqrt(self.inertia_tensor_eigvals[1])
+
+    def _eccentricity(self):
+        l1, l2 = self.inertia_tensor_eigvals
+        return 0.0 if l1 == 0 else math.sqrt(1 - l2 / l1)
+
+    def _orientation(self):
+        a, b, c = self.exact_tensor
+        if a == c:
+            return -math.pi / 4 if b < 0 else math.pi / 4
+        y, x = -2 * b, c - a
+        return 0.5 * math.atan2(y.numerator / y.denominator, x.numerator / x.denominator)
+
+    def _bbox_area(self):
+        r0, c0, r1, c1 = self.bbox
+        return (r1 - r0) * (c1 - c0)
+
+    def _extent(self):
+        return self.area / self.bbox_area
+
+    def _equivalent_diameter(self):
+        return math.sqrt(4 * self.area / math.pi)
+
+    def _perimeter(self):
+        p = self.perim
+        return p[0] + p[1] * math.sqrt(2) + p[2] * ((1 + math.sqrt(2)) / 2)
+
+    def _euler_number(self):
+        q = self.quads
+        return (q[0] - q[1] - 2 * q[2]) // 4
+
+
+class ShapeRegionProps(RegionProps):
+    """RegionProps that also answers the shape properties (SHAPE_PROPERTIES) from its ShapeMeasures, each made on first read."""
+    __slots__ = ("shape",)
+
+    def __init__(self, label, bbox, centroid, area, shape):
+        RegionProps.__init__(self, label, bbox, centroid, area)
+        self.shape = shape
+
+    def __getattr__(self, name):
+        if name in SHAPE_PROPERTIES:
+            return getattr(self.shape, name)
+        if name in SHAPE_NOT_PROVIDED:
+            raise _not_provided(name)
+        raise AttributeError(name)
 
 
 def segment_crop_box(bbox, frame_shape, min_seg_size, crop_region):

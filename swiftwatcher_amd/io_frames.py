@@ -73,10 +73,12 @@ class PresegmentingReader:
     identical (windows are independent).  Needs to know what segment_queue will be asked: crop_region, min_seg_size, queue_size (a ROI
     stream carries the first two in its header).  The stage images of such a window are produced only if somebody reads them."""
 
-    def __init__(self, reader, crop_region=None, queue_size=21, windows=8, min_seg_size=None, device=0, params=None, classifier=None):
+    def __init__(self, reader, crop_region=None, queue_size=21, windows=8, min_seg_size=None, device=0, params=None, classifier=None,
+                 shape_props=False):
         import collections
         import weakref
         self.reader = reader
+        self.shape_props = bool(shape_props)         # the prepared segments carry shape records (a FrameQueue(shape_props=True) takes no others)
         self.crop_region = crop_region if crop_region is not None else reader.crop_region
         self.min_seg_size = tuple(min_seg_size if min_seg_size is not None else getattr(reader, "min_seg_size", (24, 24)))
         self.queue_size, self.windows, self.device, self.params = int(queue_size), max(int(windows), 1), device, params
@@ -124,11 +126,12 @@ class PresegmentingReader:
             if triples:
                 hint = self._classifier_hint() if self._classifier_hint is not None else None
                 info = {}
+                shape = {"shape_props": True} if self.shape_props else {}
                 popped = ds.segment_windows(triples, self.crop_region, self.min_seg_size, device=self.device, params=self.params,
-                                            classifier=hint, owner=self, info=info)
+                                            classifier=hint, owner=self, info=info, **shape)
                 for (frames, numbers, stamps), snap, frs, iters in zip(triples, snaps, popped, info["iters"]):
                     ds.PRESEGMENTED[id(frames[0])] = ds.Presegmented(list(frames), [f.segments for f in frs], self.crop_region,
-                                                                       self.min_seg_size, self.params, iters, self.device)
+                                                                       self.min_seg_size, self.params, iters, self.device, **shape)
                     out.append((frames, numbers, stamps, snap))
             done.result = out
         except BaseException as exc:                  # surfaces in get_n_frames

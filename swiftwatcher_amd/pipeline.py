@@ -13,7 +13,7 @@ from . import image_filtering as img
 
 def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size=21, classifier=None, min_seg_size=(24, 24),
                              device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None,
-                             track_by_window=True, review=None, review_text=False, review_stages=()):
+                             track_by_window=True, review=None, review_text=False, review_stages=(), shape_props=False):
     """Same call order as __main__.py:62-100.  corners = ((x1, y1), (x2, y2)) of the chimney's top edge: crop region
     and ROI mask are then generated from the video's first frame (:62-63) instead of being passed in.  Returns the tracker's detected events (lists of Segment objects,
     the structure the reference hands to event classification).  windows_per_call > 1 reads that many queue-fuls
@@ -27,7 +27,10 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     events are the same with and without it.  review_text: a writer made here from a path also writes the status line and the event
     numbers (ReviewWriter's text=True); a ReviewWriter handed in carries its own setting.  review_stages: names of stage images
     (rpca, thresh, labels, ...: ReviewWriter's stages=) that a writer made here from a path shows as panels beside every frame; the
-    segment path then keeps those images on the GPU, where the writer reads them."""
+    segment path then keeps those images on the GPU, where the writer reads them.  shape_props: every segment (those of the returned
+    events among them) also answers the shape properties of image_filtering.ShapeMeasures -- orientation, eccentricity, axis lengths,
+    perimeter, moments, ... -- from one more GPU call per window over its label planes; counts and events are the same with and
+    without it, and without it nothing is different (no extra call, no label planes)."""
     if corners is not None:
         first_frame = reader.read_frame(0, increment=False)                        # :62
         crop_region, roi_mask, _ = img.generate_regions(first_frame, corners)      # :63
@@ -43,18 +46,22 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
                                            stages=review_stages)
     try:
         return _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_seg_size, device, keep_stages, windows_per_call,
-                              export_dir, params, track_by_window, tracker, review)
+                              export_dir, params, track_by_window, tracker, review, shape_props)
     finally:
         if own_review is not None:
             own_review.close()
 
 
 def _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_seg_size, device, keep_stages, windows_per_call, export_dir,
-                   params, track_by_window, tracker, review):
+                   params, track_by_window, tracker, review, shape_props=False):
     """swift_counting_algorithm once the regions, the tracker and the review writer exist."""
     seen = 0                                         # events already handed to the review
     stages = _review_stages([review])                # the stage images the review shows: kept on the GPU by the segment path
     keep = {"stages": stages} if stages else {}      # (without them the segmenters are called as they always were)
+    if shape_props:
+        keep["shape_props"] = True
+        if hasattr(reader, "shape_props"):           # a reader that segments ahead (io_frames.PresegmentingReader): its windows carry the records
+            reader.shape_props = True
     if classifier is not None and getattr(reader, "_classifier_hint", False) is None:
         import weakref
         reader._classifier_hint = weakref.ref(classifier)          # a reader that segments ahead scores every batch for this classifier
@@ -104,7 +111,8 @@ def _counting_loop(reader, crop_region, roi_mask, queue_size, classifier, min_se
                     seen = len(tracker.detected_events)
         worker.join()
         return tracker.detected_events
-    queue = FrameQueue(queue_size, device=device, params=params, keep_stages=keep_stages or bool(stages))
+    queue = FrameQueue(queue_size, device=device, params=params, keep_stages=keep_stages or bool(stages),
+                       **({"shape_props": True} if shape_props else {}))
     while queue.frames_processed < reader.total_frames:
         frames, numbers, stamps = reader.get_n_frames(n=queue.maxlen)          # :73 (pads with null frames)
         queue.push_list_of_frames(frames, numbers, stamps)                     # :74
@@ -155,7 +163,8 @@ def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None,
     YUV4MPEG2 stream of unknown length -- "-" (standard input), a FIFO's path, a file descriptor, a binary file object (a pipe from a
     decoder: proc.stdout).  Regions either explicit or from corners=...; params, review (a path or a
     review.ReviewWriter: the review video of the count), review_text (text in a review made from a path) and review_stages (stage
-    images as panels in it) as in swift_counting_algorithm."""
+    images as panels in it) as in swift_counting_algorithm; so is shape_props=True (among **kw): the events' segments then carry the
+    shape properties."""
     opened = None
     if _is_video_source(frames):
         from .io_y4m import open_y4m
@@ -242,7 +251,7 @@ def schedule_videos(readers, sizes, segment, consume, in_flight=4, windows_per_c
 
 def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows_per_call=1, classifier=None, queue_size=21,
                         min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True, reviews=None,
-                        review_text=False, review_stages=()):
+                        review_text=False, review_stages=(), shape_props=False):
     """count_swifts over a list of videos (the reference's loop over its video list, __main__.py:21), several videos at a time on one
     GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
     windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
@@ -253,21 +262,22 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
     (crop_region, roi_mask), or corners: per video the chimney's top edge (the regions then come from its first frame, :62-63).
     reviews: per video a path, a review.ReviewWriter or None -- that video's review video (swift_counting_algorithm's review=);
     review_text: the writers made here from paths also write text (its review_text=); review_stages: and show these stage images as
-    panels (its review_stages=).
+    panels (its review_stages=).  shape_props: as swift_counting_algorithm's; one shape call per group of a GPU call, since the
+    groups' geometries differ.
     Returns [(count, events), ...] in input order."""
     from .io_y4m import open_y4m
     readers = [open_y4m(v) if _is_video_source(v) else v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
     opened = [r for r, v in zip(readers, videos) if r is not v and hasattr(r, "close")]          # (closed again when the count is done)
     try:
         return _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device,
-                             pad_factor, params, track_by_window, reviews, review_text, review_stages)
+                             pad_factor, params, track_by_window, reviews, review_text, review_stages, shape_props)
     finally:
         for r in opened:
             r.close()
 
 
 def _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device, pad_factor, params,
-                  track_by_window=True, reviews=None, review_text=False, review_stages=()):
+                  track_by_window=True, reviews=None, review_text=False, review_stages=(), shape_props=False):
     """count_swifts_videos over readers."""
     if regions is None:
         if corners is None:
@@ -300,6 +310,8 @@ def _count_videos(readers, regions, corners, in_flight, windows_per_call, classi
 
         stages = _review_stages(reviews)             # the stage images the reviews show: kept on the GPU by the segment path
         keep = {"stages": stages} if stages else {}  # (without them the segmenter is called as it always was)
+        if shape_props:
+            keep["shape_props"] = True
 
         def segment(groups):
             out = segment_window_groups([(w, regions[v][0]) for v, w in groups], min_seg_size, device=device, params=params,
