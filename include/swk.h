@@ -470,6 +470,33 @@ typedef struct swk_segment_shape {
 int32_t swk_segment_shapes_u8(swk_ctx *ctx, const uint8_t *labels, int32_t mem, int32_t count, int32_t H, int32_t W,
                               int64_t frame_stride, int64_t row_stride, int32_t seg_cap, swk_segment_shape *shapes, int32_t *nseg);
 
+/* ---- stabilization: per-frame integer shift search against an anchor image ------------------------------------
+ * No counterpart in the reference, which assumes a camera that does not move.  For each of `count` BGR frames of Hs x Ws pixels
+ * (frame f, pixel (r, c) at frames + f * frame_stride + r * row_stride + 3 c; strides in bytes, row_stride >= 3 Ws, frame_stride of
+ * either sign; mem = SWK_MEM_DEVICE: read where they lie, SWK_MEM_HOST: copied up) every integer shift (dy, dx), |dy|, |dx| <=
+ * search, whose rectangle [y0 + dy, y0 + dy + Ho) x [x0 + dx, x0 + dx + Wo) lies inside the frame is a candidate; the others are
+ * excluded (no reflected pixels).  The score of a candidate is the sum over the rectangle of
+ * |anchor[r][c] - gray(frame)[y0 + dy + r][x0 + dx + c]|, gray as swk_bgr2gray's for gray_mode, bit for bit; an exact integer.
+ * The smallest score is chosen; ties go to the smallest dy^2 + dx^2, then the smallest dy, then the smallest dx.
+ * A frame whose Hs x Ws x 3 bytes are all zero (a reader's null frame) is not matched: dy = dx = 0 and sad = sad_unshifted.
+ *   anchor     [Ho][Wo] u8 grey, dense, anchor_bytes = Ho * Wo (anchor_mem: host or device)
+ *   shifts     host [count]
+ *   sad_table  optional, host [count][(2 search + 1)^2], entry (dy + search) * (2 search + 1) + dx + search; UINT64_MAX where the
+ *              candidate is excluded
+ *   out        [count][Ho][Wo][3] dense (out_mem: host or device): each frame's chosen rectangle
+ * SWK_ERR_ARG, before anything is copied or launched and with the outputs untouched: a null pointer (sad_table may be null),
+ * count < 1, a frame side outside 1..32768, search outside 0..16, a nominal rectangle that leaves the frame, anchor_bytes other
+ * than Ho * Wo, row_stride < 3 Ws, an unknown gray_mode or mem.  SWK_ERR_CAPACITY: more than 2^24 frames. */
+typedef struct swk_shift {
+    int32_t dy, dx;
+    uint64_t sad;             /* the chosen candidate's score */
+    uint64_t sad_unshifted;   /* the score of (0, 0) */
+} swk_shift;
+int32_t swk_stabilize_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32_t count, int32_t Hs, int32_t Ws, int64_t frame_stride,
+                         int64_t row_stride, int32_t y0, int32_t x0, int32_t Ho, int32_t Wo, int32_t search, const uint8_t *anchor,
+                         int32_t anchor_mem, int64_t anchor_bytes, int32_t gray_mode, swk_shift *shifts, uint64_t *sad_table,
+                         uint8_t *out, int32_t out_mem);
+
 /* ---- classifier input (segment_classification.py:18-24) -------------------------------------------------
  * ToPILImage -> Resize((24,24)) (Pillow's antialiased bilinear resampling, 8-bit fixed point, restated
  * exactly) -> Pad(100) -> ToTensor -> Normalize(mean, std) for nseg segment crops.

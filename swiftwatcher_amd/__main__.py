@@ -1,6 +1,6 @@
 """python -m swiftwatcher_amd SOURCE [SOURCE ...] (--corners X1,Y1,X2,Y2 | --attributes FILE) [--start N] [--end N]
        [--classify WEIGHTS] [--out DIR] [--shape-props] [--review PATH [--review-text] [--review-stages LIST]] [--windows-per-call K]
-       [--device D]
+       [--stabilize [S]] [--device D]
 
 The reference's main() (__main__.py:13-53) without its UI: every SOURCE -- a .y4m file, or "-" for a YUV4MPEG2 stream on standard
 input (`ffmpeg -i evening.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners 812,640,1105,642`) -- is counted by
@@ -15,7 +15,11 @@ JSON lines.  --review-text (with --review only) writes the tables' keys into eve
 every event shown, k its row in the events table.  --review-stages rpca,thresh,labels (with --review only; combines with
 --review-text) puts those stage images of every frame beside it as captioned panels: keys gray rpca bilateral thresh opened labels.
 --shape-props measures every segment's shape on the GPU (pipeline.count_swifts' shape_props=True) and, with --out DIR, also writes
-DIR/segments_shape.csv: one row per segment of every event (SHAPE_CSV_COLUMNS)."""
+DIR/segments_shape.csv: one row per segment of every event (SHAPE_CSV_COLUMNS).
+--stabilize [S] (S = 8 without a value, at most 16) is for shaken footage: every frame is cut at the integer shift of up to S pixels
+that matches it best to the video's first frame (stabilize.StabilizingReader) before it is segmented; with --out DIR it also writes
+DIR/stabilization.csv, one row per frame (frame_number, dy, dx, sad, sad_unshifted), and the JSON line gains
+"stabilize": {"search": S, "moved_frames": k, "max_shift": m}."""
 import argparse
 import json
 import os
@@ -58,6 +62,16 @@ def _stage_list(text):
         raise argparse.ArgumentTypeError(str(exc))
 
 
+def _search_range(text):
+    try:
+        s = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("the search range is a number of pixels (got %r)" % text)
+    if not 1 <= s <= 16:
+        raise argparse.ArgumentTypeError("the search range is 1..16 pixels (got %d)" % s)
+    return s
+
+
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m swiftwatcher_amd", description="Count chimney swifts in YUV4MPEG2 videos on the MI355X.")
     p.add_argument("sources", nargs="+", metavar="SOURCE", help="a .y4m file, or - for a YUV4MPEG2 stream on standard input")
@@ -73,6 +87,9 @@ def build_parser():
     p.add_argument("--review-text", action="store_true", help="with --review: draw frame number, time, counts and event numbers into it")
     p.add_argument("--review-stages", type=_stage_list, default=(), metavar="LIST",
                    help="with --review: stage images shown as panels beside every frame, e.g. rpca,thresh,labels")
+    p.add_argument("--stabilize", type=_search_range, nargs="?", const=8, default=0, metavar="S",
+                   help="stabilize shaken footage: search shifts of up to S pixels per frame (8 without a value); with --out also write "
+                        "stabilization.csv")
     p.add_argument("--windows-per-call", type=int, default=1, metavar="K", help="queue-fuls segmented per GPU call")
     p.add_argument("--device", type=int, default=0, metavar="D", help="GPU index")
     return p
@@ -160,10 +177,20 @@ def main(argv=None):
         if review and len(jobs) > 1:
             os.makedirs(review, exist_ok=True)
             review = os.path.join(review, stem + ".y4m")
+        counted = reader
         try:
-            count, events = pipeline.count_swifts(reader, corners=corners, classifier=classifier, device=args.device,
+            if args.stabilize:                                                     # (the regions of :62-63 here: the wrapper needs the crop region)
+                from . import image_filtering as img
+                from .stabilize import StabilizingReader
+                crop_region, roi_mask, _ = img.generate_regions(reader.read_frame(0, increment=False), corners)
+                counted = StabilizingReader(reader, crop_region, args.stabilize, device=args.device)
+                regions = dict(crop_region=crop_region, roi_mask=roi_mask)
+            else:
+                regions = dict(corners=corners)
+            count, events = pipeline.count_swifts(counted, classifier=classifier, device=args.device,
                                                   windows_per_call=args.windows_per_call, review=review or None, review_text=args.review_text,
-                                                  review_stages=args.review_stages, **({"shape_props": True} if args.shape_props else {}))
+                                                  review_stages=args.review_stages, **({"shape_props": True} if args.shape_props else {}),
+                                                  **regions)
             frames, fps, first, last = reader.total_frames, reader.fps, reader.start_frame, reader.end_frame
         except (OSError, ValueError) as exc:
             print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)
@@ -177,7 +204,15 @@ def main(argv=None):
                 export_results(out_dir, ec.classify_events(events), fps, first, last)
             if args.shape_props:
                 write_shape_csv(os.path.join(out_dir, "segments_shape.csv"), events)
-        print(json.dumps({"source": source, "frames": int(frames), "events": len(events), "count": int(count)}), flush=True)
+        line = {"source": source, "frames": int(frames), "events": len(events), "count": int(count)}
+        if args.stabilize:
+            from .stabilize import summary, write_csv
+            if args.out:                                                           # (also for a video without events: the shifts are about frames)
+                out_dir = args.out if len(jobs) == 1 else os.path.join(args.out, stem)
+                os.makedirs(out_dir, exist_ok=True)
+                write_csv(os.path.join(out_dir, "stabilization.csv"), counted.shifts)
+            line["stabilize"] = summary(counted.shifts, args.stabilize)
+        print(json.dumps(line), flush=True)
     return 0
 
 

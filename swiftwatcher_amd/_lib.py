@@ -57,6 +57,9 @@ assert SEGMENT_DTYPE.itemsize == ctypes.sizeof(Segment) == 48
 SHAPE_DTYPE = np.dtype([("label", "<i4"), ("reserved_", "<i4"), ("m", "<i8", (10,)), ("border", "<i8"), ("perim", "<i8", (3,)),
                         ("quads", "<i8", (3,))])
 assert SHAPE_DTYPE.itemsize == 144
+# swk_shift
+SHIFT_DTYPE = np.dtype([("dy", "<i4"), ("dx", "<i4"), ("sad", "<u8"), ("sad_unshifted", "<u8")])
+assert SHIFT_DTYPE.itemsize == 24
 SHAPE_MOMENT_ORDER = ((0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (3, 0), (2, 1), (1, 2), (0, 3))
 DEBUG_GUARD_BYTES, DEBUG_FILL = 64, 0xA5          # swk_debug_filter_fused (include/swk_debug.h)
 DEBUG_PLANE_DTYPE = np.dtype([("H", "<i4"), ("W", "<i4"), ("off", "<i8")])
@@ -210,6 +213,8 @@ _SIGS = {
     "swk_ccl_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_regionprops_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_segment_shapes_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_int64] * 2 + [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
+    "swk_stabilize_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_int64] * 2 + [ctypes.c_int32] * 5 +
+                         [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3 + [ctypes.c_int32]),
     "swk_classifier_input": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "swk_set_sparse_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
     "swk_set_integer_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
@@ -1203,6 +1208,63 @@ class Context:
         self.segment_shapes_raw(ptr, mem, F, H, W, fs, rs, seg_cap, shapes, nseg)
         del keep
         return (shapes[0, :nseg[0]], int(nseg[0])) if single else (shapes, nseg)
+
+    def stabilize_raw(self, ptr, mem, count, Hs, Ws, frame_stride, row_stride, y0, x0, Ho, Wo, search, anchor_ptr, anchor_mem, anchor_bytes,
+                      gray_mode, shifts, table, out_ptr, out_mem):
+        """swk_stabilize_u8 on raw pointers; shifts / table: the host arrays it fills (table may be None)."""
+        self._check(self._lib.swk_stabilize_u8(self._h, ptr, int(mem), int(count), int(Hs), int(Ws), int(frame_stride), int(row_stride),
+                                               int(y0), int(x0), int(Ho), int(Wo), int(search), anchor_ptr, int(anchor_mem),
+                                               int(anchor_bytes), int(gray_mode), _ptr(shifts), _ptr(table), out_ptr, int(out_mem)))
+
+    def stabilize(self, frames, rect, search, anchor, gray_mode=GRAY_Q14, device_out=False, table=False):
+        """swk_stabilize_u8: for every BGR frame the integer shift (|dy|, |dx| <= search, rectangles that leave the frame excluded) at
+        which the grey of its rectangle differs least, in summed absolute difference, from the anchor, and the frame's pixels there.
+        frames: uint8 (count, Hs, Ws, 3) -- a numpy array of any frame and row strides (copied up), or a torch tensor on this
+        context's GPU (read in place) --, contiguous along a pixel row.  rect = (y0, x0, Ho, Wo): the nominal rectangle.  anchor:
+        uint8 (Ho, Wo), numpy or a tensor on the GPU.  Returns (shifts: SHIFT_DTYPE records (count,), the table (count, 2 search + 1,
+        2 search + 1) uint64 indexed [f, dy + search, dx + search] with UINT64_MAX at excluded candidates, or None without
+        table=True, pixels (count, Ho, Wo, 3): a numpy array, or with device_out=True a torch uint8 tensor on the GPU)."""
+        def on_gpu(a):
+            return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
+        keep = [frames, anchor]
+        if on_gpu(frames):
+            if str(frames.dtype) != "torch.uint8" or frames.dim() != 4 or frames.shape[3] != 3 or frames.stride(3) != 1 or frames.stride(2) != 3:
+                raise ValueError("device frames are uint8 (count, Hs, Ws, 3), contiguous along a row")
+            count, Hs, Ws = (int(x) for x in frames.shape[:3])
+            fptr, fmem, fs, rs = frames.data_ptr(), MEM_DEVICE, int(frames.stride(0)), int(frames.stride(1))
+        else:
+            a = np.asarray(frames)
+            if a.dtype != np.uint8 or a.ndim != 4 or a.shape[3] != 3:
+                raise ValueError("frames are uint8 (count, Hs, Ws, 3)")
+            if a.strides[3] != 1 or a.strides[2] != 3 or a.strides[1] < 3 * a.shape[2]:
+                a = np.ascontiguousarray(a)
+            keep.append(a)
+            count, Hs, Ws = a.shape[:3]
+            fptr, fmem, fs, rs = a.ctypes.data, MEM_HOST, a.strides[0], a.strides[1]
+        if on_gpu(anchor):
+            if str(anchor.dtype) != "torch.uint8" or not anchor.is_contiguous():
+                raise ValueError("a device anchor is a contiguous uint8 tensor")
+            aptr, amem, abytes = anchor.data_ptr(), MEM_DEVICE, int(anchor.numel())
+        else:
+            an = np.ascontiguousarray(anchor, np.uint8)
+            keep.append(an)
+            aptr, amem, abytes = an.ctypes.data, MEM_HOST, an.size
+        y0, x0, Ho, Wo = (int(v) for v in rect)
+        search = int(search)
+        shape = (count, Ho, Wo, 3) if Ho > 0 and Wo > 0 and count > 0 else (1, 1, 1, 3)          # (the library refuses those)
+        if device_out:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device="cuda:%d" % self.device)
+            optr, omem = out.data_ptr(), MEM_DEVICE
+        else:
+            out = np.empty(shape, np.uint8)
+            optr, omem = out.ctypes.data, MEM_HOST
+        shifts = np.zeros(max(count, 1), SHIFT_DTYPE)
+        side = 2 * search + 1 if 0 <= search <= 16 else 1
+        tab = np.zeros((max(count, 1), side, side), np.uint64) if table else None
+        self.stabilize_raw(fptr, fmem, count, Hs, Ws, fs, rs, y0, x0, Ho, Wo, search, aptr, amem, abytes, gray_mode, shifts, tab, optr, omem)
+        del keep
+        return shifts, tab, out
 
 
 def stage_frames(frames, y0, y1, x0, x1, dst, threads=4):

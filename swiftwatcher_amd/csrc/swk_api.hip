@@ -23,7 +23,8 @@ enum Slot {
     SL_ROI = 0, SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8, SL_LAB32, SL_A, SL_Y, SL_E, SL_PN,
     SL_BM, SL_VPREV, SL_GPART, SL_ZZPART, SL_WIN, SL_ACTIVE, SL_PARENT, SL_ROOTBITS, SL_WORDPREFIX,
     SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_TMP_IN, SL_TMP_OUT, SL_TMP_AUX, SL_COLORW, SL_SPACEW,
-    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_SEGLARGE, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_REVIEW, SL_SHAPE_TAB, SL_SHAPE_REC, SL_SHAPE_NSEG, SL_COUNT
+    SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_SEGLARGE, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_REVIEW, SL_SHAPE_TAB, SL_SHAPE_REC, SL_SHAPE_NSEG,
+    SL_STAB_PLANE, SL_STAB_TAB, SL_STAB_REC, SL_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int fam; };
@@ -2084,6 +2085,56 @@ int32_t swk_segment_shapes_u8(swk_ctx *ctx, const uint8_t *labels, int32_t mem, 
     launch_segment_shapes(ctx->stream, planes, count, H, W, fs, rs, table, seg_cap, drec, dnseg);
     HIPCHK(ctx, hipMemcpyAsync(shapes, drec, rec_b, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(nseg, dnseg, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
+int32_t swk_stabilize_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32_t count, int32_t Hs, int32_t Ws, int64_t frame_stride,
+                         int64_t row_stride, int32_t y0, int32_t x0, int32_t Ho, int32_t Wo, int32_t search, const uint8_t *anchor,
+                         int32_t anchor_mem, int64_t anchor_bytes, int32_t gray_mode, swk_shift *shifts, uint64_t *sad_table, uint8_t *out,
+                         int32_t out_mem)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!frames || !anchor || !shifts || !out) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (count < 1) return fail(ctx, SWK_ERR_ARG, "count must be at least 1");
+    if (Hs < 1 || Ws < 1 || Hs > 32768 || Ws > 32768) return fail(ctx, SWK_ERR_ARG, "frame size must be 1..32768 on each side");
+    if (search < 0 || search > 16) return fail(ctx, SWK_ERR_ARG, "search must be in 0..16");
+    if (Ho < 1 || Wo < 1 || y0 < 0 || x0 < 0 || (int64_t)y0 + Ho > Hs || (int64_t)x0 + Wo > Ws)
+        return fail(ctx, SWK_ERR_ARG, "the nominal rectangle leaves the source frame");
+    if (anchor_bytes != (int64_t)Ho * Wo) return fail(ctx, SWK_ERR_ARG, "the anchor must hold Ho x Wo bytes");
+    if (row_stride < (int64_t)Ws * 3) return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
+    if (gray_mode != SWK_GRAY_Q14 && gray_mode != SWK_GRAY_Q15) return fail(ctx, SWK_ERR_ARG, "gray_mode must be SWK_GRAY_Q14 or SWK_GRAY_Q15");
+    for (int32_t m : {mem, anchor_mem, out_mem})
+        if (m != SWK_MEM_HOST && m != SWK_MEM_DEVICE) return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
+    if (count > (1 << 24)) return fail(ctx, SWK_ERR_CAPACITY, "too many frames in one call");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint8_t *src = frames, *danchor = anchor;
+    int64_t fs = frame_stride, rs = row_stride;
+    const size_t out_b = (size_t)count * Ho * Wo * 3, tab_b = stabilize_table_bytes(count, search);
+    if (mem == SWK_MEM_HOST) {
+        uint8_t *din;
+        NEED(ctx, SL_TMP_IN, (size_t)count * Hs * Ws * 3, din);
+        const int rc = upload_rects(ctx, din, frames, row_stride, frame_stride, (size_t)Ws * 3, (size_t)Hs, count);
+        if (rc) return rc;
+        src = din; rs = (int64_t)Ws * 3; fs = (int64_t)Hs * rs;
+    }
+    if (anchor_mem == SWK_MEM_HOST) {
+        uint8_t *da;
+        NEED(ctx, SL_TMP_AUX, (size_t)anchor_bytes, da);
+        HIPCHK(ctx, hipMemcpyAsync(da, anchor, (size_t)anchor_bytes, hipMemcpyHostToDevice, ctx->stream));
+        danchor = da;
+    }
+    uint8_t *dout = out, *plane, *rec;
+    void *table;
+    if (out_mem == SWK_MEM_HOST) NEED(ctx, SL_TMP_OUT, out_b, dout);
+    NEED(ctx, SL_STAB_PLANE, stabilize_plane_bytes(count, Hs, Ws), plane);
+    NEED(ctx, SL_STAB_TAB, tab_b, table);
+    NEED(ctx, SL_STAB_REC, (size_t)count * (sizeof(swk_shift) + 4), rec);          // the records, then the frames' non-zero flags
+    swk_shift *dshifts = (swk_shift *)rec;
+    launch_stabilize(ctx->stream, src, fs, rs, count, Hs, Ws, y0, x0, Ho, Wo, search, danchor, gray_mode, plane,
+                     (uint32_t *)(rec + (size_t)count * sizeof(swk_shift)), table, dshifts, dout);
+    HIPCHK(ctx, hipMemcpyAsync(shifts, dshifts, (size_t)count * sizeof(swk_shift), hipMemcpyDeviceToHost, ctx->stream));
+    if (sad_table) HIPCHK(ctx, hipMemcpyAsync(sad_table, table, tab_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(out, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
 }
 

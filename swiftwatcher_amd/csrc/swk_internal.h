@@ -255,6 +255,14 @@ size_t shape_table_bytes(int F);
 void launch_segment_shapes(hipStream_t s, const uint8_t *labels, int F, int H, int W, int64_t fs, int64_t rs, void *table, int seg_cap,
                            swk_segment_shape *shapes, int32_t *nseg);
 
+// stabilize.hip: the shift search of swk_stabilize_u8 over F device frames (frame f, pixel (r, c) at frames + f * fs + r * rs + 3 c);
+// anchor [Ho][Wo] dense; scratch: plane (stabilize_plane_bytes), nonzero [F], table (stabilize_table_bytes; what sad_table gets);
+// shifts [F] and out [F][Ho][Wo][3] on the device
+size_t stabilize_plane_bytes(int F, int Hs, int Ws);
+size_t stabilize_table_bytes(int F, int S);
+void launch_stabilize(hipStream_t s, const uint8_t *frames, int64_t fs, int64_t rs, int F, int Hs, int Ws, int y0, int x0, int Ho, int Wo,
+                      int S, const uint8_t *anchor, int gray_mode, uint8_t *plane, uint32_t *nonzero, void *table, swk_shift *shifts,
+                      uint8_t *out);
 
 // ---- several groups of windows in one call ---------------------------------------------------------------
 // swk_batch_run and swk_batch_run_groups share one driver (run_batch, swk_api.hip).  A call of one group takes the uniform
