@@ -497,7 +497,40 @@ int32_t swk_stabilize_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32
                          int32_t anchor_mem, int64_t anchor_bytes, int32_t gray_mode, swk_shift *shifts, uint64_t *sad_table,
                          uint8_t *out, int32_t out_mem);
 
-/* ---- classifier input (segment_classification.py:18-24) -------------------------------------------------
+/* ---- stabilization to a quarter pixel: swk_stabilize_u8's search, then 25 quarter-pixel candidates around its winner -------
+ * The arguments of swk_stabilize_u8; `shifts` takes swk_subshift records and there is one more optional table.  All integers.
+ * Stage 1 is swk_stabilize_u8's search bit for bit (candidates, scores, tie rule, null frames, sad_table); its winner is (dy, dx).
+ * Stage 2: the candidates are the total shifts in quarter pixels (Qy, Qx) = (4 dy + qy, 4 dx + qx), qy, qx in -2..2.  Per axis
+ * i = floor(Q / 4) and the phase p = Q mod 4 in 0..3.  The resampled value at anchor pixel (r, c) is separable with one rounding:
+ *     h[r'][c] = sum_k T[px][k] * g[r'][x0 + ix + c - 1 + k]                    k = 0..3
+ *     v[r][c]  = sum_k T[py][k] * h[y0 + iy + r - 1 + k][c]
+ *     R[r][c]  = clamp((v + 8192) >> 14, 0, 255)                                (>> of a negative value rounds down)
+ * with T Catmull-Rom in units of 1/128: T[0] = {0, 128, 0, 0}, T[1] = {-9, 111, 29, -3}, T[2] = {-8, 72, 72, -8},
+ * T[3] = {-3, 29, 111, -9} (every row sums to 128; g >= 0, so |v| <= (144 * 144 + 16 * 16) * 255 < 2^23: int32 holds it).  Phase (0, 0) reproduces the pixel.  For the
+ * score g is the grey of the source frame, swk_bgr2gray's for gray_mode.  A candidate is admissible if on an axis with phase 0 the
+ * rectangle [o + i, o + i + size) and on an axis with another phase the footprint [o + i - 1, o + i + size + 2) lies inside the
+ * frame (o = y0 or x0); the others are excluded (no reflected pixels); q = (0, 0) is always admissible.
+ * Score = sum |anchor[r][c] - R[r][c]|; the smallest is chosen, ties go to the smallest Qy^2 + Qx^2, then Qy, then Qx.  A null
+ * frame (all bytes zero) gets Q = (0, 0).
+ *   shifts     host [count]
+ *   sad_table  optional, as swk_stabilize_u8's
+ *   sub_table  optional, host [count][25], entry (qy + 2) * 5 + qx + 2; UINT64_MAX where the candidate is excluded
+ *   out        [count][Ho][Wo][3] dense: the frame's B, G and R, each resampled by the formula at the chosen (Qy, Qx); a frame
+ *              left at q = (0, 0) is byte for byte what swk_stabilize_u8 writes
+ * SWK_ERR_ARG and SWK_ERR_CAPACITY exactly as swk_stabilize_u8 (sub_table may be null). */
+typedef struct swk_subshift {
+    int32_t dy, dx;             /* stage 1's winner, pixels */
+    int32_t qy_total, qx_total; /* the chosen total shift (Qy, Qx), quarter pixels */
+    uint64_t sad;               /* the chosen candidate's score */
+    uint64_t sad_int;           /* stage 1's score: that of q = (0, 0) */
+    uint64_t sad_unshifted;     /* the score of the shift (0, 0) */
+} swk_subshift;
+int32_t swk_stabilize_subpel_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32_t count, int32_t Hs, int32_t Ws,
+                                int64_t frame_stride, int64_t row_stride, int32_t y0, int32_t x0, int32_t Ho, int32_t Wo, int32_t search,
+                                const uint8_t *anchor, int32_t anchor_mem, int64_t anchor_bytes, int32_t gray_mode, swk_subshift *shifts,
+                                uint64_t *sad_table, uint64_t *sub_table, uint8_t *out, int32_t out_mem);
+
+/* ---- classifier input(segment_classification.py:18-24) -------------------------------------------------
  * ToPILImage -> Resize((24,24)) (Pillow's antialiased bilinear resampling, 8-bit fixed point, restated
  * exactly) -> Pad(100) -> ToTensor -> Normalize(mean, std) for nseg segment crops.
  *   crops    packed uint8 H x W x 3 images (host), crop i at byte offsets[i] with hw[2i] rows, hw[2i+1] columns

@@ -1,6 +1,6 @@
 """python -m swiftwatcher_amd SOURCE [SOURCE ...] (--corners X1,Y1,X2,Y2 | --attributes FILE) [--start N] [--end N]
        [--classify WEIGHTS] [--out DIR] [--shape-props] [--review PATH [--review-text] [--review-stages LIST]] [--windows-per-call K]
-       [--stabilize [S]] [--device D]
+       [--stabilize [S] [--stabilize-subpel]] [--device D]
 
 The reference's main() (__main__.py:13-53) without its UI: every SOURCE -- a .y4m file, or "-" for a YUV4MPEG2 stream on standard
 input (`ffmpeg -i evening.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners 812,640,1105,642`) -- is counted by
@@ -19,7 +19,10 @@ DIR/segments_shape.csv: one row per segment of every event (SHAPE_CSV_COLUMNS).
 --stabilize [S] (S = 8 without a value, at most 16) is for shaken footage: every frame is cut at the integer shift of up to S pixels
 that matches it best to the video's first frame (stabilize.StabilizingReader) before it is segmented; with --out DIR it also writes
 DIR/stabilization.csv, one row per frame (frame_number, dy, dx, sad, sad_unshifted), and the JSON line gains
-"stabilize": {"search": S, "moved_frames": k, "max_shift": m}."""
+"stabilize": {"search": S, "moved_frames": k, "max_shift": m}.
+--stabilize-subpel (with --stabilize) adds the quarter-pixel stage: every frame is resampled at the best of the 25 quarter-pixel
+shifts around the integer one.  stabilization.csv then has three more columns -- shift_y, shift_x: the total shift in pixels with
+two decimal places (-1.25), and sad_subpel -- and the "stabilize" object gains "subpel": true and "fractional_frames": k."""
 import argparse
 import json
 import os
@@ -90,6 +93,8 @@ def build_parser():
     p.add_argument("--stabilize", type=_search_range, nargs="?", const=8, default=0, metavar="S",
                    help="stabilize shaken footage: search shifts of up to S pixels per frame (8 without a value); with --out also write "
                         "stabilization.csv")
+    p.add_argument("--stabilize-subpel", action="store_true",
+                   help="with --stabilize: refine every frame's shift to a quarter pixel and resample it there")
     p.add_argument("--windows-per-call", type=int, default=1, metavar="K", help="queue-fuls segmented per GPU call")
     p.add_argument("--device", type=int, default=0, metavar="D", help="GPU index")
     return p
@@ -107,6 +112,8 @@ def plan(argv):
         parser.error("--review-text needs --review PATH")
     if args.review_stages and not args.review:
         parser.error("--review-stages needs --review PATH")
+    if args.stabilize_subpel and not args.stabilize:
+        parser.error("--stabilize-subpel needs --stabilize")
     shared = None
     try:
         if args.corners is not None:
@@ -183,7 +190,8 @@ def main(argv=None):
                 from . import image_filtering as img
                 from .stabilize import StabilizingReader
                 crop_region, roi_mask, _ = img.generate_regions(reader.read_frame(0, increment=False), corners)
-                counted = StabilizingReader(reader, crop_region, args.stabilize, device=args.device)
+                counted = StabilizingReader(reader, crop_region, args.stabilize, device=args.device,
+                                            **({"subpel": True} if args.stabilize_subpel else {}))
                 regions = dict(crop_region=crop_region, roi_mask=roi_mask)
             else:
                 regions = dict(corners=corners)
@@ -207,11 +215,12 @@ def main(argv=None):
         line = {"source": source, "frames": int(frames), "events": len(events), "count": int(count)}
         if args.stabilize:
             from .stabilize import summary, write_csv
+            sub = (counted.subshifts,) if args.stabilize_subpel else ()
             if args.out:                                                           # (also for a video without events: the shifts are about frames)
                 out_dir = args.out if len(jobs) == 1 else os.path.join(args.out, stem)
                 os.makedirs(out_dir, exist_ok=True)
-                write_csv(os.path.join(out_dir, "stabilization.csv"), counted.shifts)
-            line["stabilize"] = summary(counted.shifts, args.stabilize)
+                write_csv(os.path.join(out_dir, "stabilization.csv"), counted.shifts, *sub)
+            line["stabilize"] = summary(counted.shifts, args.stabilize, *sub)
         print(json.dumps(line), flush=True)
     return 0
 

@@ -60,6 +60,10 @@ assert SHAPE_DTYPE.itemsize == 144
 # swk_shift
 SHIFT_DTYPE = np.dtype([("dy", "<i4"), ("dx", "<i4"), ("sad", "<u8"), ("sad_unshifted", "<u8")])
 assert SHIFT_DTYPE.itemsize == 24
+SUBSHIFT_DTYPE = np.dtype([("dy", "<i4"), ("dx", "<i4"), ("qy_total", "<i4"), ("qx_total", "<i4"), ("sad", "<u8"), ("sad_int", "<u8"),
+                           ("sad_unshifted", "<u8")])          # swk_subshift
+assert SUBSHIFT_DTYPE.itemsize == 40
+STABILIZE_SUBPEL_TILE = (32, 64)          # kSubRows, kSubCols of csrc/stabilize.hip: the anchor tile of a workgroup of the quarter-pixel score kernel
 SHAPE_MOMENT_ORDER = ((0, 0), (1, 0), (0, 1), (2, 0), (1, 1), (0, 2), (3, 0), (2, 1), (1, 2), (0, 3))
 DEBUG_GUARD_BYTES, DEBUG_FILL = 64, 0xA5          # swk_debug_filter_fused (include/swk_debug.h)
 DEBUG_PLANE_DTYPE = np.dtype([("H", "<i4"), ("W", "<i4"), ("off", "<i8")])
@@ -215,6 +219,8 @@ _SIGS = {
     "swk_segment_shapes_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_int64] * 2 + [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_stabilize_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_int64] * 2 + [ctypes.c_int32] * 5 +
                          [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3 + [ctypes.c_int32]),
+    "swk_stabilize_subpel_u8": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 4 + [ctypes.c_int64] * 2 + [ctypes.c_int32] * 5 +
+                                [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 4 + [ctypes.c_int32]),
     "swk_classifier_input": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32]),
     "swk_set_sparse_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
     "swk_set_integer_start": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
@@ -1224,6 +1230,37 @@ class Context:
         uint8 (Ho, Wo), numpy or a tensor on the GPU.  Returns (shifts: SHIFT_DTYPE records (count,), the table (count, 2 search + 1,
         2 search + 1) uint64 indexed [f, dy + search, dx + search] with UINT64_MAX at excluded candidates, or None without
         table=True, pixels (count, Ho, Wo, 3): a numpy array, or with device_out=True a torch uint8 tensor on the GPU)."""
+        a = self._stabilize_args(frames, rect, search, anchor, device_out)
+        shifts = np.zeros(max(a["count"], 1), SHIFT_DTYPE)
+        tab = np.zeros((max(a["count"], 1), a["side"], a["side"]), np.uint64) if table else None
+        self.stabilize_raw(*a["source"], *a["rect"], a["search"], *a["anchor"], gray_mode, shifts, tab, *a["out_ptr"])
+        return shifts, tab, a["out"]
+
+    def stabilize_subpel_raw(self, ptr, mem, count, Hs, Ws, frame_stride, row_stride, y0, x0, Ho, Wo, search, anchor_ptr, anchor_mem,
+                             anchor_bytes, gray_mode, shifts, table, sub_table, out_ptr, out_mem):
+        """swk_stabilize_subpel_u8 on raw pointers; shifts (SUBSHIFT_DTYPE) / table / sub_table: the host arrays it fills (the tables
+        may be None)."""
+        self._check(self._lib.swk_stabilize_subpel_u8(self._h, ptr, int(mem), int(count), int(Hs), int(Ws), int(frame_stride),
+                                                      int(row_stride), int(y0), int(x0), int(Ho), int(Wo), int(search), anchor_ptr,
+                                                      int(anchor_mem), int(anchor_bytes), int(gray_mode), _ptr(shifts), _ptr(table),
+                                                      _ptr(sub_table), out_ptr, int(out_mem)))
+
+    def stabilize_subpel(self, frames, rect, search, anchor, gray_mode=GRAY_Q14, device_out=False, table=False):
+        """swk_stabilize_subpel_u8: stabilize()'s integer search, then the 25 quarter-pixel shifts around its winner, each scored on
+        the grey resampled with the 4-tap Catmull-Rom filter (include/swk.h), and the frame's B, G and R resampled at the chosen one.
+        Arguments as stabilize().  Returns (shifts: SUBSHIFT_DTYPE records (count,) -- dy, dx of the integer stage, qy_total and
+        qx_total in quarter pixels --, None or with table=True the pair (stage 1's table as stabilize()'s, the quarter-pixel table
+        (count, 5, 5) uint64 indexed [f, qy + 2, qx + 2], UINT64_MAX at excluded candidates), pixels as stabilize()'s)."""
+        a = self._stabilize_args(frames, rect, search, anchor, device_out)
+        shifts = np.zeros(max(a["count"], 1), SUBSHIFT_DTYPE)
+        tab = np.zeros((max(a["count"], 1), a["side"], a["side"]), np.uint64) if table else None
+        sub = np.zeros((max(a["count"], 1), 5, 5), np.uint64) if table else None
+        self.stabilize_subpel_raw(*a["source"], *a["rect"], a["search"], *a["anchor"], gray_mode, shifts, tab, sub, *a["out_ptr"])
+        return shifts, ((tab, sub) if table else None), a["out"]
+
+    def _stabilize_args(self, frames, rect, search, anchor, device_out):
+        """What stabilize and stabilize_subpel pass on: source = (ptr, mem, count, Hs, Ws, frame stride, row stride), rect, search,
+        anchor = (ptr, mem, bytes), out and out_ptr = (ptr, mem), side of the integer table; keep: what must outlive the call."""
         def on_gpu(a):
             return hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)
         keep = [frames, anchor]
@@ -1259,12 +1296,8 @@ class Context:
         else:
             out = np.empty(shape, np.uint8)
             optr, omem = out.ctypes.data, MEM_HOST
-        shifts = np.zeros(max(count, 1), SHIFT_DTYPE)
-        side = 2 * search + 1 if 0 <= search <= 16 else 1
-        tab = np.zeros((max(count, 1), side, side), np.uint64) if table else None
-        self.stabilize_raw(fptr, fmem, count, Hs, Ws, fs, rs, y0, x0, Ho, Wo, search, aptr, amem, abytes, gray_mode, shifts, tab, optr, omem)
-        del keep
-        return shifts, tab, out
+        return dict(source=(fptr, fmem, count, Hs, Ws, fs, rs), rect=(y0, x0, Ho, Wo), search=search, anchor=(aptr, amem, abytes),
+                    out=out, out_ptr=(optr, omem), count=count, side=2 * search + 1 if 0 <= search <= 16 else 1, keep=keep)
 
 
 def stage_frames(frames, y0, y1, x0, x1, dst, threads=4):

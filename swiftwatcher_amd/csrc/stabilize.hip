@@ -16,6 +16,29 @@
 //                  (13 mod 32) puts the three or four rows the 32 lanes of a ds_read_b32 group touch on disjoint banks.
 //   k_stab_pick    one workgroup per frame: the minimum by the rule above, the record, UINT64_MAX into the excluded table entries.
 //   k_stab_copy    the chosen rectangle's BGR bytes, four per thread.
+//
+// The quarter-pixel stage (swk_stabilize_subpel_u8) runs after k_stab_gray, k_stab_sad and k_stab_pick, which it leaves as they are:
+// the 25 total shifts (4 dy + qy, 4 dx + qx), qy, qx = -2..2, around stage 1's winner, each scored by the summed absolute difference
+// between the anchor and the grey plane resampled with the 4-tap Catmull-Rom filter in units of 1/128 (one rounding, exact integers).
+//   k_stab_sub_sad   workgroup = (frame, tile of kSubRows anchor rows x kSubCols columns); it reads its frame's stage-1 record.  The
+//                    anchor tile and the grey tile at the winner's offset with a halo of 2 pixels on every side sit in LDS (floor(Q / 4)
+//                    is d - 1 or d and the taps are -1..+2: rows and columns d - 2 .. d + 2 of a pixel).  A thread owns one column and
+//                    kSubRowsPerThread rows of it and keeps the 25 sums in registers: walking down, it filters one new grey row
+//                    horizontally for the five qx (five bytes, 16 multiply-adds without the zero taps) into a window of five such rows
+//                    that lives in registers, and combines the window vertically for the five qy (25 x 4 multiply-adds), so a row
+//                    is filtered once for the five vertical offsets it serves.  q = -2, -1 read rows d - 2 .. d + 1 at phases 2, 3,
+//                    q = 0, 1, 2 rows d - 1 .. d + 2 at phases 0, 1, 2: one 5 x 5 weight matrix, constant after unrolling.  Pixels
+//                    outside the anchor are skipped by predicate and the tile's grey outside the plane is staged as zero (only taps of
+//                    weight zero or of excluded candidates meet it).  Sums: DPP/shuffle within a wave, LDS across the four waves, then one
+//                    64-bit atomic add per admissible candidate and workgroup.
+//                    LDS: 32 x 64 B anchor + 36 rows x 19 dwords grey + 25 sums = 4.9 KB (4,884 B); 125 VGPRs as compiled (25 sums,
+//                    25 window values, the grey bytes and filtered values of the unrolled steps in flight): 4 waves per SIMD by
+//                    registers, so 4 workgroups of 4 waves per CU, registers and not LDS (32 workgroups' worth) being the limit.
+//   k_stab_sub_pick  one wave per frame: UINT64_MAX into the excluded entries, the minimum by (score, Qy^2 + Qx^2, Qy, Qx), the record;
+//                    a null frame keeps Q = (0, 0).
+//   k_stab_resample  in k_stab_copy's place: four output bytes per thread, every byte the 16-tap sum of its channel at the chosen
+//                    phases (taps of weight zero are not read, so a phase-0 axis touches no pixel outside the rectangle); at phase
+//                    (0, 0), which includes every null frame, it is k_stab_copy's copy.
 #include "swk_internal.h"
 
 namespace swk {
@@ -209,6 +232,246 @@ void launch_stabilize(hipStream_t s, const uint8_t *frames, int64_t fs, int64_t 
                            shifts + f0);
         note_launch();
         hipLaunchKernelGGL(k_stab_copy, dim3((cq + 255) / 256, fc), dim3(256), 0, s, fp, fs, rs, y0, x0, Ho, Wo, shifts + f0,
+                           out + (int64_t)f0 * Ho * Wo * 3);
+        note_launch();
+    }
+}
+
+// ---- the quarter-pixel stage ------------------------------------------------------------------------------------------------------
+constexpr int kSubRows = 32, kSubCols = 64, kSubThreads = 256;
+constexpr int kSubRowsPerThread = kSubRows / (kSubThreads / kSubCols);          // 8
+constexpr int kSubHalo = 2;
+constexpr int kSubGreyRows = kSubRows + 2 * kSubHalo;                            // 36
+constexpr int kSubGreyDw = 19;                                                   // 3 bytes of alignment + 64 + 4 of halo = 71 bytes
+static_assert(kSubGreyDw * 4 >= 3 + kSubCols + 2 * kSubHalo, "grey tile too narrow");
+static_assert(kSubCols == 64 && kSubThreads == 4 * kSubCols, "a wave takes a band of rows, a lane a column");
+
+// Catmull-Rom at phase p / 4, units of 1/128
+__device__ __constant__ int kSubTap[4][4] = {{0, 128, 0, 0}, {-9, 111, 29, -3}, {-8, 72, 72, -8}, {-3, 29, 111, -9}};
+
+// The weight of sample d - 2 + w (w = 0..4) for the candidate q = j - 2: q < 0 is phase q + 4 at floor(Q / 4) = d - 1 (samples
+// d - 2 .. d + 1), q >= 0 phase q at d (samples d - 1 .. d + 2).
+__device__ __forceinline__ constexpr int sub_weight(int j, int w)
+{
+    constexpr int T[4][4] = {{0, 128, 0, 0}, {-9, 111, 29, -3}, {-8, 72, 72, -8}, {-3, 29, 111, -9}};
+    const int q = j - 2, p = q < 0 ? q + 4 : q, k = q < 0 ? w : w - 1;
+    return k < 0 || k > 3 ? 0 : T[p][k];
+}
+
+// one axis of a candidate's admissibility: o = y0 or x0, size = Ho or Wo, lim = Hs or Ws, Q the total shift in quarter pixels
+__device__ __forceinline__ bool sub_axis_inside(int o, int size, int lim, int Q)
+{
+    const int i = Q >> 2;                                                         // floor
+    return (Q & 3) ? (o + i - 1 >= 0 && o + i + size + 2 <= lim) : (o + i >= 0 && o + i + size <= lim);
+}
+
+// sub [F][25], zero before the launch; shifts: stage 1's records
+__global__ __launch_bounds__(kSubThreads) void k_stab_sub_sad(const uint8_t *__restrict__ anchor, const uint8_t *__restrict__ plane, int Hs,
+                                                              int Ws, int pitch, int y0, int x0, int Ho, int Wo,
+                                                              const swk_shift *__restrict__ shifts, u64 *__restrict__ sub)
+{
+    __shared__ uint32_t s_a[kSubRows][kSubCols / 4];
+    __shared__ uint32_t s_g[kSubGreyRows][kSubGreyDw];
+    __shared__ uint32_t s_sum[25];
+    const int t = threadIdx.x, f = blockIdx.z;
+    const int r0 = blockIdx.y * kSubRows, c0 = blockIdx.x * kSubCols;
+    const int nr = Ho - r0 < kSubRows ? Ho - r0 : kSubRows;
+    const int nc = Wo - c0 < kSubCols ? Wo - c0 : kSubCols;
+    const int dy = shifts[f].dy, dx = shifts[f].dx;
+    if (t < 25) s_sum[t] = 0;
+    // ---- anchor tile: bytes outside the anchor are zero (and skipped below) ----
+    for (int i = t; i < kSubRows * (kSubCols / 4); i += kSubThreads) {
+        const int lr = i / (kSubCols / 4), lw = i - lr * (kSubCols / 4);
+        uint32_t word = 0;
+        if (lr < nr) {
+            const uint8_t *row = anchor + (int64_t)(r0 + lr) * Wo + c0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (4 * lw + k < nc) word |= (uint32_t)row[4 * lw + k] << (8 * k);
+        }
+        s_a[lr][lw] = word;
+    }
+    // ---- grey tile with its halo: LDS row lr = plane row y0 + dy + r0 - 2 + lr, LDS dword lw = plane bytes cb + 4 lw .. + 3 ----
+    const int gx0 = x0 + dx + c0 - kSubHalo, gy0 = y0 + dy + r0 - kSubHalo;
+    const int cb = gx0 & ~3, off = gx0 - cb;                          // (floor to a multiple of 4, also below zero)
+    const uint8_t *img = plane + (int64_t)f * Hs * pitch;
+    for (int i = t; i < kSubGreyRows * kSubGreyDw; i += kSubThreads) {
+        const int lr = i / kSubGreyDw, lw = i - lr * kSubGreyDw;
+        const int gy = gy0 + lr, gx = cb + 4 * lw;
+        uint32_t word = 0;
+        if (lr < nr + 2 * kSubHalo && gy >= 0 && gy < Hs && gx >= 0 && gx + 4 <= pitch) word = *(const uint32_t *)(img + (int64_t)gy * pitch + gx);
+        s_g[lr][lw] = word;
+    }
+    __syncthreads();
+    const int tc = t & (kSubCols - 1), rb = (t / kSubCols) * kSubRowsPerThread;
+    uint32_t acc[25];
+#pragma unroll
+    for (int k = 0; k < 25; ++k) acc[k] = 0;
+    if (rb < nr) {                                                    // (wave-uniform)
+        const uint8_t *gcol = (const uint8_t *)&s_g[0][0] + off + tc;
+        const uint8_t *acol = (const uint8_t *)&s_a[0][0] + tc;
+        int win[5][5];                                                // win[w][jx]: the filtered row d - 2 + w of the current pixel
+#pragma unroll
+        for (int w = 0; w < 5; ++w)
+#pragma unroll
+            for (int j = 0; j < 5; ++j) win[w][j] = 0;
+#pragma unroll
+        for (int step = 0; step < kSubRowsPerThread + 2 * kSubHalo; ++step) {
+            const uint8_t *row = gcol + (rb + step) * (kSubGreyDw * 4);
+            int g[5];
+#pragma unroll
+            for (int w = 0; w < 5; ++w) g[w] = row[w];
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+#pragma unroll
+                for (int j = 0; j < 5; ++j) win[w][j] = win[w + 1][j];
+#pragma unroll
+            for (int j = 0; j < 5; ++j) {
+                int h = 0;
+#pragma unroll
+                for (int w = 0; w < 5; ++w)
+                    if (sub_weight(j, w) != 0) h += sub_weight(j, w) * g[w];
+                win[4][j] = h;
+            }
+            if (step < 2 * kSubHalo) continue;
+            const int pr = rb + step - 2 * kSubHalo;                  // the anchor row whose five filtered rows the window now holds
+            if (pr < nr && tc < nc) {
+                const uint32_t a = acol[pr * kSubCols];
+#pragma unroll
+                for (int jy = 0; jy < 5; ++jy)
+#pragma unroll
+                    for (int jx = 0; jx < 5; ++jx) {
+                        int v = 8192;
+#pragma unroll
+                        for (int w = 0; w < 5; ++w)
+                            if (sub_weight(jy, w) != 0) v += sub_weight(jy, w) * win[w][jx];
+                        v >>= 14;
+                        v = v < 0 ? 0 : v > 255 ? 255 : v;
+                        acc[jy * 5 + jx] = __builtin_amdgcn_sad_u8(a, (uint32_t)v, acc[jy * 5 + jx]);
+                    }
+            }
+        }
+    }
+    // ---- the workgroup's 25 sums (at most 32 * 64 * 255 each), then one atomic per admissible candidate ----
+#pragma unroll
+    for (int k = 0; k < 25; ++k) {
+        uint32_t s = acc[k];
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
+        if ((t & 63) == 0 && s) atomicAdd(&s_sum[k], s);
+    }
+    __syncthreads();
+    if (t < 25) {
+        const int Qy = 4 * dy + t / 5 - 2, Qx = 4 * dx + t % 5 - 2;
+        if (sub_axis_inside(y0, Ho, Hs, Qy) && sub_axis_inside(x0, Wo, Ws, Qx))      // excluded: k_stab_sub_pick marks it
+            atomicAdd(&sub[(int64_t)f * 25 + t], (u64)s_sum[t]);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_stab_sub_pick(u64 *__restrict__ sub, const swk_shift *__restrict__ shifts,
+                                                      const uint32_t *__restrict__ nonzero, int Hs, int Ws, int y0, int x0, int Ho, int Wo,
+                                                      swk_subshift *__restrict__ recs)
+{
+    __shared__ u64 s_score[25];
+    const int f = blockIdx.x, t = threadIdx.x;
+    const swk_shift first = shifts[f];
+    u64 *tab = sub + (int64_t)f * 25;
+    if (t < 25) {
+        const int Qy = 4 * first.dy + t / 5 - 2, Qx = 4 * first.dx + t % 5 - 2;
+        const bool inside = sub_axis_inside(y0, Ho, Hs, Qy) && sub_axis_inside(x0, Wo, Ws, Qx);
+        if (!inside) tab[t] = ~0ull;
+        s_score[t] = inside ? tab[t] : ~0ull;                         // (no score reaches UINT64_MAX)
+    }
+    __syncthreads();
+    if (t == 0) {
+        StabKey best{s_score[12], 16 * (first.dy * first.dy + first.dx * first.dx), 4 * first.dy, 4 * first.dx};      // q = (0, 0): always a candidate
+        if (nonzero[f])                                               // a null frame is not matched
+            for (int k = 0; k < 25; ++k) {
+                if (s_score[k] == ~0ull) continue;
+                const int Qy = 4 * first.dy + k / 5 - 2, Qx = 4 * first.dx + k % 5 - 2;
+                const StabKey key{s_score[k], Qy * Qy + Qx * Qx, Qy, Qx};
+                if (stab_less(key, best)) best = key;
+            }
+        swk_subshift rec;
+        rec.dy = first.dy; rec.dx = first.dx; rec.qy_total = best.dy; rec.qx_total = best.dx;
+        rec.sad = best.sad; rec.sad_int = first.sad; rec.sad_unshifted = first.sad_unshifted;
+        recs[f] = rec;
+    }
+}
+
+// out [F][Ho][Wo][3] dense; four bytes of a row per thread
+__global__ __launch_bounds__(256) void k_stab_resample(const uint8_t *__restrict__ frames, int64_t fs, int64_t rs, int y0, int x0, int Ho,
+                                                       int Wo, const swk_subshift *__restrict__ recs, uint8_t *__restrict__ out)
+{
+    const int f = blockIdx.y;
+    const int rowb = Wo * 3, wq = (rowb + 3) >> 2;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= Ho * wq) return;
+    const int r = idx / wq, c = (idx - r * wq) << 2;
+    const int nb = rowb - c < 4 ? rowb - c : 4;
+    const int Qy = recs[f].qy_total, Qx = recs[f].qx_total;
+    const int py = Qy & 3, px = Qx & 3;
+    // byte c of row r at phase (0, 0); the taps reach rows -1..+2 and pixels -1..+2 (3 bytes each) around it
+    const uint8_t *src = frames + (int64_t)f * fs + (int64_t)(y0 + (Qy >> 2) + r) * rs + (int64_t)(x0 + (Qx >> 2)) * 3 + c;
+    uint8_t *dst = out + ((int64_t)f * Ho + r) * rowb + c;
+    uint32_t word = 0;
+    if (py == 0 && px == 0) {
+        for (int k = 0; k < nb; ++k) word |= (uint32_t)src[k] << (8 * k);
+    } else {
+        for (int k = 0; k < nb; ++k) {
+            int v = 8192;
+            for (int ky = 0; ky < 4; ++ky) {
+                const int wy = kSubTap[py][ky];
+                if (wy == 0) continue;                                // (not read: it may lie outside the frame)
+                const uint8_t *row = src + (int64_t)(ky - 1) * rs + k;
+                int h = 0;
+                for (int kx = 0; kx < 4; ++kx) {
+                    const int wx = kSubTap[px][kx];
+                    if (wx != 0) h += wx * (int)row[3 * (kx - 1)];
+                }
+                v += wy * h;
+            }
+            v >>= 14;
+            word |= (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v) << (8 * k);
+        }
+    }
+    if (nb == 4 && ((uintptr_t)dst & 3) == 0) *(uint32_t *)dst = word;
+    else for (int k = 0; k < nb; ++k) dst[k] = (uint8_t)(word >> (8 * k));
+}
+
+size_t stabilize_sub_table_bytes(int F) { return (size_t)F * 25 * sizeof(u64); }
+
+void launch_stabilize_subpel(hipStream_t s, const uint8_t *frames, int64_t fs, int64_t rs, int F, int Hs, int Ws, int y0, int x0, int Ho,
+                             int Wo, int S, const uint8_t *anchor, int gray_mode, uint8_t *plane, uint32_t *nonzero, void *table,
+                             swk_shift *shifts, void *sub_table, swk_subshift *recs, uint8_t *out)
+{
+    u64 *tab = (u64 *)table, *sub = (u64 *)sub_table;
+    const int pitch = stabilize_pitch(Ws), ncand = (2 * S + 1) * (2 * S + 1);
+    hipError_t me = hipMemsetAsync(tab, 0, stabilize_table_bytes(F, S), s);
+    if (me == hipSuccess) me = hipMemsetAsync(sub, 0, stabilize_sub_table_bytes(F), s);
+    if (me == hipSuccess) me = hipMemsetAsync(nonzero, 0, (size_t)F * 4, s);
+    if (me != hipSuccess) { g_launch_error = (int)me; return; }          // surfaces at the context's next sync()
+    const int gq = Hs * (pitch >> 2), cq = Ho * ((Wo * 3 + 3) >> 2);
+    for (int f0 = 0; f0 < F; f0 += 32768) {
+        const int fc = F - f0 < 32768 ? F - f0 : 32768;
+        const uint8_t *fp = frames + (int64_t)f0 * fs;
+        uint8_t *pp = plane + (int64_t)f0 * Hs * pitch;
+        hipLaunchKernelGGL(k_stab_gray, dim3((gq + 255) / 256, fc), dim3(256), 0, s, fp, fs, rs, Hs, Ws, pitch, gray_mode, pp, nonzero + f0);
+        note_launch();
+        const dim3 grid((Wo + kStabCols - 1) / kStabCols, (Ho + kStabRows - 1) / kStabRows, fc);
+        hipLaunchKernelGGL(k_stab_sad, grid, dim3(kStabThreads), 0, s, anchor, pp, Hs, Ws, pitch, y0, x0, Ho, Wo, S, tab + (int64_t)f0 * ncand);
+        note_launch();
+        hipLaunchKernelGGL(k_stab_pick, dim3(fc), dim3(256), 0, s, tab + (int64_t)f0 * ncand, nonzero + f0, Hs, Ws, y0, x0, Ho, Wo, S,
+                           shifts + f0);
+        note_launch();
+        const dim3 sgrid((Wo + kSubCols - 1) / kSubCols, (Ho + kSubRows - 1) / kSubRows, fc);
+        hipLaunchKernelGGL(k_stab_sub_sad, sgrid, dim3(kSubThreads), 0, s, anchor, pp, Hs, Ws, pitch, y0, x0, Ho, Wo, shifts + f0,
+                           sub + (int64_t)f0 * 25);
+        note_launch();
+        hipLaunchKernelGGL(k_stab_sub_pick, dim3(fc), dim3(64), 0, s, sub + (int64_t)f0 * 25, shifts + f0, nonzero + f0, Hs, Ws, y0, x0, Ho,
+                           Wo, recs + f0);
+        note_launch();
+        hipLaunchKernelGGL(k_stab_resample, dim3((cq + 255) / 256, fc), dim3(256), 0, s, fp, fs, rs, y0, x0, Ho, Wo, recs + f0,
                            out + (int64_t)f0 * Ho * Wo * 3);
         note_launch();
     }

@@ -24,7 +24,7 @@ enum Slot {
     SL_BM, SL_VPREV, SL_GPART, SL_ZZPART, SL_WIN, SL_ACTIVE, SL_PARENT, SL_ROOTBITS, SL_WORDPREFIX,
     SL_NCOMP, SL_TABLE, SL_SUMS, SL_SEGS, SL_NSEG, SL_TMP_IN, SL_TMP_OUT, SL_TMP_AUX, SL_COLORW, SL_SPACEW,
     SL_TAPDR, SL_TAPDC, SL_SALT, SL_WIDE, SL_REDO_X, SL_REDO_S, SL_REDO_P, SL_SEGOFFS, SL_SEGLARGE, SL_CL_CROPS, SL_CL_OFFS, SL_CL_HW, SL_CL_PATCH, SL_CL_NET, SL_GRP, SL_REVIEW, SL_SHAPE_TAB, SL_SHAPE_REC, SL_SHAPE_NSEG,
-    SL_STAB_PLANE, SL_STAB_TAB, SL_STAB_REC, SL_COUNT
+    SL_STAB_PLANE, SL_STAB_TAB, SL_STAB_REC, SL_SUBPEL_PLANE, SL_SUBPEL_TAB, SL_SUBPEL_REC, SL_SUBPEL_SUBTAB, SL_COUNT
 };
 
 struct EventPair { hipEvent_t a, b; int fam; };
@@ -2088,10 +2088,10 @@ int32_t swk_segment_shapes_u8(swk_ctx *ctx, const uint8_t *labels, int32_t mem, 
     return sync(ctx);
 }
 
-int32_t swk_stabilize_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32_t count, int32_t Hs, int32_t Ws, int64_t frame_stride,
-                         int64_t row_stride, int32_t y0, int32_t x0, int32_t Ho, int32_t Wo, int32_t search, const uint8_t *anchor,
-                         int32_t anchor_mem, int64_t anchor_bytes, int32_t gray_mode, swk_shift *shifts, uint64_t *sad_table, uint8_t *out,
-                         int32_t out_mem)
+// the refusals that swk_stabilize_u8 and swk_stabilize_subpel_u8 share (shifts: either call's record array)
+static int32_t stabilize_refusal(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32_t count, int32_t Hs, int32_t Ws, int64_t row_stride,
+                                 int32_t y0, int32_t x0, int32_t Ho, int32_t Wo, int32_t search, const uint8_t *anchor, int32_t anchor_mem,
+                                 int64_t anchor_bytes, int32_t gray_mode, const void *shifts, const uint8_t *out, int32_t out_mem)
 {
     if (!ctx) return SWK_ERR_ARG;
     if (!frames || !anchor || !shifts || !out) return fail(ctx, SWK_ERR_ARG, "null argument");
@@ -2106,6 +2106,17 @@ int32_t swk_stabilize_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32
     for (int32_t m : {mem, anchor_mem, out_mem})
         if (m != SWK_MEM_HOST && m != SWK_MEM_DEVICE) return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
     if (count > (1 << 24)) return fail(ctx, SWK_ERR_CAPACITY, "too many frames in one call");
+    return SWK_OK;
+}
+
+int32_t swk_stabilize_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32_t count, int32_t Hs, int32_t Ws, int64_t frame_stride,
+                         int64_t row_stride, int32_t y0, int32_t x0, int32_t Ho, int32_t Wo, int32_t search, const uint8_t *anchor,
+                         int32_t anchor_mem, int64_t anchor_bytes, int32_t gray_mode, swk_shift *shifts, uint64_t *sad_table, uint8_t *out,
+                         int32_t out_mem)
+{
+    const int32_t refused = stabilize_refusal(ctx, frames, mem, count, Hs, Ws, row_stride, y0, x0, Ho, Wo, search, anchor, anchor_mem,
+                                              anchor_bytes, gray_mode, shifts, out, out_mem);
+    if (refused) return refused;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const uint8_t *src = frames, *danchor = anchor;
     int64_t fs = frame_stride, rs = row_stride;
@@ -2134,6 +2145,50 @@ int32_t swk_stabilize_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32
                      (uint32_t *)(rec + (size_t)count * sizeof(swk_shift)), table, dshifts, dout);
     HIPCHK(ctx, hipMemcpyAsync(shifts, dshifts, (size_t)count * sizeof(swk_shift), hipMemcpyDeviceToHost, ctx->stream));
     if (sad_table) HIPCHK(ctx, hipMemcpyAsync(sad_table, table, tab_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(out, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
+}
+
+int32_t swk_stabilize_subpel_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32_t count, int32_t Hs, int32_t Ws,
+                                int64_t frame_stride, int64_t row_stride, int32_t y0, int32_t x0, int32_t Ho, int32_t Wo, int32_t search,
+                                const uint8_t *anchor, int32_t anchor_mem, int64_t anchor_bytes, int32_t gray_mode, swk_subshift *shifts,
+                                uint64_t *sad_table, uint64_t *sub_table, uint8_t *out, int32_t out_mem)
+{
+    const int32_t refused = stabilize_refusal(ctx, frames, mem, count, Hs, Ws, row_stride, y0, x0, Ho, Wo, search, anchor, anchor_mem,
+                                              anchor_bytes, gray_mode, shifts, out, out_mem);
+    if (refused) return refused;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const uint8_t *src = frames, *danchor = anchor;
+    int64_t fs = frame_stride, rs = row_stride;
+    const size_t out_b = (size_t)count * Ho * Wo * 3, tab_b = stabilize_table_bytes(count, search), sub_b = stabilize_sub_table_bytes(count);
+    if (mem == SWK_MEM_HOST) {
+        uint8_t *din;
+        NEED(ctx, SL_TMP_IN, (size_t)count * Hs * Ws * 3, din);
+        const int rc = upload_rects(ctx, din, frames, row_stride, frame_stride, (size_t)Ws * 3, (size_t)Hs, count);
+        if (rc) return rc;
+        src = din; rs = (int64_t)Ws * 3; fs = (int64_t)Hs * rs;
+    }
+    if (anchor_mem == SWK_MEM_HOST) {
+        uint8_t *da;
+        NEED(ctx, SL_TMP_AUX, (size_t)anchor_bytes, da);
+        HIPCHK(ctx, hipMemcpyAsync(da, anchor, (size_t)anchor_bytes, hipMemcpyHostToDevice, ctx->stream));
+        danchor = da;
+    }
+    uint8_t *dout = out, *plane, *rec;
+    void *table, *sub;
+    if (out_mem == SWK_MEM_HOST) NEED(ctx, SL_TMP_OUT, out_b, dout);
+    NEED(ctx, SL_SUBPEL_PLANE, stabilize_plane_bytes(count, Hs, Ws), plane);
+    NEED(ctx, SL_SUBPEL_TAB, tab_b, table);
+    NEED(ctx, SL_SUBPEL_SUBTAB, sub_b, sub);
+    // the records, then stage 1's records, then the frames' non-zero flags
+    NEED(ctx, SL_SUBPEL_REC, (size_t)count * (sizeof(swk_subshift) + sizeof(swk_shift) + 4), rec);
+    swk_subshift *drecs = (swk_subshift *)rec;
+    swk_shift *dfirst = (swk_shift *)(rec + (size_t)count * sizeof(swk_subshift));
+    launch_stabilize_subpel(ctx->stream, src, fs, rs, count, Hs, Ws, y0, x0, Ho, Wo, search, danchor, gray_mode, plane,
+                            (uint32_t *)(rec + (size_t)count * (sizeof(swk_subshift) + sizeof(swk_shift))), table, dfirst, sub, drecs, dout);
+    HIPCHK(ctx, hipMemcpyAsync(shifts, drecs, (size_t)count * sizeof(swk_subshift), hipMemcpyDeviceToHost, ctx->stream));
+    if (sad_table) HIPCHK(ctx, hipMemcpyAsync(sad_table, table, tab_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (sub_table) HIPCHK(ctx, hipMemcpyAsync(sub_table, sub, sub_b, hipMemcpyDeviceToHost, ctx->stream));
     if (out_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(out, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
 }

@@ -263,6 +263,12 @@ size_t stabilize_table_bytes(int F, int S);
 void launch_stabilize(hipStream_t s, const uint8_t *frames, int64_t fs, int64_t rs, int F, int Hs, int Ws, int y0, int x0, int Ho, int Wo,
                       int S, const uint8_t *anchor, int gray_mode, uint8_t *plane, uint32_t *nonzero, void *table, swk_shift *shifts,
                       uint8_t *out);
+// the same search, then the quarter-pixel stage of swk_stabilize_subpel_u8: sub_table (stabilize_sub_table_bytes; what sub_table gets)
+// and recs [F] on the device; shifts [F] is stage 1's scratch; out is resampled at the chosen phase
+size_t stabilize_sub_table_bytes(int F);
+void launch_stabilize_subpel(hipStream_t s, const uint8_t *frames, int64_t fs, int64_t rs, int F, int Hs, int Ws, int y0, int x0, int Ho,
+                             int Wo, int S, const uint8_t *anchor, int gray_mode, uint8_t *plane, uint32_t *nonzero, void *table,
+                             swk_shift *shifts, void *sub_table, swk_subshift *recs, uint8_t *out);
 
 // ---- several groups of windows in one call ---------------------------------------------------------------
 // swk_batch_run and swk_batch_run_groups share one driver (run_batch, swk_api.hip).  A call of one group takes the uniform

@@ -13,7 +13,8 @@ from . import image_filtering as img
 
 def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size=21, classifier=None, min_seg_size=(24, 24),
                              device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None,
-                             track_by_window=True, review=None, review_text=False, review_stages=(), shape_props=False, stabilize=0):
+                             track_by_window=True, review=None, review_text=False, review_stages=(), shape_props=False, stabilize=0,
+                             stabilize_subpel=False):
     """Same call order as __main__.py:62-100.  corners = ((x1, y1), (x2, y2)) of the chimney's top edge: crop region
     and ROI mask are then generated from the video's first frame (:62-63) instead of being passed in.  Returns the tracker's detected events (lists of Segment objects,
     the structure the reference hands to event classification).  windows_per_call > 1 reads that many queue-fuls
@@ -33,13 +34,16 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     without it, and without it nothing is different (no extra call, no label planes).  stabilize: a search range S of 1..16 pixels
     (True = 8) for shaken footage: the reader is wrapped in a stabilize.StabilizingReader, which hands out every frame cut at the
     integer shift that matches it best to the video's first frame (one more GPU call per window, swk_stabilize_u8); everything else
-    sees a stabilized video.  A reader that is a StabilizingReader already is taken as it is.  0 (the default): nothing is different."""
+    sees a stabilized video.  A reader that is a StabilizingReader already is taken as it is.  0 (the default): nothing is different.
+    stabilize_subpel=True (with stabilize; ValueError without): the quarter-pixel stage after the integer search
+    (swk_stabilize_subpel_u8 in swk_stabilize_u8's place): every frame is resampled at the best of the 25 quarter-pixel shifts
+    around the integer one.  False (the default): nothing is different."""
     if corners is not None:
         first_frame = reader.read_frame(0, increment=False)                        # :62
         crop_region, roi_mask, _ = img.generate_regions(first_frame, corners)      # :63
     if crop_region is None or roi_mask is None:
         raise ValueError("either corners or crop_region + roi_mask are needed")
-    reader = _stabilized(reader, crop_region, stabilize, min_seg_size, device, params)
+    reader = _stabilized(reader, crop_region, stabilize, min_seg_size, device, params, stabilize_subpel)
     if hasattr(reader, "set_region"):                # a reader of a pipe (io_y4m.Y4MStreamReader): it keeps only what this loop reads
         reader.set_region(crop_region, min_seg_size)
     tracker = SegmentTracker(roi_mask)
@@ -56,14 +60,19 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
             own_review.close()
 
 
-def _stabilized(reader, crop_region, stabilize, min_seg_size, device, params):
-    """The reader itself, or with stabilize = S > 0 a stabilize.StabilizingReader around it (grey as the segment path's params say)."""
+def _stabilized(reader, crop_region, stabilize, min_seg_size, device, params, subpel=False):
+    """The reader itself, or with stabilize = S > 0 a stabilize.StabilizingReader around it (grey as the segment path's params say);
+    subpel: with its quarter-pixel stage."""
     if not stabilize:
+        if subpel:
+            raise ValueError("stabilize_subpel refines the integer search of stabilize=S: it needs stabilize")
         return reader
     from .stabilize import StabilizingReader, search_range
     if isinstance(reader, StabilizingReader):
         return reader
     kw = {"gray_mode": params.gray_mode} if params is not None else {}
+    if subpel:
+        kw["subpel"] = True
     return StabilizingReader(reader, crop_region, search_range(stabilize), min_seg_size, device=device, **kw)
 
 
@@ -180,7 +189,7 @@ def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None,
     review.ReviewWriter: the review video of the count), review_text (text in a review made from a path) and review_stages (stage
     images as panels in it) as in swift_counting_algorithm; so is shape_props=True (among **kw): the events' segments then carry the
     shape properties; and stabilize=S (among **kw; True = 8): shaken footage is brought back onto its first frame before it is
-    segmented."""
+    segmented, with stabilize_subpel=True to a quarter pixel."""
     opened = None
     if _is_video_source(frames):
         from .io_y4m import open_y4m
@@ -267,7 +276,7 @@ def schedule_videos(readers, sizes, segment, consume, in_flight=4, windows_per_c
 
 def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows_per_call=1, classifier=None, queue_size=21,
                         min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True, reviews=None,
-                        review_text=False, review_stages=(), shape_props=False, stabilize=0):
+                        review_text=False, review_stages=(), shape_props=False, stabilize=0, stabilize_subpel=False):
     """count_swifts over a list of videos (the reference's loop over its video list, __main__.py:21), several videos at a time on one
     GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
     windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
@@ -279,21 +288,23 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
     reviews: per video a path, a review.ReviewWriter or None -- that video's review video (swift_counting_algorithm's review=);
     review_text: the writers made here from paths also write text (its review_text=); review_stages: and show these stage images as
     panels (its review_stages=).  shape_props: as swift_counting_algorithm's; one shape call per group of a GPU call, since the
-    groups' geometries differ.  stabilize: as swift_counting_algorithm's, one StabilizingReader per video.
+    groups' geometries differ.  stabilize and stabilize_subpel: as swift_counting_algorithm's, one StabilizingReader per video.
     Returns [(count, events), ...] in input order."""
     from .io_y4m import open_y4m
     readers = [open_y4m(v) if _is_video_source(v) else v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
     opened = [r for r, v in zip(readers, videos) if r is not v and hasattr(r, "close")]          # (closed again when the count is done)
     try:
         return _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device,
-                             pad_factor, params, track_by_window, reviews, review_text, review_stages, shape_props, stabilize)
+                             pad_factor, params, track_by_window, reviews, review_text, review_stages, shape_props, stabilize,
+                             stabilize_subpel)
     finally:
         for r in opened:
             r.close()
 
 
 def _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device, pad_factor, params,
-                  track_by_window=True, reviews=None, review_text=False, review_stages=(), shape_props=False, stabilize=0):
+                  track_by_window=True, reviews=None, review_text=False, review_stages=(), shape_props=False, stabilize=0,
+                  stabilize_subpel=False):
     """count_swifts_videos over readers."""
     if regions is None:
         if corners is None:
@@ -304,8 +315,11 @@ def _count_videos(readers, regions, corners, in_flight, windows_per_call, classi
             regions.append((crop_region, roi_mask))
     if len(regions) != len(readers):
         raise ValueError("one region pair per video")
+    if stabilize_subpel and not stabilize:
+        raise ValueError("stabilize_subpel refines the integer search of stabilize=S: it needs stabilize")
     if stabilize:
-        readers = [_stabilized(r, crop_region, stabilize, min_seg_size, device, params) for r, (crop_region, _) in zip(readers, regions)]
+        readers = [_stabilized(r, crop_region, stabilize, min_seg_size, device, params, stabilize_subpel)
+                   for r, (crop_region, _) in zip(readers, regions)]
     for r, (crop_region, _) in zip(readers, regions):
         if hasattr(r, "set_region"):                 # a reader of a pipe (io_y4m.Y4MStreamReader): it keeps only what this loop reads
             r.set_region(crop_region, min_seg_size)

@@ -6,7 +6,11 @@ that moves one pixel between frames puts every edge of the chimney into the spar
 frames, and per window asks the GPU (swk_stabilize_u8, csrc/stabilize.hip) for the integer shift of every frame at which the grey of
 the crop region plus its margin differs least from an anchor image, and for the frame's pixels there.  It returns them as
 io_roi_stream.RoiFrame objects labelled with the UNSHIFTED origin, so FrameQueue, the batch calls, the classifier hand-over, the
-tracker and the review writer see a stabilized video and need not know."""
+tracker and the review writer see a stabilized video and need not know.
+
+With subpel=True the call is swk_stabilize_subpel_u8: after the integer search the 25 quarter-pixel shifts around its winner are scored
+on the grey resampled with a 4-tap Catmull-Rom filter, and the frame's pixels are resampled at the best one, which takes the half
+pixel of residue that integer shifts leave out of the segment stage's sparse term."""
 import numpy as np
 
 from . import _lib
@@ -49,9 +53,16 @@ class StabilizingReader:
     the newest stabilized frame of that window (dusk footage darkens over an hour: a fixed anchor would end up matching against
     another exposure); reanchor=0 never replaces it.  shifts: frame number -> (dy, dx, sad, sad_unshifted).
 
-    backend: what makes the calls (stabilize and bgr2gray of _lib.Context); None = the process's context on `device`."""
+    subpel=True: the quarter-pixel stage follows the integer search (stabilize_subpel of the backend instead of stabilize).  The
+    rectangle read per window, and the one a pipe's reader is asked to hold, grow by search + 2 instead of search: the filter's
+    footprint.  shifts keeps its meaning -- the integer stage's (dy, dx, sad, sad_unshifted) -- and subshifts: frame number ->
+    (Qy, Qx, sad_subpel) holds the chosen total shift in quarter pixels and its score.  The anchor is replaced by the same rule: the
+    grey of the newest stabilized (here: resampled) frame, as handed out.
 
-    def __init__(self, reader, crop_region, search=8, min_seg_size=(24, 24), reanchor=1, device=0, gray_mode=_lib.GRAY_Q14, backend=None):
+    backend: what makes the calls (stabilize, stabilize_subpel and bgr2gray of _lib.Context); None = the process's context on `device`."""
+
+    def __init__(self, reader, crop_region, search=8, min_seg_size=(24, 24), reanchor=1, device=0, gray_mode=_lib.GRAY_Q14, backend=None,
+                 subpel=False):
         if isinstance(reader, RoiStreamReader) or isinstance(getattr(reader, "reader", None), RoiStreamReader):
             raise ValueError("a ROI stream file (RoiStreamReader) holds the crop region plus a fixed margin of half the minimum segment "
                              "size: there are no pixels to search a shift in; stabilize the source it was written from")
@@ -65,17 +76,20 @@ class StabilizingReader:
         self.min_seg_size = tuple(int(s) for s in min_seg_size)
         self.reanchor, self.device, self.gray_mode = int(reanchor), device, int(gray_mode)
         self._backend = backend
+        self.subpel = bool(subpel)
+        self.grow = self.search + 2 if self.subpel else self.search          # pixels read around the margin rectangle on every side
         self.anchor = None
         self.shifts = {}
+        self.subshifts = {}
         self.windows = 0
         self._staging = None
         if hasattr(reader, "set_region"):
-            grown = (self.min_seg_size[0] + 2 * self.search, self.min_seg_size[1] + 2 * self.search)
+            grown = (self.min_seg_size[0] + 2 * self.grow, self.min_seg_size[1] + 2 * self.grow)
             try:
                 reader.set_region(self.crop_region, grown)
             except ValueError as exc:
                 raise ValueError("stabilize: the stream reader has already fixed the rectangle it holds, which is smaller than the crop "
-                                 "region plus its margin plus %d search pixels (%s)" % (self.search, exc))
+                                 "region plus its margin plus %d search pixels (%s)" % (self.grow, exc))
 
     # ---- the wrapped reader's surface ----
     def __getattr__(self, name):                     # fps, total_frames, start_frame, end_frame, filepath, read_frame, get_frame, counters
@@ -116,7 +130,7 @@ class StabilizingReader:
         full_shape = tuple(first.shape)
         if len(full_shape) != 3 or full_shape[2] != 3:
             raise ValueError("stabilization needs BGR frames (H, W, 3)")
-        (ya, yb, xa, xb), (sa, sb, ta, tb) = search_rect(full_shape, self.crop_region, self.search, self.min_seg_size)
+        (ya, yb, xa, xb), (sa, sb, ta, tb) = search_rect(full_shape, self.crop_region, self.grow, self.min_seg_size)
         Ho, Wo = yb - ya, xb - xa
         real = [k for k, num in enumerate(numbers) if num >= 0]
         if self.anchor is None and not real:         # nothing but null frames before any real one: nothing to match against
@@ -133,31 +147,55 @@ class StabilizingReader:
             if not isinstance(cutout, np.ndarray):
                 cutout = cutout.contiguous().cpu().numpy()
             self.anchor = np.ascontiguousarray(ctx.bgr2gray(np.ascontiguousarray(cutout), self.gray_mode))
-        shifts, _, pixels = ctx.stabilize(stack, (ya - sa, xa - ta, Ho, Wo), self.search, self.anchor, gray_mode=self.gray_mode)
-        for k in real:
-            s = shifts[k]
-            self.shifts[int(numbers[k])] = (int(s["dy"]), int(s["dx"]), int(s["sad"]), int(s["sad_unshifted"]))
+        if self.subpel:
+            shifts, _, pixels = ctx.stabilize_subpel(stack, (ya - sa, xa - ta, Ho, Wo), self.search, self.anchor, gray_mode=self.gray_mode)
+            for k in real:
+                s = shifts[k]
+                self.shifts[int(numbers[k])] = (int(s["dy"]), int(s["dx"]), int(s["sad_int"]), int(s["sad_unshifted"]))
+                self.subshifts[int(numbers[k])] = (int(s["qy_total"]), int(s["qx_total"]), int(s["sad"]))
+        else:
+            shifts, _, pixels = ctx.stabilize(stack, (ya - sa, xa - ta, Ho, Wo), self.search, self.anchor, gray_mode=self.gray_mode)
+            for k in real:
+                s = shifts[k]
+                self.shifts[int(numbers[k])] = (int(s["dy"]), int(s["dx"]), int(s["sad"]), int(s["sad_unshifted"]))
         self.windows += 1
         if self.reanchor and real and self.windows % self.reanchor == 0:
             self.anchor = np.ascontiguousarray(ctx.bgr2gray(np.ascontiguousarray(pixels[real[-1]]), self.gray_mode))
         return [RoiFrame(pixels[k], (ya, xa), full_shape) for k in range(len(frames))], numbers, stamps
 
 
-def summary(shifts, search):
+def summary(shifts, search, subshifts=None):
     """The CLI's "stabilize" entry: {"search": S, "moved_frames": frames with a shift other than (0, 0), "max_shift": the largest
-    |dy| or |dx|}"""
+    |dy| or |dx|}; with the quarter-pixel stage's subshifts also "subpel": true and "fractional_frames": frames whose chosen total
+    shift is not a whole number of pixels on both axes"""
     moved = [v for v in shifts.values() if v[0] or v[1]]
-    return {"search": int(search), "moved_frames": len(moved), "max_shift": max((max(abs(v[0]), abs(v[1])) for v in moved), default=0)}
+    out = {"search": int(search), "moved_frames": len(moved), "max_shift": max((max(abs(v[0]), abs(v[1])) for v in moved), default=0)}
+    if subshifts is not None:
+        out["subpel"] = True
+        out["fractional_frames"] = sum(1 for v in subshifts.values() if v[0] % 4 or v[1] % 4)
+    return out
 
 
 CSV_COLUMNS = ("frame_number", "dy", "dx", "sad", "sad_unshifted")
+CSV_SUBPEL_COLUMNS = ("shift_y", "shift_x", "sad_subpel")
 
 
-def write_csv(path, shifts):
-    """stabilization.csv: one row per frame, ascending frame number"""
+def write_csv(path, shifts, subshifts=None):
+    """stabilization.csv: one row per frame, ascending frame number; with the quarter-pixel stage's subshifts three more columns: the
+    chosen total shift in pixels as decimal text with two places (-1.25) and its score"""
     import csv
     with open(path, "w", newline="") as fh:
         w = csv.writer(fh)
-        w.writerow(CSV_COLUMNS)
+        w.writerow(CSV_COLUMNS + (CSV_SUBPEL_COLUMNS if subshifts is not None else ()))
         for number in sorted(shifts):
-            w.writerow([int(number)] + [int(x) for x in shifts[number]])
+            row = [int(number)] + [int(x) for x in shifts[number]]
+            if subshifts is not None:
+                Qy, Qx, sad = subshifts[number]
+                row += [quarter_text(Qy), quarter_text(Qx), int(sad)]
+            w.writerow(row)
+
+
+def quarter_text(Q):
+    """Q quarter pixels as pixels with two decimal places: -5 -> "-1.25" (exact: integer arithmetic)"""
+    Q = int(Q)
+    return "%s%d.%02d" % ("-" if Q < 0 else "", abs(Q) // 4, abs(Q) % 4 * 25)

@@ -7,7 +7,10 @@
 2. The counting loop: pipeline.count_swifts over a seeded synthetic clip (crop region 424 x 212 in 480 x 270 pictures) with and
    without stabilize=8, alternating round by round: frames/s of each, their ratio, and where a window's extra time goes -- the
    reader's get_n_frames alone (staging the search rectangles, the call, the anchor) and the library call inside it.
-    python tools/bench_stabilize.py [--reps 30] [--repeats 5] [--rounds 5] [--frames 210] [--windows-per-call 2]"""
+--subpel adds the quarter-pixel stage (swk_stabilize_subpel_u8, stabilize_subpel=True) to both: the call at S = 8 on the same
+sources, device and host, beside swk_stabilize_u8 in the same blocks ("subpel_device_s8", "subpel_host_s8"), and the counting loop
+with stabilize=8, stabilize_subpel=True as a third variant of every round.
+    python tools/bench_stabilize.py [--subpel] [--reps 30] [--repeats 5] [--rounds 5] [--frames 210] [--windows-per-call 2]"""
 import argparse
 import json
 import os
@@ -23,7 +26,7 @@ from swiftwatcher_amd import _lib          # noqa: E402
 HO, WO = 212 + 24, 424 + 24
 
 
-def call_rows(ctx, reps, repeats):
+def call_rows(ctx, reps, repeats, subpel=False):
     import torch
     from swiftwatcher_amd import synthetic
     rows = []
@@ -38,6 +41,9 @@ def call_rows(ctx, reps, repeats):
             calls["device_s%d" % S] = lambda d=dev, a=danchor, r=rect, s=S: ctx.stabilize(d, r, s, a, device_out=True)
             if S == 8:
                 calls["host_s%d" % S] = lambda f=frames, a=anchor, r=rect, s=S: ctx.stabilize(f, r, s, a)
+                if subpel:
+                    calls["subpel_device_s%d" % S] = lambda d=dev, a=danchor, r=rect, s=S: ctx.stabilize_subpel(d, r, s, a, device_out=True)
+                    calls["subpel_host_s%d" % S] = lambda f=frames, a=anchor, r=rect, s=S: ctx.stabilize_subpel(f, r, s, a)
             meta[S] = dict(source_bytes=int(frames.nbytes), out_bytes=n * HO * WO * 3, candidates=(2 * S + 1) ** 2)
         ms = {name: [] for name in calls}
         for call in calls.values():
@@ -57,7 +63,7 @@ def call_rows(ctx, reps, repeats):
     return rows
 
 
-def loop_rows(frames_n, rounds, wpc, search=8):
+def loop_rows(frames_n, rounds, wpc, search=8, subpel=False):
     from swiftwatcher_amd import pipeline, synthetic
     from swiftwatcher_amd.io_frames import ArrayReader
     from swiftwatcher_amd.stabilize import StabilizingReader
@@ -68,13 +74,18 @@ def loop_rows(frames_n, rounds, wpc, search=8):
     kw = dict(crop_region=crop, roi_mask=roi_mask, windows_per_call=wpc)
     want = pipeline.count_swifts(frames, **kw)                                   # warm-up, and the count both variants must give
     pipeline.count_swifts(frames, stabilize=search, **kw)
-    times = {"plain": [], "stabilized": []}
+    variants = {"plain": {}, "stabilized": {"stabilize": search}}
+    if subpel:
+        variants["subpel"] = {"stabilize": search, "stabilize_subpel": True}
+        pipeline.count_swifts(frames, **variants["subpel"], **kw)
+    times = {name: [] for name in variants}
     for _ in range(rounds):
         for name in times:
             t0 = time.perf_counter()
-            got = pipeline.count_swifts(frames, **({} if name == "plain" else {"stabilize": search}), **kw)
+            got = pipeline.count_swifts(frames, **variants[name], **kw)
             times[name].append(time.perf_counter() - t0)
-            assert got[0] == want[0] and len(got[1]) == len(want[1])             # (a clip that does not move: every shift is (0, 0))
+            if name != "subpel":                         # (a clip that does not move: every integer shift is (0, 0); noise can move the
+                assert got[0] == want[0] and len(got[1]) == len(want[1])             # quarter-pixel choice of a frame)
     # where a window's extra time goes: the reader alone, and the library call inside it
     ctx = _lib.default_context(0)
     inner, spent = ctx.stabilize, []
@@ -104,6 +115,11 @@ def loop_rows(frames_n, rounds, wpc, search=8):
     plain_read_ms = (time.perf_counter() - t0) / plain_windows * 1e3
     med = {k: float(np.median(v)) for k, v in times.items()}
     windows = -(-(frames_n + 1) // 21)
+    extra = {}
+    if subpel:
+        extra = {"subpel_fps": round(frames_n / med["subpel"], 1), "subpel_s": [round(t, 4) for t in times["subpel"]],
+                 "subpel_over_plain": round(med["subpel"] / med["plain"], 4), "subpel_over_stabilized": round(med["subpel"] / med["stabilized"], 4),
+                 "subpel_extra_ms_per_window": round((med["subpel"] - med["plain"]) / windows * 1e3, 4)}
     return [{"bench": "stabilize_loop", "frames": frames_n, "windows_per_call": wpc, "crop": [424, 212], "search": search, "events": len(want[1]),
              "plain_fps": round(frames_n / med["plain"], 1), "stabilized_fps": round(frames_n / med["stabilized"], 1),
              "plain_s": [round(t, 4) for t in times["plain"]], "stabilized_s": [round(t, 4) for t in times["stabilized"]],
@@ -111,7 +127,7 @@ def loop_rows(frames_n, rounds, wpc, search=8):
              "extra_ms_per_window": round((med["stabilized"] - med["plain"]) / windows * 1e3, 4),
              "reader_get_n_frames_ms_per_window": round(float(np.median(per_window)) * 1e3, 4),
              "of_which_library_call_ms": round(float(np.median(spent)) * 1e3, 4),
-             "plain_reader_get_n_frames_ms_per_window": round(plain_read_ms, 4)}]
+             "plain_reader_get_n_frames_ms_per_window": round(plain_read_ms, 4), **extra}]
 
 
 def main():
@@ -121,12 +137,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--frames", type=int, default=210)
     ap.add_argument("--windows-per-call", type=int, default=2)
+    ap.add_argument("--subpel", action="store_true", help="also time swk_stabilize_subpel_u8 and the loop with stabilize_subpel=True")
     a = ap.parse_args()
     ctx = _lib.default_context(0)
-    for row in call_rows(ctx, a.reps, a.repeats):
+    for row in call_rows(ctx, a.reps, a.repeats, a.subpel):
         print(json.dumps(row), flush=True)
     for wpc in sorted({1, a.windows_per_call}):
-        for row in loop_rows(a.frames, a.rounds, wpc):
+        for row in loop_rows(a.frames, a.rounds, wpc, subpel=a.subpel):
             print(json.dumps(row), flush=True)
 
 
