@@ -172,7 +172,10 @@ int32_t swk_debug_tracker_force_assignment(swk_tracker *t, int32_t skip_frames, 
  * size (today 2 for all four shapes).  knob 2: workgroup layout of the split-bf16 Winograd 3 x 3 expands (results do
  * not depend on it, bit for bit): 0 = each shape's default, 1 = one column block and two tile groups of 32 tiles per wave for every
  * shape, 2 = two waves per column block sharing one filter slice (48 -> 192 as 12 waves, 64 -> 256 as 16, 32 -> 128 as 8 waves over 128
- * tiles) for every shape that has such a layout.  Any other knob or value: SWK_ERR_ARG. */
+ * tiles) for every shape that has such a layout.  knob 4, conv1 and the wide plain squeezes (256 -> 48, 384 -> 48, 384 -> 64): 0 = the float32
+ * kernel; 1 = the default: each shape's own choice, the same at every batch size (today the split-bf16 kernel with its weights in LDS
+ * for conv1 and all three squeezes: float32-accurate, another summation order; environment default SWK_SQUEEZE_SPLIT_BF16, beside SWK_EXPAND_SPLIT_BF16
+ * for knob 1).  Any other knob (3 included) or value: SWK_ERR_ARG. */
 int32_t swk_set_cnn_tuning(int32_t knob, int32_t value);
 
 #ifdef __cplusplus

@@ -39,7 +39,11 @@ int launch_expand1x1_split_bf16_ws(hipStream_t s, const float *src, int64_t rows
 // A/B switch (swk_set_cnn_tuning knob 1) for the expand1x1 shapes: 0 = the float32 kernel, 1 = the split-bf16 kernel with its weights in
 // LDS, 2 = the split-bf16 kernel with its weights in registers, 3 = each shape's default (swk_nhwc_conv1x1_bias_relu_place)
 extern int g_expand_split_bf16;
-extern int g_wino_bf16s_layout;          // A/B switch (swk_set_cnn_tuning knob 2): workgroup layout of the split-bf16 Winograd expands
+// the wide plain squeezes (256 -> 48, 384 -> 48, 384 -> 64) on split-bf16 products (cnn_squeeze_bf16.hip); SWK_ERR_ARG for other shapes
+int launch_squeeze1x1_split_bf16(hipStream_t s, const float *src, int64_t rows, const Crop &cr, int cin, int h, int w, const float *wgt,
+                                 const float *bias, int cout, const Place &pl);
+extern int g_squeeze_split_bf16;         // A/B switch (swk_set_cnn_tuning knob 4), conv1 and the wide squeezes: 0 = the float32 kernels, 1 = each shape's default
+extern int g_wino_bf16s_layout;         // A/B switch (swk_set_cnn_tuning knob 2): workgroup layout of the split-bf16 Winograd expands
 
 // The fused epilogue: register quad g of an accumulator = four consecutive output channels of the lane's pixel; bias, ReLU, one
 // float4 store.  An add, then a max (the library is built without contraction).
@@ -62,6 +66,17 @@ __device__ __forceinline__ void split3(float x, __bf16 &a, __bf16 &b, __bf16 &c)
     const float r = x - (float)a;
     b = (__bf16)r;
     c = (__bf16)(r - (float)b);
+}
+// eight consecutive channels (two float4s) into the three operands of a k-step of v_mfma_f32_32x32x16_bf16
+__device__ __forceinline__ void split3(const float4 lo, const float4 hi, bf16x8 &p1, bf16x8 &p2, bf16x8 &p3)
+{
+    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        __bf16 a, b, c;
+        split3(v[j], a, b, c);
+        p1[j] = a; p2[j] = b; p3[j] = c;
+    }
 }
 inline void split3_host(float x, uint16_t part[3])
 {

@@ -15,6 +15,11 @@
 //     value used by ~12 output pixels).
 //   * A operand (weights): all of W, re-laid [dy][j][half][co] with pitch 97, sits in LDS (65 KB); one ds_read_b32 per MFMA.
 //   * three accumulators (96 channels) per 32 pixels; a register quad = four consecutive channels of the lane's pixel: float4 stores.
+//
+// Two kernels behind swk_nhwc_conv7x7s2_bias_relu.  k_conv7x7s2_relu (the float32 MFMA, described above) runs at 100 of the 157 TFLOP/s
+// of the float32 matrix pipe while moving 1.6 TB/s: pipe-bound.  k_conv7x7s2_bf16s_relu, the DEFAULT at every size (swk_set_cnn_tuning
+// knob 4 = 0 goes back to the float32 kernel), forms the same float32 products from split bf16 operands at 11 k-steps x 6 MFMAs of 32
+// cycles per 32 channels where float32 takes 84 of 64; it is described at its definition below.  Measured: DESIGN section 6.
 // Launched on the CALLER's stream (PyTorch's current stream).
 #include "cnn_common.h"
 
@@ -98,6 +103,102 @@ __global__ __launch_bounds__(512, 4) void k_conv7x7s2_relu(const float *__restri
     }
 }
 
+// ---- the same convolution with every float32 product formed from split bf16 operands (cnn_expand_bf16.hip: split3, six products per
+// k-step, smallest first) on v_mfma_f32_32x32x16_bf16.  K is ordered (patch row dy, j = 3 dx + c) with a patch row's 21 floats padded to
+// 24 by zero weights, so that a lane's eight consecutive k lie in one image row: k = 24 dy + j, 7 x 24 = 168, eleven k-steps of 16 (the
+// last eight k are an eighth patch row of zero weights).  Lane (pixel r, half h) supplies k = 16 s + 8 h .. + 7 of k-step s: eight
+// consecutive floats of image row 2 (lo + y) + dy from column 6 (lo + x) + j, four 8-byte loads.  The pad columns 21..23 and the
+// eighth row are real pixels of the same image (the entry point's check 2 (lo + m - 1) + 8 <= side keeps the 24th float of a patch
+// row and the eighth row inside it) multiplied by zero weights.  Split weights in LDS, [11 k-steps][3 column blocks][3 parts][2 halves]
+// [32 output channels][8 bf16] = 99 KB, staged in W's own order and split once per persistent workgroup; one 8-wave workgroup per CU. ----
+__global__ __launch_bounds__(512) void k_conv7x7s2_bf16s_relu(const float *__restrict__ src, int64_t rows, int side, int lo, int m,
+                                                         const float *__restrict__ wgt, const float *__restrict__ bias, float *__restrict__ dst,
+                                                         FastDiv fmm, FastDiv fm)
+{
+    constexpr int NB = 3, NP = 96, KS = 11, OPS = KS * NB;
+    extern __shared__ uint4 lds_c[];               // split weights: [KS][NB][3][2][32] x 16 bytes, then the bias
+    float *lbias = (float *)(lds_c + OPS * 192);
+    __bf16 *lw = (__bf16 *)lds_c;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+    // ---- weights: zeros first (pad columns, eighth row), then W[co][c][dy][dx] walked in its own order (consecutive lanes read
+    //      consecutive floats; see the staging loop of k_conv7x7s2_relu), each value split and its three parts stored ----
+    for (int i = tid; i < OPS * 192; i += 512) lds_c[i] = make_uint4(0u, 0u, 0u, 0u);
+    if (tid < NP) lbias[tid] = bias[tid];
+    __syncthreads();
+    for (int i = tid; i < NP * 147; i += 512) {
+        const int co = i / 147, rem = i - co * 147, c = rem / 49, r2 = rem - c * 49, dy = r2 / 7, dx = r2 - dy * 7;
+        const int k = 24 * dy + 3 * dx + c, st = k >> 4, kg = (k >> 3) & 1, e = k & 7, nb = co >> 5, mch = co & 31;
+        __bf16 w1, w2, w3;
+        split3(wgt[i], w1, w2, w3);
+        __bf16 *d = lw + (((st * NB + nb) * 3) * 64 + kg * 32 + mch) * 8 + e;
+        d[0] = w1; d[64 * 8] = w2; d[128 * 8] = w3;
+    }
+    __syncthreads();
+
+    const int mm2 = m * m, rowf = side * 3;                          // floats per image row
+    const int64_t ntiles = (rows + 31) >> 5;
+    // operand reads run one (k-step, column block) ahead of the products (33 operands, an odd number: the two register sets do not come
+    // round at the end of a tile, so each tile starts with a read of its own)
+    bf16x8 wq[2][3];
+    auto read_w = [&](int op, int set) {
+        const uint4 *q = lds_c + op * 192 + lane;
+        wq[set][0] = __builtin_bit_cast(bf16x8, q[0]); wq[set][1] = __builtin_bit_cast(bf16x8, q[64]); wq[set][2] = __builtin_bit_cast(bf16x8, q[128]);
+    };
+    for (int64_t tile = (int64_t)blockIdx.x * 8 + wave; tile < ntiles; tile += (int64_t)gridDim.x * 8) {
+        const int64_t q = tile * 32 + r;
+        const bool valid = q < rows;
+        const unsigned qq = valid ? (unsigned)q : (unsigned)rows - 1u;          // rows < 2^31 (checked by the launcher)
+        const unsigned b = fmm.div(qq), rem = qq - b * (unsigned)mm2, y = fm.div(rem), x = rem - y * (unsigned)m;
+        const float *p = src + (((int64_t)b * side + 2 * (lo + y)) * (int64_t)side + 2 * (lo + x)) * 3;
+        // all eleven k-steps of the tile leave at once (88 registers: two waves per SIMD have 256)
+        float2 raw[KS][4];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const int k0 = 16 * s, k1 = 16 * s + 8;          // the lane's first k: half 0, half 1
+            const float *ps = p + (hh ? (k1 / 24) * rowf + k1 % 24 : (k0 / 24) * rowf + k0 % 24);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) raw[s][v] = *(const float2 *)(ps + 2 * v);
+        }
+        __builtin_amdgcn_sched_barrier(0);          // left alone the scheduler moves every load next to its split and waits for it there
+        read_w(0, 0);
+        f16v acc[NB];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[nb][e] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            bf16x8 x1, x2, x3;
+            split3(make_float4(raw[s][0].x, raw[s][0].y, raw[s][1].x, raw[s][1].y), make_float4(raw[s][2].x, raw[s][2].y, raw[s][3].x, raw[s][3].y),
+                   x1, x2, x3);
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) {
+                const int op = s * NB + nb, set = op & 1;
+                if (op + 1 < OPS) read_w(op + 1, set ^ 1);
+                // smallest terms first
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[set][0], x3, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[set][1], x2, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[set][2], x1, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[set][0], x2, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[set][1], x1, acc[nb], 0, 0, 0);
+                acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[set][0], x1, acc[nb], 0, 0, 0);
+                if (op + 1 < OPS) __builtin_amdgcn_sched_group_barrier(0x100 /* DS read */, 3, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008 /* MFMA */, 6, 0);
+            }
+        }
+        if (valid) {
+            float *o = dst + q * NP + 4 * hh;
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int c = nb * 32 + 8 * g;
+                    store_bias_relu(o + c, acc[nb], g, *(const float4 *)(lbias + c + 4 * hh));
+                }
+        }
+    }
+}
+
 }  // namespace swk
 
 #pragma GCC visibility push(default)
@@ -112,11 +213,21 @@ int32_t swk_nhwc_conv7x7s2_bias_relu(void *stream, const float *src, int32_t n, 
         (((uintptr_t)src) & 7) || (((uintptr_t)dst) & 15))
         return SWK_ERR_ARG;
     using namespace swk;
+    const int64_t rows = (int64_t)n * m * m, ntiles = (rows + 31) / 32;
+    if (rows > (int64_t)0x7fffff00) return SWK_ERR_CAPACITY;
+    if (g_squeeze_split_bf16) {          // the default at every size (knob 4 = 0: the float32 kernel below)
+        const size_t lds_s = (size_t)11 * 3 * 192 * 16 + 96 * sizeof(float);
+        static unsigned long long attr_mask_s = 0;
+        if (!ensure_dyn_lds((const void *)k_conv7x7s2_bf16s_relu, 160 * 1024 - 256, attr_mask_s)) return SWK_ERR_HIP;
+        int64_t blocks = (ntiles + 7) / 8;
+        if (blocks > 256) blocks = 256;          // one 8-wave workgroup per CU (99 KB of LDS), persistent over the row tiles
+        hipLaunchKernelGGL(k_conv7x7s2_bf16s_relu, dim3((unsigned)blocks), dim3(512), lds_s, (hipStream_t)stream, src, rows, side, lo, m, weight, bias,
+                           dst, FastDiv((unsigned)(m * m)), FastDiv((unsigned)m));
+        return hipGetLastError() == hipSuccess ? SWK_OK : SWK_ERR_HIP;
+    }
     const size_t lds = (size_t)(((4 * 21 * 2 * 97 + 3) & ~3) + 96) * sizeof(float);
     static unsigned long long attr_mask = 0;
     if (!ensure_dyn_lds((const void *)k_conv7x7s2_relu, 160 * 1024 - 256, attr_mask)) return SWK_ERR_HIP;
-    const int64_t rows = (int64_t)n * m * m, ntiles = (rows + 31) / 32;
-    if (rows > (int64_t)0x7fffff00) return SWK_ERR_CAPACITY;
     int64_t blocks = (ntiles + 7) / 8;
     if (blocks > 512) blocks = 512;          // two 8-wave workgroups per CU (65 KB of LDS each), persistent over the row tiles
     hipLaunchKernelGGL(k_conv7x7s2_relu, dim3((unsigned)blocks), dim3(512), lds, (hipStream_t)stream, src, rows, side, lo, m, weight, bias, dst,

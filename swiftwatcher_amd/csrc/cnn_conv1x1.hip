@@ -24,6 +24,10 @@
 //   * the weights (at most 512 x 64 or 64 x 256 floats) sit transposed in LDS, [ci][co] with pitch N + 1: the staging
 //     reads W coalesced along ci and writes conflict-free, and an operand read is 32 consecutive floats per half.
 // Launched on the CALLER's stream (PyTorch's current stream), like the other glue kernels (cnn_aux.hip).
+//
+// Shapes that no longer take this kernel by default (chosen per shape, never per size, in swk_nhwc_conv1x1_bias_relu_place below):
+// the Fire expand1x1s (cnn_expand_bf16.hip, knob 1) and the wide plain squeezes 256 -> 48, 384 -> 48, 384 -> 64 (cnn_squeeze_bf16.hip,
+// knob 4), both on float32 products formed from split bf16 operands.
 #include "cnn_common.h"
 
 namespace swk {
@@ -160,13 +164,20 @@ static int launch_conv1x1_d(hipStream_t s, const float *src, int64_t rows, const
 }
 
 int g_expand_split_bf16 = getenv("SWK_EXPAND_SPLIT_BF16") ? atoi(getenv("SWK_EXPAND_SPLIT_BF16")) : 3;
-int g_conv1x1_ring = 0;          // A/B knob: 0 = 16-wave workgroups, column blocks of the wide expands split over two waves; 1 = the
+int g_squeeze_split_bf16 = getenv("SWK_SQUEEZE_SPLIT_BF16") ? atoi(getenv("SWK_SQUEEZE_SPLIT_BF16")) != 0 : 1;
+int g_conv1x1_ring = 0;         // A/B knob: 0 = 16-wave workgroups, column blocks of the wide expands split over two waves; 1 = the
                                  // first layout (8 waves, every wave all column blocks, activation ring as deep as fits)
 
 // knob 1 = 3 (the default): the kernel each Fire expand1x1 shape takes, as a value of the knob
 static int expand1x1_default_route(int cin)
 {
     return cin == 16 || cin == 32 || cin == 48 || cin == 64 ? 2 : 0;
+}
+
+// knob 4 = 1 (the default): the squeeze shapes that take k_squeeze1x1_bf16s (a shape that does not win its measurement leaves this list)
+static bool squeeze1x1_default_route(int cin, int cout)
+{
+    return (cin == 256 && cout == 48) || (cin == 384 && (cout == 48 || cout == 64));
 }
 
 #define SWK_C1_ARGS s, src, rows, cr, cin, h, w, wgt, bias, cout, pl
@@ -234,6 +245,10 @@ int32_t swk_nhwc_conv1x1_bias_relu_place(void *stream, const float *src, int32_t
                      : route == 1 ? launch_expand1x1_split_bf16(s, src, rows, cr, cin, h, w, weight, bias, cout, pl) : SWK_ERR_ARG;
         if (rc != SWK_ERR_ARG) return rc;
     }
+    if (g_squeeze_split_bf16 && squeeze1x1_default_route(cin, cout)) {          // the wide plain squeezes: again per shape, never per size
+        const int rc = launch_squeeze1x1_split_bf16(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
+        if (rc != SWK_ERR_ARG) return rc;
+    }
     switch ((cout + 31) / 32) {
     case 1: return launch_conv1x1<1>(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
     case 2: return launch_conv1x1<2>(s, src, rows, cr, cin, h, w, weight, bias, cout, pl);
@@ -251,8 +266,11 @@ int32_t swk_nhwc_conv1x1_bias_relu_place(void *stream, const float *src, int32_t
 // bits); 2 = the split-bf16 kernel with its weights in registers (the same bits as 1); 3, the default: each shape's own choice of these.
 // knob 2: workgroup layout of the split-bf16 Winograd expands (cnn_wino3x3_bf16s.hip; results do not depend on it): 0 = each shape's default,
 // 1 = one column block and two tile groups per wave for every shape, 2 = the shared-filter layout for every shape that has one.
+// knob 4, conv1 (cnn_conv1.hip) and the wide plain squeezes (256 -> 48, 384 -> 48, 384 -> 64): 0 = the float32 kernels; 1, the default: each shape's own choice, the
+// split-bf16 kernel of cnn_squeeze_bf16.hip (float32-accurate, another summation order).  (Knob 3 does not exist and is refused.)
 int32_t swk_set_cnn_tuning(int32_t knob, int32_t value)
 {
+    if (knob == 4 && (value == 0 || value == 1)) { swk::g_squeeze_split_bf16 = value; return SWK_OK; }
     if (knob == 0 && (value == 0 || value == 1)) { swk::g_conv1x1_ring = value; return SWK_OK; }
     if (knob == 1 && value >= 0 && value <= 3) { swk::g_expand_split_bf16 = value; return SWK_OK; }
     if (knob == 2 && value >= 0 && value <= 2) { swk::g_wino_bf16s_layout = value; return SWK_OK; }

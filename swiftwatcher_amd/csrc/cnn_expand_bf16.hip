@@ -35,17 +35,6 @@
 
 namespace swk {
 
-__device__ __forceinline__ void split3(const float4 lo, const float4 hi, bf16x8 &p1, bf16x8 &p2, bf16x8 &p3)
-{
-    const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 a, b, c;
-        split3(v[j], a, b, c);
-        p1[j] = a; p2[j] = b; p3[j] = c;
-    }
-}
-
 // NBLK column blocks of 32 output channels; KS = cin / 16 k-steps; CS waves share a row tile (each NBLK / CS column blocks); NWV waves.
 template <int NBLK, int KS, int CS, int NWV>
 __global__ __launch_bounds__(64 * NWV) void k_expand1x1_bf16s(const float *__restrict__ src, int64_t rows, int sh, int sw, int crop_y, int crop_x,
