@@ -174,7 +174,14 @@ int32_t swk_device_read(swk_ctx *ctx, const void *src_device, void *dst_host, in
  * Replaces, for a batch of windows, FrameQueue.preprocess_queue + segment_queue
  * (data_structures.py:171-217): crop -> gray -> RPCA/IALM -> bilateral -> to-zero
  * threshold -> 3x3 grey opening -> connected components -> region properties.
- * Windows are independent (no state is carried between them). */
+ * Windows are independent (no state is carried between them).
+ * Frames per call: nwin * n <= 2^24 over all groups (SWK_ERR_ARG above); the image stages split the frames into launches of 32768.
+ * Windows per call: the IALM kernels put the window in the grid's y extent and do not split it, so the windows of one IALM
+ * (sub-)batch -- all windows of swk_batch_run; in a groups call the groups whose ROI has at least n pixels together, and each group
+ * below that alone -- may number at most hipDeviceAttributeMaxGridDimY of the context's device (65536 on the MI355X; read once when the
+ * context is made, swk_debug_max_windows in swk_debug.h reports it).  A call above it returns SWK_ERR_CAPACITY before anything is
+ * allocated, copied or launched, names the limit in swk_last_error, and leaves the context usable.  (A device that reported 2^24 or
+ * more would make the rule unreachable behind the frame rule.) */
 int32_t swk_batch_run(swk_ctx *ctx, const swk_input *in, const swk_params *p, swk_output *out);
 /* Several groups of windows in ONE call.  A group is what one swk_batch_run call takes: one video's windows with its own frames
  * pointer, mem, channels, nwin, Hc, Wc, x0, y0, frame_stride and row_stride.  Every group has the same n.  outs[g] receives group
@@ -431,7 +438,8 @@ int32_t swk_grey_open3x3_u8(swk_ctx *ctx, const uint8_t *src, int32_t count, int
 int32_t swk_grey_open_u8(swk_ctx *ctx, const uint8_t *src, int32_t count, int32_t H, int32_t W, int32_t kh, int32_t kw, uint8_t *dst);
 /* resize_frame (image_filtering.py:206-212): cv2.resize(frame, (dW, dH)) = INTER_LINEAR on 8-bit pixels, [count][H][W][channels] ->
  * [count][dH][dW][channels].  PARITY UNPINNED (OpenCV 4.1.0's generic 8u arithmetic restated); dead code in the reference (both call
- * sites are commented out, data_structures.py:179-181), kept for the completeness of the module's surface. */
+ * sites are commented out, data_structures.py:179-181), kept for the completeness of the module's surface.  SWK_ERR_CAPACITY: more than
+ * 65535 frames in one call (the kernel does not split them). */
 int32_t swk_resize_linear_u8(swk_ctx *ctx, const uint8_t *src, int32_t count, int32_t H, int32_t W, int32_t channels, int32_t dH, int32_t dW,
                              uint8_t *dst);
 /* cc_labeling (image_filtering.py:325-329) before the uint8 cast: int32 labels, and the

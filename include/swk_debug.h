@@ -157,6 +157,16 @@ int32_t swk_debug_filter_fused(swk_ctx *ctx, const uint8_t *src, int32_t count, 
 int32_t swk_debug_ccl_frame_props(swk_ctx *ctx, const uint8_t *opened, int32_t count, int32_t H, int32_t W, int32_t connectivity,
                                   int32_t label_order, int32_t seg_cap, uint8_t *labels, swk_segment *segs, int32_t *nseg);
 
+/* Labelling route of swk_ccl_u8, swk_batch_run and swk_batch_run_groups: on = every frame size takes the multi-kernel labeller
+ * (csrc/ccl.hip: k_ccl_init / union / flatten / wordprefix / label through launch_ccl, and k_props* through launch_regionprops where a
+ * batch call wants records), which otherwise only runs for frames the one-workgroup kernel does not take; 0 (default) = each frame size's
+ * own route.  swk_debug_ccl_frame_props is unaffected.  Results never depend on it: the tests run the small pattern frames and more
+ * than 32768 frames through the path that way. */
+int32_t swk_debug_force_ccl_multi_kernel(swk_ctx *ctx, int32_t on);
+/* The largest window count of one IALM (sub-)batch that the context's device takes (swk.h, "Windows per call"): its grid y extent,
+ * hipDeviceAttributeMaxGridDimY, read once when the context is made.  Negative: error. */
+int32_t swk_debug_max_windows(swk_ctx *ctx);
+
 /* White-box hook of the window tracker's tests: after skip_frames more frames, the next frame that swk_track_window steps takes
  * col4row[n] (n = its previous plus its current segments, each entry in [0, n)) instead of the solver's assignment -- the one way to an
  * assignment that leaves a current segment without a status (SWK_ERR_TRACK_STATUS), which no optimal solver returns.  Used up by that

@@ -231,6 +231,8 @@ _SIGS = {
     "swk_debug_resize_table": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "swk_debug_filter_fused": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                                 ctypes.c_int64, ctypes.POINTER(Params)] + [ctypes.c_void_p] * 4),
+    "swk_debug_force_ccl_multi_kernel": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_int32]),
+    "swk_debug_max_windows": (ctypes.c_int32, [ctypes.c_void_p]),
     "swk_debug_ccl_frame_props": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int32] * 6 + [ctypes.c_void_p] * 3),
     "swk_last_eig_sweeps": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_void_p]),
     "swk_set_norm_speculation": (ctypes.c_int32, [ctypes.c_void_p, ctypes.c_double]),
@@ -1162,6 +1164,18 @@ class Context:
         self._check(self._lib.swk_debug_ccl_frame_props(self._h, _ptr(s), s.shape[0], s.shape[1], s.shape[2], int(connectivity),
                                                         int(label_order), int(seg_cap), _ptr(lab), _ptr(segs), _ptr(nseg)))
         return lab, segs, nseg
+
+    def force_ccl_multi_kernel(self, on=True):
+        """swk_debug_force_ccl_multi_kernel: ccl_u8 and the batch calls label every frame size by the multi-kernel path (results never
+        depend on it)."""
+        self._check(self._lib.swk_debug_force_ccl_multi_kernel(self._h, int(bool(on))))
+
+    def max_windows(self):
+        """swk_debug_max_windows: the largest window count of one IALM (sub-)batch the device takes (its grid y extent)."""
+        v = int(self._lib.swk_debug_max_windows(self._h))
+        if v < 0:
+            self._check(v)
+        return v
 
     def regionprops_u8(self, labels, seg_cap=255):
         s, single = self._planes(labels)

@@ -64,6 +64,8 @@ struct swk_ctx {
     double norm_spec = 256.0;      // M-state pass: ||Z|| every other iteration while above 256 x tol (<= 0: every iteration)
     int sparse_backoff = 0, norm_backoff = 0;   // batches for which a guess stays off after it failed (same video, same behaviour)
     int eig_method = 0;                  // 0 Newton-Schulz (MFMA), 1 Jacobi
+    int max_grid_y = 65535;              // hipDeviceAttributeMaxGridDimY of the device: the IALM kernels put the window in blockIdx.y, unsplit
+    bool force_ccl_multi = false;        // swk_debug_force_ccl_multi_kernel: every frame size takes launch_ccl (+ launch_regionprops)
     hipEvent_t ev_poll[2] = {nullptr, nullptr};   // the host polls convergence two iterations late (ialm_chain)
     std::vector<int32_t> last_stage;     // staging route of each group of the last batch call (host_stage_plan's kind; -1: a device group)
     std::vector<IalmWin> last_hw;        // host copy of the last batch's per-window IALM state (account_iters): diagnostics
@@ -98,6 +100,18 @@ int fail(swk_ctx *ctx, int code, const char *msg)
 {
     if (ctx) ctx->err = msg;
     return code;
+}
+
+// The IALM kernels put the window in blockIdx.y and do not split it (include/swk.h, "Windows per call"): a call with more windows in
+// one IALM (sub-)batch than the device's grid y extent is refused before anything is allocated, copied or launched.
+int check_windows(swk_ctx *ctx, int64_t nwin)
+{
+    if (nwin <= ctx->max_grid_y) return SWK_OK;
+    char buf[160];
+    snprintf(buf, sizeof buf, "too many windows in one call: %lld, the device takes %d at most (grid y extent; windows are not chunked)",
+             (long long)nwin, ctx->max_grid_y);
+    ctx->err = buf;
+    return SWK_ERR_CAPACITY;
 }
 
 int need(swk_ctx *ctx, Slot s, size_t bytes, void **out)
@@ -710,6 +724,7 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
     size_t total = 0;                     // stage-plane bytes: sub-batches one after the other, each 256-byte aligned
     int sub_first = 0;                    // windows in sub-batch order
     for (Sub &sb : subs) {
+        if (int rcw = check_windows(ctx, sb.nwin)) return rcw;
         Pmax = sb.P > Pmax ? sb.P : Pmax;
         if ((int64_t)fpad_max * ialm_pstride(sb.P) >= (1ll << 28))
             return fail(ctx, SWK_ERR_ARG, "window too large: frames x padded ROI pixels must stay below 2^28");
@@ -788,7 +803,7 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
     std::vector<char> fused(G);
     for (int g = 0; g < G; ++g) {
         const int H = groups[g].Hc, W = groups[g].Wc, Fg = groups[g].nwin * n;
-        fused[g] = ccl_frame_supported(H, W);
+        fused[g] = !ctx->force_ccl_multi && ccl_frame_supported(H, W);
         Pp = std::max(Pp, ccl_padded(H, W));
         words = std::max(words, ccl_words(H, W));
         if (fused[g]) lds = std::max(lds, ccl_frame_lds_bytes(H, W));
@@ -1060,8 +1075,14 @@ int32_t swk_ctx_create(int32_t device, int32_t max_windows, int32_t max_n, int32
         return SWK_ERR_NOGPU;
     }
     if (hipSetDevice(device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return SWK_ERR_HIP; }
+    int grid_y = 0;
+    if (hipDeviceGetAttribute(&grid_y, hipDeviceAttributeMaxGridDimY, device) != hipSuccess || grid_y < 1) {
+        g_create_error = "hipDeviceGetAttribute(hipDeviceAttributeMaxGridDimY) failed";
+        return SWK_ERR_HIP;
+    }
     swk_ctx *ctx = new swk_ctx();
     ctx->device = device;
+    ctx->max_grid_y = grid_y;
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
         hipHostMalloc((void **)&ctx->h_active, 256, hipHostMallocDefault) != hipSuccess) {
         g_create_error = "stream / pinned memory creation failed";
@@ -1286,6 +1307,15 @@ int32_t swk_prof_redo_windows(swk_ctx *ctx, int64_t *windows)
     *windows = ctx->redo_windows;
     return SWK_OK;
 }
+
+int32_t swk_debug_force_ccl_multi_kernel(swk_ctx *ctx, int32_t on)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    ctx->force_ccl_multi = on != 0;
+    return SWK_OK;
+}
+
+int32_t swk_debug_max_windows(swk_ctx *ctx) { return ctx ? ctx->max_grid_y : SWK_ERR_ARG; }
 
 int32_t swk_set_eig_method(swk_ctx *ctx, int32_t method)
 {
@@ -1813,6 +1843,7 @@ static int debug_stage_and_start(swk_ctx *ctx, const uint8_t *X, int nwin, int n
 {
     if (!ctx || !X || nwin < 1 || n < 1 || n > kMaxNWide || P < 1 || !(lmbda > 0.0)) return fail(ctx, SWK_ERR_ARG, "bad argument");
     if ((int64_t)nwin * n * P >= (1ll << 31)) return fail(ctx, SWK_ERR_ARG, "too many pixels in one call");
+    if (int rcw = check_windows(ctx, nwin)) return rcw;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t elems = (size_t)nwin * n * P;
     uint8_t *dX, *dS;
@@ -1971,6 +2002,8 @@ int32_t swk_resize_linear_u8(swk_ctx *ctx, const uint8_t *src, int32_t count, in
 {
     if (!ctx || !src || !dst || count < 1 || H < 1 || W < 1 || dH < 1 || dW < 1 || channels < 1 || channels > 4)
         return fail(ctx, SWK_ERR_ARG, "bad argument");
+    // (k_resize_linear_u8 puts the frame in the grid's z extent and does not split it)
+    if (count > 65535) return fail(ctx, SWK_ERR_CAPACITY, "too many frames in one call (65535 at most)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // per-axis tables (OpenCV 4.1.0 resizeGeneric_ for INTER_LINEAR, 8u: float32 coordinates, 11-bit weights)
     std::vector<int> idx((size_t)dW + dH);
@@ -2019,7 +2052,7 @@ int32_t swk_ccl_u8(swk_ctx *ctx, const uint8_t *src, int32_t count, int32_t H, i
     int rc = ensure_ccl(ctx, count, H, W, &cb);
     if (rc) return rc;
     HIPCHK(ctx, hipMemcpyAsync(din, src, px, hipMemcpyHostToDevice, ctx->stream));
-    if (ccl_frame_supported(H, W))
+    if (!ctx->force_ccl_multi && ccl_frame_supported(H, W))
         launch_ccl_frame(ctx->stream, din, count, H, W, connectivity, label_order, cb, dlab, nullptr, false, 1, nullptr, nullptr);
     else
         launch_ccl(ctx->stream, din, count, H, W, connectivity, label_order, cb, dlab, nullptr);

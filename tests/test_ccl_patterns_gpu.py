@@ -89,6 +89,27 @@ def test_ccl_multi_kernel_path(ctx, orc, shape, conn, order):
         np.testing.assert_array_equal(lab, ref, err_msg=case.name)
 
 
+@pytest.fixture()
+def forced(ctx):
+    """the context with the multi-kernel labeller forced for every frame size (swk_debug_force_ccl_multi_kernel), for one test"""
+    ctx.force_ccl_multi_kernel(True)
+    yield ctx
+    ctx.force_ccl_multi_kernel(False)
+
+
+@pytest.mark.parametrize("conn,order", PAIRS, ids=PAIR_IDS)
+@pytest.mark.parametrize("case", FAMILIES, ids=lambda c: c.name)
+def test_ccl_single_frames_multi_kernel_forced(forced, orc, case, conn, order):
+    """the pattern families through k_ccl_init / union / flatten / wordprefix / label, which otherwise only meets frames too large
+    for one workgroup"""
+    n, lab = forced.ccl_u8(case.img, conn, order)
+    nref, ref = orc.ccl_u8(case.img, conn, order)
+    want = case.comps8 if conn == 8 else case.comps4
+    assert nref == want or want is None
+    assert n == nref
+    np.testing.assert_array_equal(lab, ref)
+
+
 # ------------------------------------------------------------------ stage level: swk_regionprops_u8
 def _check_regionprops(ctx, orc, lab8, name):
     want = orc_seg_tuples(orc.regionprops_u8(lab8))
@@ -218,6 +239,14 @@ def test_batch_either_side_of_the_run_cap(ctx, orc):
     assert any(900 <= r <= cp.RUN_CAP for _, r, _ in regimes) and any(cp.RUN_CAP < r <= 1200 for _, r, _ in regimes)
     res = ctx.batch_run(_roi("cap_212x424"), 1, 21)
     _check_call(ctx, orc, res, _oracle("cap_212x424"), what="cap_212x424")
+
+
+def test_batch_either_side_of_the_run_cap_multi_kernel_forced(forced, orc):
+    """case c's window with launch_ccl + launch_regionprops in the batch call: 341 / 342 / 400 components a frame, so the u8 labels
+    wrap and k_props unites label k with label 256 + k"""
+    res = forced.batch_run(_roi("cap_212x424"), 1, 21)
+    forced.force_ccl_multi_kernel(False)          # (_check_call's own swk_ccl_u8 takes the one-workgroup kernel: two routes, one result)
+    _check_call(forced, orc, res, _oracle("cap_212x424"), what="cap_212x424 forced")
 
 
 @pytest.mark.parametrize("name,residue,fallback", [("dense_212x424", 0, True), ("dense_211x422", 2, True), ("dense_211x423", 1, True),
