@@ -243,27 +243,7 @@ int ensure_ccl(swk_ctx *ctx, int F, int H, int W, CclBuffers *b)
     return SWK_OK;
 }
 
-// ---- host input -> device (swk_batch_run's copy strategies; swk_batch_run_groups stages its host groups the same way) ----
-struct HostStage { int kind; size_t bytes; };
-enum { ST_DENSE = 0, ST_WHOLE, ST_ROWS, ST_2D };
-
-HostStage host_stage_plan(const swk_input *in)
-{
-    const int F = in->nwin * in->n, H = in->Hc, W = in->Wc;
-    const size_t plane = (size_t)F * H * W;
-    const int64_t fs = in->frame_stride, rs = in->row_stride, afs = fs < 0 ? -fs : fs;
-    const int x0 = in->x0, y0 = in->y0;
-    const size_t rowb = (size_t)W * in->channels;
-    if (x0 == 0 && (size_t)rs == rowb && fs == (int64_t)H * rs) return {ST_DENSE, plane * in->channels};
-    if (rs >= (int64_t)(x0 + W) * in->channels && rs % in->channels == 0 && afs % rs == 0 && afs >= (int64_t)(y0 + H) * rs &&
-        (size_t)F * (size_t)afs <= 2 * plane * in->channels) {
-        const size_t whole = (size_t)F * (size_t)afs;
-        return {ST_WHOLE, whole > plane * in->channels ? whole : plane * in->channels};
-    }
-    if (x0 == 0 && (size_t)rs == rowb) return {ST_ROWS, plane * in->channels};
-    return {ST_2D, plane * in->channels};
-}
-
+// ---- host input -> device (the copy strategy comes from host_stage_plan, batch_plan.h) ----
 // Copies `in` to roi and says where the kernels find it there: frame 0 at *dframes, strides *fs / *rs, ROI origin (*x0, *y0).
 int host_stage_copy(swk_ctx *ctx, const swk_input *in, const HostStage &st, uint8_t *roi, const uint8_t **dframes, int64_t *fs_out,
                     int64_t *rs_out, int *x0_out, int *y0_out)
@@ -665,148 +645,71 @@ int copy_out(swk_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spi
 }
 
 // ---- the batch driver of swk_batch_run (one group) and swk_batch_run_groups (G groups) ----------------
-// A group is one video's windows, with its own frames, memory, ROI and strides.  Every frame's u8 stage planes start at an offset
-// of their own and hold its H x W pixels.  The IALM runs once over all groups whose ROI has at least n pixels, on X planes zero-padded
-// to the largest of those ROIs (Pmax): zero pixel rows change neither X^T X nor ||X||_F nor max|X|, and their rows of A, E, Y and S
-// stay zero.  A group with fewer pixels than frames runs as a sub-batch of its own at its true P (there svp = min(P, n),
-// image_filtering.py:285, so padding would change the result).  One group is the plan's degenerate case -- one sub-batch, pitch = P,
-// offset 0 -- and takes the uniform kernels, working in the caller's device buffers where it may; several groups take the
-// per-frame geometry kernels, driven by descriptor tables, on library buffers.
+// plan_batch (batch_plan.h) turns (groups, outs) into a BatchPlan on the host: sub-batches, placement, staging, record flags and the
+// layout of the descriptor tables.  run_batch refuses what the parameters, the plan or the device rule out, reserves every buffer
+// (batch_buffers), then runs the stages below once, in order.  Each stage owns its fork -- one group: the uniform kernels, in the
+// caller's device buffers where it may; several groups: the per-frame geometry kernels, driven by the descriptor tables, on library
+// buffers -- and its profiling family.
 std::array<uint8_t *, 6> out_planes(const swk_output &o) { return {o.gray, o.rpca, o.bilateral, o.thresh, o.opened, o.labels}; }
 
-int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p, swk_output *outs)
+// What the batch path's filter (and, with `labels`, its labeller) cannot run, by the parameters alone: the message, or null
+const char *params_refusal(const swk_params *p, bool labels)
 {
-    if (p->open_kh != 3 || p->open_kw != 3) return fail(ctx, SWK_ERR_ARG, "only the (3,3) opening window is implemented");
-    if (p->connectivity != 4 && p->connectivity != 8) return fail(ctx, SWK_ERR_ARG, "connectivity must be 4 or 8");
-    // the fused filter kernel has one instantiation per radius 1..4; refused here, before any buffer or launch (ensure_bilateral's own check
-    // comes after the buffers)
-    if (bilateral_radius(p->bil_d, p->bil_sigma_space) > 4) return fail(ctx, SWK_ERR_ARG, "bilateral diameter > 9 is not supported");
-    const int n = groups[0].n;
-    int64_t nwin64 = 0;
-    for (int g = 0; g < G; ++g) {
-        const swk_input *in = &groups[g];
-        const swk_output *out = &outs[g];
-        if (!in->frames) return fail(ctx, SWK_ERR_ARG, "null frames");
-        if (in->nwin < 1 || in->n < 1 || in->Hc < 1 || in->Wc < 1) return fail(ctx, SWK_ERR_ARG, "empty batch");
-        if (in->n != n) return fail(ctx, SWK_ERR_ARG, "every group must have the same frames per window");
-        if (in->channels != 1 && in->channels != 3) return fail(ctx, SWK_ERR_ARG, "channels must be 1 or 3");
-        if (in->n > kMaxNWide) return fail(ctx, SWK_ERR_ARG, "frames per window must be <= 128");
-        if (out->segs && (out->seg_cap < 1 || out->seg_cap > 255)) return fail(ctx, SWK_ERR_ARG, "seg_cap must be in 1..255");
-        if (in->Hc < 4 || in->Wc < 4) return fail(ctx, SWK_ERR_ARG, "ROI must be at least 4x4");
-        nwin64 += in->nwin;
-    }
-    if (nwin64 * n > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "too many frames in one call");
-    const int nwin = (int)nwin64, F = nwin * n;
-    const bool single = G == 1;
+    if (p->open_kh != 3 || p->open_kw != 3) return "only the (3,3) opening window is implemented";
+    if (labels && p->connectivity != 4 && p->connectivity != 8) return "connectivity must be 4 or 8";
+    // the fused filter kernel has one instantiation per radius 1..4 (ensure_bilateral's own check comes after the buffers)
+    if (bilateral_radius(p->bil_d, p->bil_sigma_space) > 4) return "bilateral diameter > 9 is not supported";
+    return nullptr;
+}
 
-    // ---- sub-batches of the IALM: [0] = every group with P >= n, padded to its largest P; then one per group with P < n ----
-    struct Sub { std::vector<int> gs; int P = 0, nwin = 0, w0 = 0; int64_t off = 0; bool A = false, E = false; };
-    std::vector<Sub> subs(1);
-    int Pmax = 0, Hmax = 0, Wmax = 0;
-    for (int g = 0; g < G; ++g) {
-        const int P = groups[g].Hc * groups[g].Wc;
-        Hmax = std::max(Hmax, groups[g].Hc);
-        Wmax = std::max(Wmax, groups[g].Wc);
-        Sub *sb = &subs[0];
-        if (P < n) { subs.emplace_back(); sb = &subs.back(); }
-        sb->gs.push_back(g);
-        sb->P = P > sb->P ? P : sb->P;
-        sb->nwin += groups[g].nwin;
-        sb->A = sb->A || outs[g].A; sb->E = sb->E || outs[g].E;
-    }
-    if (subs[0].gs.empty()) subs.erase(subs.begin());
-    std::vector<int> sub_of(G);
-    for (size_t k = 0; k < subs.size(); ++k)
-        for (int g : subs[k].gs) sub_of[g] = (int)k;
-    // capacity: run_ialm's limit on the padded plane (at the wider fpad of the two pass families: its reruns may take the other),
-    // checked here so that a refused call launches nothing
-    const int fpad_max = std::max(ialm_fpad(true, n), ialm_fpad(false, n));
-    size_t total = 0;                     // stage-plane bytes: sub-batches one after the other, each 256-byte aligned
-    int sub_first = 0;                    // windows in sub-batch order
-    for (Sub &sb : subs) {
-        if (int rcw = check_windows(ctx, sb.nwin)) return rcw;
-        Pmax = sb.P > Pmax ? sb.P : Pmax;
-        if ((int64_t)fpad_max * ialm_pstride(sb.P) >= (1ll << 28))
-            return fail(ctx, SWK_ERR_ARG, "window too large: frames x padded ROI pixels must stay below 2^28");
-        sb.off = (int64_t)total;
-        total += ((size_t)sb.nwin * n * sb.P + 255) & ~(size_t)255;
-        sb.w0 = sub_first;
-        sub_first += sb.nwin;
-    }
-    // region records: one stride for the call (the largest cap), each group's own cap where it counts
-    bool want_props = false, seg_last = true, host_total = true;
-    int capmax = 1;
-    for (int g = 0; g < G; ++g) {
-        want_props = want_props || outs[g].segs || outs[g].nseg;
-        if (outs[g].segs && outs[g].seg_cap > capmax) capmax = outs[g].seg_cap;
-        seg_last = seg_last && outs[g].segs && groups[g].channels == 3;
-        host_total = host_total && outs[g].mem == SWK_MEM_HOST && outs[g].nseg;
-    }
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    int rc;
-    ctx->last.valid = false;
+struct BatchBuffers {
+    uint8_t *roi = nullptr;                          // host groups' staged frames
+    uint8_t *pl[6] = {};                             // stage planes: gray (X), sparse image (S), bilateral, threshold, opened, labels
+    double *pn = nullptr;                            // host outputs' A / E staging, (pixels, frames) layout
+    swk_segment *dsegs = nullptr; int32_t *dnseg = nullptr;
+    CclBuffers cb{};
+    size_t lds = 0;                                  // the largest ccl_frame_lds_bytes of the fused groups (0: none is)
+    std::vector<char> fused;                         // per group: its frames take the one-workgroup labeller
+    uint8_t *tmp_in = nullptr, *tmp_out = nullptr;   // several groups: dense copy of an unfused group's opened / label planes
+    uint8_t *dtab = nullptr;                         // several groups: the descriptor tables
+};
 
-    // ---- every buffer first (a later NEED may not move one a queued kernel uses) ----
-    std::vector<HostStage> st(G);
-    std::vector<size_t> roi_off(G, 0);
-    size_t roi_bytes = 0;
-    for (int g = 0; g < G; ++g)
-        if (groups[g].mem == SWK_MEM_HOST) {
-            st[g] = host_stage_plan(&groups[g]);
-            roi_off[g] = roi_bytes;
-            roi_bytes += (st[g].bytes + 255) & ~(size_t)255;
-        }
-    ctx->last_stage.resize(G);
-    for (int g = 0; g < G; ++g) ctx->last_stage[g] = groups[g].mem == SWK_MEM_HOST ? st[g].kind : -1;
-    size_t pn_bytes = 0;
-    std::vector<size_t> pn_off(G, 0);
-    for (int g = 0; g < G; ++g)
-        if ((outs[g].A || outs[g].E) && outs[g].mem == SWK_MEM_HOST) {
-            pn_off[g] = pn_bytes;
-            pn_bytes += (size_t)groups[g].nwin * n * groups[g].Hc * groups[g].Wc * 8;
-        }
-    uint8_t *roi = nullptr;
-    if (roi_bytes) NEED(ctx, SL_ROI, roi_bytes, roi);
-    // stage planes: gray (X), sparse image (S), bilateral, threshold, opened, labels.  One group works in the caller's device buffers
-    // (mem = SWK_MEM_DEVICE or planes_on_device) -- but a gray plane whose size is not a whole number of dwords stays in the library's
-    // padded buffer: k_gram_u8 reads it in dwords; the caller's copy is made at the end
+// Every buffer of a batch call, before its first launch: a later NEED may not move one a queued kernel uses, so no stage calls NEED.
+int batch_buffers(swk_ctx *ctx, const BatchPlan &plan, const swk_input *groups, const swk_output *outs, BatchBuffers *buf)
+{
+    const int G = (int)plan.grp.size(), n = plan.n, F = plan.F;
+    const bool single = plan.single;
+    if (plan.roi_bytes) NEED(ctx, SL_ROI, plan.roi_bytes, buf->roi);
+    // One group works in the caller's device buffers (mem = SWK_MEM_DEVICE or planes_on_device) -- but a gray plane whose size is not
+    // a whole number of dwords stays in the library's padded buffer: k_gram_u8 reads it in dwords; the caller's copy is made at the end
     const bool in_place = single && (outs[0].mem == SWK_MEM_DEVICE || outs[0].planes_on_device != 0);
     const Slot plane_slot[6] = {SL_X, SL_S, SL_BIL, SL_THR, SL_OPEN, SL_LAB8};
-    uint8_t *pl[6] = {};
     for (int i = 0; i < 6; ++i) {
         bool wanted = i != 2 && i != 3;          // the filter writes the bilateral and threshold images only when asked for
         for (int g = 0; g < G; ++g) wanted = wanted || out_planes(outs[g])[i];
         if (!wanted) continue;
         uint8_t *mine = in_place ? out_planes(outs[0])[i] : nullptr;
         if (i == 0 && ((size_t)F * groups[0].Hc * groups[0].Wc) % 4) mine = nullptr;
-        if (!mine) NEED(ctx, plane_slot[i], total + (i == 0 ? 4 : 0), mine);
-        pl[i] = mine;
+        if (!mine) NEED(ctx, plane_slot[i], plan.total + (i == 0 ? 4 : 0), mine);
+        buf->pl[i] = mine;
     }
-    uint8_t *const dX = pl[0], *const dS = pl[1], *const dBil = pl[2], *const dThr = pl[3], *const dOpen = pl[4], *const dLab = pl[5];
-    double *pn = nullptr;
-    if (pn_bytes) NEED(ctx, SL_PN, pn_bytes, pn);
-    // A or E of group g, (pixels, frames) layout: the caller's device buffer, or the group's part of the host outputs' staging buffer
-    auto ae_dst = [&](int g, int which) {
-        double *dst = which == 0 ? outs[g].A : outs[g].E;
-        return dst && outs[g].mem == SWK_MEM_HOST ? pn + pn_off[g] / 8 : dst;
-    };
-    swk_segment *dsegs = nullptr; int32_t *dnseg = nullptr;
-    if (want_props) {
+    if (plan.pn_bytes) NEED(ctx, SL_PN, plan.pn_bytes, buf->pn);
+    if (plan.want_props) {
         const bool rec_in_place = single && outs[0].mem == SWK_MEM_DEVICE;          // one group's device records are written in place
-        if (rec_in_place && outs[0].segs) dsegs = outs[0].segs; else NEED(ctx, SL_SEGS, (size_t)F * capmax * sizeof(swk_segment), dsegs);
-        if (rec_in_place && outs[0].nseg) dnseg = outs[0].nseg; else NEED(ctx, SL_NSEG, (size_t)F * 4, dnseg);
+        if (rec_in_place && outs[0].segs) buf->dsegs = outs[0].segs;
+        else NEED(ctx, SL_SEGS, (size_t)F * plan.capmax * sizeof(swk_segment), buf->dsegs);
+        if (rec_in_place && outs[0].nseg) buf->dnseg = outs[0].nseg; else NEED(ctx, SL_NSEG, (size_t)F * 4, buf->dnseg);
     }
     // labelling: the one-workgroup-per-frame kernel for every group that fits it, the multi-kernel path for the others (several
     // groups: on a dense copy of the group's planes)
-    size_t lds = 0, Pp = 1, words = 1, ccl_F = 1, ccl_Pp = 1, ccl_words_ = 1, tmp_bytes = 16;
-    std::vector<char> fused(G);
+    size_t Pp = 1, words = 1, ccl_F = 1, ccl_Pp = 1, ccl_words_ = 1, tmp_bytes = 16;
+    buf->fused.resize(G);
     for (int g = 0; g < G; ++g) {
         const int H = groups[g].Hc, W = groups[g].Wc, Fg = groups[g].nwin * n;
-        fused[g] = !ctx->force_ccl_multi && ccl_frame_supported(H, W);
+        buf->fused[g] = !ctx->force_ccl_multi && ccl_frame_supported(H, W);
         Pp = std::max(Pp, ccl_padded(H, W));
         words = std::max(words, ccl_words(H, W));
-        if (fused[g]) lds = std::max(lds, ccl_frame_lds_bytes(H, W));
+        if (buf->fused[g]) buf->lds = std::max(buf->lds, ccl_frame_lds_bytes(H, W));
         else {
             ccl_F = std::max(ccl_F, (size_t)Fg);
             ccl_Pp = std::max(ccl_Pp, ccl_padded(H, W));
@@ -814,7 +717,7 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
             if (!single) tmp_bytes = std::max(tmp_bytes, (size_t)Fg * H * W);
         }
     }
-    CclBuffers cb{};
+    CclBuffers &cb = buf->cb;
     cb.Pp = (int)Pp;
     cb.words = (int)words;          // (the geometry kernel takes each frame's own)
     NEED(ctx, SL_PARENT, std::max((size_t)F * Pp, ccl_F * ccl_Pp) * 4, cb.parent);
@@ -823,220 +726,261 @@ int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p,
     NEED(ctx, SL_NCOMP, (size_t)F * 4, cb.ncomp);
     NEED(ctx, SL_TABLE, ccl_F * 256 * 8 * 4, cb.table);
     NEED(ctx, SL_SUMS, ccl_F * 256 * 2 * 8, cb.sums);
-    uint8_t *tmp_in = nullptr, *tmp_out = nullptr;
-    if (tmp_bytes > 16) { NEED(ctx, SL_TMP_IN, tmp_bytes, tmp_in); NEED(ctx, SL_TMP_OUT, tmp_bytes, tmp_out); }
-    // several groups: descriptor tables, one upload: windows (gather), frames (filter), frames (labelling), frames (classifier
-    // inputs), windows in sub-batch order (A, then E)
-    const size_t o_win = 0, o_gf = o_win + (((size_t)nwin * sizeof(GroupWin) + 15) & ~(size_t)15);
-    const size_t o_gc = o_gf + (size_t)F * sizeof(FrameGeom), o_sf = o_gc + (size_t)F * sizeof(FrameGeom);
-    const size_t o_pa = o_sf + (size_t)F * sizeof(SegFrame), o_pe = o_pa + (size_t)nwin * sizeof(PnWin);
-    const size_t tab_bytes = o_pe + (size_t)nwin * sizeof(PnWin);
-    uint8_t *dtab = nullptr;
-    if (!single) NEED(ctx, SL_GRP, tab_bytes, dtab);
-    rc = ensure_bilateral(ctx, p->bil_d, p->bil_sigma_color, p->bil_sigma_space);
-    if (rc) return rc;
+    if (tmp_bytes > 16) { NEED(ctx, SL_TMP_IN, tmp_bytes, buf->tmp_in); NEED(ctx, SL_TMP_OUT, tmp_bytes, buf->tmp_out); }
+    if (!single) NEED(ctx, SL_GRP, plan.tab_bytes, buf->dtab);
+    return SWK_OK;
+}
 
-    // ---- inputs: host groups staged one after the other into the ROI buffer ----
-    struct View {
-        const uint8_t *frames; int64_t fs, rs; int x0, y0;
-        int frame_h() const { return (int)((fs < 0 ? -fs : fs) / rs); }
-        int frame_w() const { return (int)(rs / 3); }
-    };
-    std::vector<View> view(G);
-    for (int g = 0; g < G; ++g) {
-        const swk_input *in = &groups[g];
-        View &v = view[g];
+// One batch call: its arguments, plan and buffers, and what a stage leaves for a later one.
+struct Batch {
+    swk_ctx *ctx; const swk_input *groups; int G; const swk_params *p; swk_output *outs;
+    BatchPlan plan;
+    BatchBuffers buf;
+    std::vector<BatchView> view;          // where the kernels find each group's frames
+    std::vector<uint8_t> tab;             // host image of the descriptor tables (uploaded asynchronously: lives until the call's final sync)
+    std::vector<IalmWin> hw_sub;          // window state, sub-batch order
+    IalmRun run{};                        // the last sub-batch's IALM
+};
+
+// A or E of group g, (pixels, frames) layout: the caller's device buffer, or the group's part of the host outputs' staging buffer
+double *ae_dst(const Batch &b, int g, int which)
+{
+    double *dst = which == 0 ? b.outs[g].A : b.outs[g].E;
+    return dst && b.outs[g].mem == SWK_MEM_HOST ? b.buf.pn + b.plan.grp[g].pn_off / 8 : dst;
+}
+
+// inputs: host groups staged one after the other into the ROI buffer
+int batch_inputs(Batch &b)
+{
+    b.view.resize(b.G);
+    for (int g = 0; g < b.G; ++g) {
+        const swk_input *in = &b.groups[g];
+        BatchView &v = b.view[g];
         v = {in->frames, in->frame_stride, in->row_stride, in->x0, in->y0};
         if (in->mem == SWK_MEM_HOST) {
-            Timed t(ctx, SWK_K_COPY);
-            rc = host_stage_copy(ctx, in, st[g], roi + roi_off[g], &v.frames, &v.fs, &v.rs, &v.x0, &v.y0);
+            Timed t(b.ctx, SWK_K_COPY);
+            const int rc = host_stage_copy(b.ctx, in, b.plan.grp[g].stage, b.buf.roi + b.plan.grp[g].roi_off, &v.frames, &v.fs, &v.rs, &v.x0, &v.y0);
             if (rc) return rc;
         }
     }
-    std::vector<int> win0(G + 1, 0);           // first window of each group, call order
-    std::vector<int> swin0(G);                 // ... and sub-batch order
-    std::vector<int64_t> goff(G);              // stage-plane offset of each group's first frame
-    std::vector<int> fill(subs.size(), 0);     // windows of each sub-batch placed so far
-    for (int g = 0; g < G; ++g) {
-        const Sub &sb = subs[sub_of[g]];
-        win0[g + 1] = win0[g] + groups[g].nwin;
-        swin0[g] = sb.w0 + fill[sub_of[g]];
-        goff[g] = sb.off + (int64_t)fill[sub_of[g]] * n * sb.P;
-        fill[sub_of[g]] += groups[g].nwin;
-    }
-    int vec = 4;
-    std::vector<uint8_t> tab(single ? 0 : tab_bytes, 0);          // (uploaded asynchronously: lives until the call's final sync)
-    if (!single) {
-        GroupWin *hwin = (GroupWin *)(tab.data() + o_win);
-        FrameGeom *hgf = (FrameGeom *)(tab.data() + o_gf), *hgc = (FrameGeom *)(tab.data() + o_gc);
-        SegFrame *hsf = (SegFrame *)(tab.data() + o_sf);
-        PnWin *hpa = (PnWin *)(tab.data() + o_pa), *hpe = (PnWin *)(tab.data() + o_pe);
-        for (int g = 0; g < G; ++g) {
-            const swk_input *in = &groups[g];
-            const View &v = view[g];
-            const int H = in->Hc, W = in->Wc, P = H * W, pitch = subs[sub_of[g]].P;
-            if (P % 4 || pitch % 4 || goff[g] % 4) vec = std::min(vec, (P % 2 || pitch % 2 || goff[g] % 2) ? 1 : 2);
-            for (int wl = 0; wl < in->nwin; ++wl) {
-                const int w = win0[g] + wl;
-                GroupWin &d = hwin[w];
-                d.src = v.frames + (int64_t)wl * n * v.fs;
-                d.fs = v.fs; d.rs = v.rs; d.off = goff[g] + (int64_t)wl * n * pitch;
-                d.x0 = v.x0; d.y0 = v.y0; d.H = H; d.W = W; d.channels = in->channels; d.pitch = pitch;
-                const int ws = swin0[g] + wl;
-                const size_t wb = (size_t)wl * n * P;
-                hpa[ws].P = hpe[ws].P = P;
-                if (outs[g].A) hpa[ws].dst = ae_dst(g, 0) + wb;
-                if (outs[g].E) hpe[ws].dst = ae_dst(g, 1) + wb;
-                for (int j = 0; j < n; ++j) {
-                    const int f = w * n + j;
-                    hgf[f] = {H, W, d.off + (int64_t)j * pitch};
-                    hgc[f] = fused[g] ? hgf[f] : FrameGeom{0, 0, 0};
-                    hsf[f].frame = v.frames + ((int64_t)wl * n + j) * v.fs;
-                    hsf[f].rs = v.rs;
-                    hsf[f].frame_h = v.frame_h();
-                    hsf[f].frame_w = v.frame_w();
-                    hsf[f].x0 = v.x0; hsf[f].y0 = v.y0;
-                    hsf[f].cap = outs[g].segs ? outs[g].seg_cap : 1;
-                }
-            }
-        }
-        HIPCHK(ctx, hipMemcpyAsync(dtab, tab.data(), tab_bytes, hipMemcpyHostToDevice, s));
-    }
-    const int H0 = groups[0].Hc, W0 = groups[0].Wc;          // (one group's geometry)
+    return SWK_OK;
+}
 
-    // ---- gray + ROI gather into the (padded) X planes ----
-    {
-        Timed t(ctx, SWK_K_GRAY);
-        if (single) launch_gray(s, view[0].frames, groups[0].channels, view[0].fs, view[0].rs, view[0].x0, view[0].y0, F, H0, W0, p->gray_mode, dX);
-        else launch_gray_groups(s, (const GroupWin *)(dtab + o_win), F, n, Pmax, p->gray_mode, dX);
-    }
+// several groups: the descriptor tables, one upload
+int batch_tables(Batch &b)
+{
+    if (b.plan.single) return SWK_OK;
+    std::vector<BatchAE> ae(b.G);
+    for (int g = 0; g < b.G; ++g) ae[g] = {ae_dst(b, g, 0), ae_dst(b, g, 1)};
+    b.tab.assign(b.plan.tab_bytes, 0);
+    fill_batch_tables(b.plan, b.groups, b.outs, b.view.data(), ae.data(), b.buf.fused.data(), b.tab.data());
+    HIPCHK(b.ctx, hipMemcpyAsync(b.buf.dtab, b.tab.data(), b.plan.tab_bytes, hipMemcpyHostToDevice, b.ctx->stream));
+    return SWK_OK;
+}
 
-    // ---- IALM per sub-batch; its float64 factors leave before the next sub-batch reuses the workspaces ----
-    std::vector<IalmWin> hw_sub;          // window state, sub-batch order
-    IalmRun run{};
-    for (size_t k = 0; k < subs.size(); ++k) {
-        const Sub &sb = subs[k];
+// gray + ROI gather into the (padded) X planes
+void batch_gray(Batch &b)
+{
+    const BatchPlan &pl = b.plan;
+    const swk_input &in = b.groups[0];
+    const BatchView &v = b.view[0];
+    Timed t(b.ctx, SWK_K_GRAY);
+    if (pl.single) launch_gray(b.ctx->stream, v.frames, in.channels, v.fs, v.rs, v.x0, v.y0, pl.F, in.Hc, in.Wc, b.p->gray_mode, b.buf.pl[0]);
+    else launch_gray_groups(b.ctx->stream, (const GroupWin *)(b.buf.dtab + pl.o_win), pl.F, pl.n, pl.Pmax, b.p->gray_mode, b.buf.pl[0]);
+}
+
+// IALM per sub-batch; its float64 factors leave before the next sub-batch reuses the workspaces
+int batch_ialm(Batch &b)
+{
+    swk_ctx *ctx = b.ctx;
+    const BatchPlan &pl = b.plan;
+    const swk_params *p = b.p;
+    hipStream_t s = ctx->stream;
+    const int n = pl.n;
+    for (size_t k = 0; k < pl.subs.size(); ++k) {
+        const BatchSub &sb = pl.subs[k];
         // (several groups: each window's own pixel count, from the scatter table, bounds the accurate first iteration's work)
-        const IalmJob job{dX + sb.off, dS + sb.off, sb.nwin, n, sb.P, single ? nullptr : (const PnWin *)(dtab + o_pa) + sb.w0,
-                          p->lmbda, p->tol, p->maxiter};
-        rc = run_ialm(ctx, job, sb.A, sb.E, &run);
+        const IalmJob job{b.buf.pl[0] + sb.off, b.buf.pl[1] + sb.off, sb.nwin, n, sb.P,
+                          pl.single ? nullptr : (const PnWin *)(b.buf.dtab + pl.o_pa) + sb.w0, p->lmbda, p->tol, p->maxiter};
+        int rc = run_ialm(ctx, job, sb.A, sb.E, &b.run);
         if (rc) return rc;
         for (int which = 0; which < 2; ++which) {
             if (!(which == 0 ? sb.A : sb.E)) continue;
-            const double *planes = which == 0 ? run.A : run.E;
+            const double *planes = which == 0 ? b.run.A : b.run.E;
             {
                 Timed t(ctx, SWK_K_COPY);
-                if (single) launch_planes_to_pn(s, planes, ae_dst(0, which), sb.nwin, n, sb.P, run.pstride, run.fpad);
-                else launch_planes_to_pn_groups(s, planes, (const PnWin *)(dtab + (which == 0 ? o_pa : o_pe)) + sb.w0, sb.nwin, n,
-                                                sb.P, run.pstride, run.fpad);
+                if (pl.single) launch_planes_to_pn(s, planes, ae_dst(b, 0, which), sb.nwin, n, sb.P, b.run.pstride, b.run.fpad);
+                else launch_planes_to_pn_groups(s, planes, (const PnWin *)(b.buf.dtab + (which == 0 ? pl.o_pa : pl.o_pe)) + sb.w0, sb.nwin, n,
+                                                sb.P, b.run.pstride, b.run.fpad);
             }
             for (int g : sb.gs) {
-                double *dst = which == 0 ? outs[g].A : outs[g].E;
-                if (dst && outs[g].mem == SWK_MEM_HOST)
-                    HIPCHK(ctx, hipMemcpyAsync(dst, ae_dst(g, which), (size_t)groups[g].nwin * n * groups[g].Hc * groups[g].Wc * 8,
+                double *dst = which == 0 ? b.outs[g].A : b.outs[g].E;
+                if (dst && b.outs[g].mem == SWK_MEM_HOST)
+                    HIPCHK(ctx, hipMemcpyAsync(dst, ae_dst(b, g, which), (size_t)b.groups[g].nwin * n * b.groups[g].Hc * b.groups[g].Wc * 8,
                                                hipMemcpyDeviceToHost, s));
             }
         }
         // the next sub-batch reuses the window-state slot: this one's state is read now (the last one's after the final sync)
-        if (k + 1 < subs.size()) {
-            rc = read_windows(ctx, run, hw_sub);
-            if (rc) return rc;
-        }
+        if (k + 1 < pl.subs.size() && (rc = read_windows(ctx, b.run, b.hw_sub))) return rc;
     }
+    return SWK_OK;
+}
 
-    // ---- bilateral + threshold + opening ----
-    {
-        Timed t(ctx, SWK_K_FILTER);
-        if (single) launch_filter_fused(s, dS, F, H0, W0, ctx->bil, p->bil_fma, p->thresh, dBil, dThr, dOpen);
-        else launch_filter_fused_geom(s, dS, F, Hmax, Wmax, (const FrameGeom *)(dtab + o_gf), total, ctx->bil, p->bil_fma, p->thresh,
-                                      dBil, dThr, dOpen);
-    }
+// bilateral + threshold + opening
+void batch_filter(Batch &b)
+{
+    swk_ctx *ctx = b.ctx;
+    const BatchPlan &pl = b.plan;
+    uint8_t *const *d = b.buf.pl;
+    Timed t(ctx, SWK_K_FILTER);
+    if (pl.single) launch_filter_fused(ctx->stream, d[1], pl.F, b.groups[0].Hc, b.groups[0].Wc, ctx->bil, b.p->bil_fma, b.p->thresh, d[2], d[3], d[4]);
+    else launch_filter_fused_geom(ctx->stream, d[1], pl.F, pl.Hmax, pl.Wmax, (const FrameGeom *)(b.buf.dtab + pl.o_gf), pl.total, ctx->bil,
+                                  b.p->bil_fma, b.p->thresh, d[2], d[3], d[4]);
+}
 
-    // ---- labels + region properties ----
-    if (want_props) HIPCHK(ctx, hipMemsetAsync(dsegs, 0, (size_t)F * capmax * sizeof(swk_segment), s));
-    if (lds) {
+// labels + region properties: one launch for the fused groups, the multi-kernel path for every other group
+int batch_labels(Batch &b)
+{
+    swk_ctx *ctx = b.ctx;
+    const BatchPlan &pl = b.plan;
+    const BatchBuffers &buf = b.buf;
+    const swk_params *p = b.p;
+    hipStream_t s = ctx->stream;
+    const bool single = pl.single;
+    const int n = pl.n, F = pl.F, capmax = pl.capmax;
+    uint8_t *const dOpen = buf.pl[4], *const dLab = buf.pl[5];
+    if (pl.want_props) HIPCHK(ctx, hipMemsetAsync(buf.dsegs, 0, (size_t)F * capmax * sizeof(swk_segment), s));
+    if (buf.lds) {
         Timed t(ctx, SWK_K_CCL);
-        if (single) launch_ccl_frame(s, dOpen, F, H0, W0, p->connectivity, p->label_order, cb, nullptr, dLab, want_props, capmax, dsegs, dnseg);
-        else launch_ccl_frame_geom(s, dOpen, F, (const FrameGeom *)(dtab + o_gc), lds, vec, p->connectivity, p->label_order, cb, dLab,
-                                   capmax, dsegs, dnseg);
+        if (single) launch_ccl_frame(s, dOpen, F, b.groups[0].Hc, b.groups[0].Wc, p->connectivity, p->label_order, buf.cb, nullptr, dLab,
+                                     pl.want_props, capmax, buf.dsegs, buf.dnseg);
+        else launch_ccl_frame_geom(s, dOpen, F, (const FrameGeom *)(buf.dtab + pl.o_gc), buf.lds, pl.vec, p->connectivity, p->label_order,
+                                   buf.cb, dLab, capmax, buf.dsegs, buf.dnseg);
     }
-    for (int g = 0; g < G; ++g) {
-        if (fused[g]) continue;
-        const int H = groups[g].Hc, W = groups[g].Wc, P = H * W, Fg = groups[g].nwin * n, pitch = subs[sub_of[g]].P;
-        const int f0 = win0[g] * n;
-        CclBuffers gb = cb;
+    for (int g = 0; g < b.G; ++g) {
+        if (buf.fused[g]) continue;
+        const BatchGroup &bg = pl.grp[g];
+        const int H = b.groups[g].Hc, W = b.groups[g].Wc, P = H * W, Fg = b.groups[g].nwin * n, pitch = bg.pitch;
+        const int f0 = bg.win0 * n;
+        CclBuffers gb = buf.cb;
         gb.Pp = (int)ccl_padded(H, W);
         gb.words = (int)ccl_words(H, W);
-        gb.ncomp = cb.ncomp + f0;
-        uint8_t *src = single ? dOpen : tmp_in, *lab = single ? dLab : tmp_out;
-        if (!single) HIPCHK(ctx, hipMemcpy2DAsync(tmp_in, P, dOpen + goff[g], pitch, P, Fg, hipMemcpyDeviceToDevice, s));
+        gb.ncomp = buf.cb.ncomp + f0;
+        uint8_t *src = single ? dOpen : buf.tmp_in, *lab = single ? dLab : buf.tmp_out;
+        if (!single) HIPCHK(ctx, hipMemcpy2DAsync(buf.tmp_in, P, dOpen + bg.goff, pitch, P, Fg, hipMemcpyDeviceToDevice, s));
         { Timed t(ctx, SWK_K_CCL); launch_ccl(s, src, Fg, H, W, p->connectivity, p->label_order, gb, nullptr, lab); }
-        if (want_props) {
+        if (pl.want_props) {
             Timed t(ctx, SWK_K_PROPS);
-            launch_regionprops(s, lab, Fg, H, W, gb, capmax, dsegs + (size_t)f0 * capmax, dnseg + f0);
+            launch_regionprops(s, lab, Fg, H, W, gb, capmax, buf.dsegs + (size_t)f0 * capmax, buf.dnseg + f0);
         }
-        if (!single) HIPCHK(ctx, hipMemcpy2DAsync(dLab + goff[g], pitch, tmp_out, P, P, Fg, hipMemcpyDeviceToDevice, s));
+        if (!single) HIPCHK(ctx, hipMemcpy2DAsync(dLab + bg.goff, pitch, buf.tmp_out, P, P, Fg, hipMemcpyDeviceToDevice, s));
     }
+    return SWK_OK;
+}
 
-    // ---- outputs, group by group, in swk_batch_run's layouts (what was written in place is not copied) ----
-    {
-        Timed t(ctx, SWK_K_COPY);
-        for (int g = 0; g < G; ++g) {
-            const swk_output *out = &outs[g];
-            const size_t P = (size_t)groups[g].Hc * groups[g].Wc, Fg = (size_t)groups[g].nwin * n, pitch = subs[sub_of[g]].P;
-            const size_t f0 = (size_t)win0[g] * n;
-            const bool dev_planes = out->mem == SWK_MEM_DEVICE || out->planes_on_device != 0;
-            const hipMemcpyKind pk = dev_planes ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-            const hipMemcpyKind ok = out->mem == SWK_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-            const std::array<uint8_t *, 6> dst = out_planes(*out);
-            for (int i = 0; i < 6; ++i)
-                if (dst[i] && (rc = copy_out(ctx, dst[i], P, pl[i] + goff[g], pitch, P, Fg, pk))) return rc;
-            const size_t rec = sizeof(swk_segment);
-            if (out->segs && (rc = copy_out(ctx, out->segs, out->seg_cap * rec, dsegs + f0 * capmax, capmax * rec, out->seg_cap * rec, Fg, ok)))
-                return rc;
-            if (out->nseg && (rc = copy_out(ctx, out->nseg, Fg * 4, dnseg + f0, Fg * 4, Fg * 4, 1, ok))) return rc;
-        }
+// outputs, group by group, in swk_batch_run's layouts (what was written in place is not copied)
+int batch_outputs(Batch &b)
+{
+    swk_ctx *ctx = b.ctx;
+    const BatchPlan &pl = b.plan;
+    const size_t capmax = pl.capmax;
+    int rc;
+    Timed t(ctx, SWK_K_COPY);
+    for (int g = 0; g < b.G; ++g) {
+        const swk_output *out = &b.outs[g];
+        const BatchGroup &bg = pl.grp[g];
+        const size_t P = (size_t)b.groups[g].Hc * b.groups[g].Wc, Fg = (size_t)b.groups[g].nwin * pl.n, pitch = bg.pitch;
+        const size_t f0 = (size_t)bg.win0 * pl.n;
+        const bool dev_planes = out->mem == SWK_MEM_DEVICE || out->planes_on_device != 0;
+        const hipMemcpyKind pk = dev_planes ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        const hipMemcpyKind ok = out->mem == SWK_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        const std::array<uint8_t *, 6> dst = out_planes(*out);
+        for (int i = 0; i < 6; ++i)
+            if (dst[i] && (rc = copy_out(ctx, dst[i], P, b.buf.pl[i] + bg.goff, pitch, P, Fg, pk))) return rc;
+        const size_t rec = sizeof(swk_segment);
+        if (out->segs && (rc = copy_out(ctx, out->segs, out->seg_cap * rec, b.buf.dsegs + f0 * capmax, capmax * rec, out->seg_cap * rec, Fg, ok)))
+            return rc;
+        if (out->nseg && (rc = copy_out(ctx, out->nseg, Fg * 4, b.buf.dnseg + f0, Fg * 4, Fg * 4, 1, ok))) return rc;
     }
-    rc = sync(ctx);
-    if (rc) return rc;
+    return SWK_OK;
+}
 
-    // ---- iteration counts (sub-batch order -> call order) and the record swk_segment_inputs_last reads ----
-    rc = read_windows(ctx, run, hw_sub);
+// after the call's final sync: iteration counts (sub-batch order -> call order) and the record swk_segment_inputs_last reads
+int batch_epilogue(Batch &b)
+{
+    swk_ctx *ctx = b.ctx;
+    const BatchPlan &pl = b.plan;
+    const int G = b.G, n = pl.n;
+    int rc = read_windows(ctx, b.run, b.hw_sub);
     if (rc) return rc;
-    std::vector<IalmWin> hw(nwin);
+    std::vector<IalmWin> hw(pl.nwin);
     for (int g = 0; g < G; ++g)
-        for (int wl = 0; wl < groups[g].nwin; ++wl) hw[win0[g] + wl] = hw_sub[swin0[g] + wl];
-    std::vector<int32_t> it(nwin);
+        for (int wl = 0; wl < b.groups[g].nwin; ++wl) hw[pl.grp[g].win0 + wl] = b.hw_sub[pl.grp[g].swin0 + wl];
+    std::vector<int32_t> it(pl.nwin);
     account_iters(ctx, hw, it.data());
     bool uploaded = false;
     for (int g = 0; g < G; ++g) {
-        if (!outs[g].iters) continue;
-        if (outs[g].mem == SWK_MEM_DEVICE) {
-            HIPCHK(ctx, hipMemcpyAsync(outs[g].iters, it.data() + win0[g], (size_t)groups[g].nwin * 4, hipMemcpyHostToDevice, s));
+        const swk_output &out = b.outs[g];
+        const int32_t *mine = it.data() + pl.grp[g].win0;
+        if (!out.iters) continue;
+        if (out.mem == SWK_MEM_DEVICE) {
+            HIPCHK(ctx, hipMemcpyAsync(out.iters, mine, (size_t)b.groups[g].nwin * 4, hipMemcpyHostToDevice, ctx->stream));
             uploaded = true;
-        } else memcpy(outs[g].iters, it.data() + win0[g], (size_t)groups[g].nwin * 4);
+        } else memcpy(out.iters, mine, (size_t)b.groups[g].nwin * 4);
     }
-    if (uploaded) HIPCHK(ctx, hipStreamSynchronize(s));          // `it` is a local
-    if (seg_last) {
-        swk_ctx::LastBatch &lb = ctx->last;
-        lb = swk_ctx::LastBatch{};
-        lb.nwin = nwin; lb.n = n;
-        lb.segs = dsegs; lb.nseg = dnseg; lb.cap = capmax;
-        if (single) {          // one geometry: k_segment_inputs
-            const View &v = view[0];
-            lb.frames = v.frames; lb.fs = v.fs; lb.rs = v.rs;
-            lb.Hc = H0; lb.Wc = W0; lb.x0 = v.x0; lb.y0 = v.y0; lb.frame_h = v.frame_h(); lb.frame_w = v.frame_w();
-        } else {
-            lb.fr = (const SegFrame *)(dtab + o_sf);          // per-frame frames and geometry: k_segment_inputs_groups
-        }
-        if (host_total) {
-            lb.total = 0;
-            for (int g = 0; g < G; ++g)
-                for (int f = 0; f < groups[g].nwin * n; ++f) lb.total += std::min(outs[g].nseg[f], outs[g].seg_cap);
-        }
-        lb.valid = true;
+    if (uploaded) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // `it` is a local
+    if (!pl.seg_last) return SWK_OK;
+    swk_ctx::LastBatch &lb = ctx->last;
+    lb = swk_ctx::LastBatch{};
+    lb.nwin = pl.nwin; lb.n = n;
+    lb.segs = b.buf.dsegs; lb.nseg = b.buf.dnseg; lb.cap = pl.capmax;
+    if (pl.single) {          // one geometry: k_segment_inputs
+        const BatchView &v = b.view[0];
+        lb.frames = v.frames; lb.fs = v.fs; lb.rs = v.rs;
+        lb.Hc = b.groups[0].Hc; lb.Wc = b.groups[0].Wc; lb.x0 = v.x0; lb.y0 = v.y0; lb.frame_h = v.frame_h(); lb.frame_w = v.frame_w();
+    } else {
+        lb.fr = (const SegFrame *)(b.buf.dtab + pl.o_sf);          // per-frame frames and geometry: k_segment_inputs_groups
     }
+    if (pl.host_total) {
+        lb.total = 0;
+        for (int g = 0; g < G; ++g)
+            for (int f = 0; f < b.groups[g].nwin * n; ++f) lb.total += std::min(b.outs[g].nseg[f], b.outs[g].seg_cap);
+    }
+    lb.valid = true;
     return SWK_OK;
+}
+
+int run_batch(swk_ctx *ctx, const swk_input *groups, int G, const swk_params *p, swk_output *outs)
+{
+    if (const char *msg = params_refusal(p, true)) return fail(ctx, SWK_ERR_ARG, msg);
+    Batch b{ctx, groups, G, p, outs};
+    const BatchPlan &pl = b.plan;
+    const char *why = nullptr;
+    int rc = plan_batch(groups, G, outs, &b.plan, &why);
+    if (rc) return fail(ctx, rc, why);
+    // capacity, checked here so that a refused call launches nothing: the grid's y extent, and run_ialm's limit on the padded plane
+    // (at the wider fpad of the two pass families: its reruns may take the other)
+    const int fpad_max = std::max(ialm_fpad(true, pl.n), ialm_fpad(false, pl.n));
+    for (const BatchSub &sb : pl.subs) {
+        if ((rc = check_windows(ctx, sb.nwin))) return rc;
+        if ((int64_t)fpad_max * ialm_pstride(sb.P) >= (1ll << 28))
+            return fail(ctx, SWK_ERR_ARG, "window too large: frames x padded ROI pixels must stay below 2^28");
+    }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->last.valid = false;
+    ctx->last_stage.resize(G);
+    for (int g = 0; g < G; ++g) ctx->last_stage[g] = pl.grp[g].stage.kind;
+    if ((rc = batch_buffers(ctx, pl, groups, outs, &b.buf))) return rc;
+    if ((rc = ensure_bilateral(ctx, p->bil_d, p->bil_sigma_color, p->bil_sigma_space))) return rc;          // (slots of its own)
+    if ((rc = batch_inputs(b))) return rc;
+    if ((rc = batch_tables(b))) return rc;
+    batch_gray(b);
+    if ((rc = batch_ialm(b))) return rc;
+    batch_filter(b);
+    if ((rc = batch_labels(b))) return rc;
+    if ((rc = batch_outputs(b))) return rc;
+    if ((rc = sync(ctx))) return rc;
+    return batch_epilogue(b);
 }
 
 }  // namespace
@@ -2230,9 +2174,8 @@ int32_t swk_debug_filter_fused(swk_ctx *ctx, const uint8_t *src, int32_t count, 
                                int64_t total, const swk_params *p, uint8_t *bilateral, uint8_t *thresh, uint8_t *opened, uint8_t *guard)
 {
     if (!ctx || !src || !p || !opened || count < 1 || count > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "bad argument");
-    // the batch path's rules (run_batch), before any buffer or launch
-    if (p->open_kh != 3 || p->open_kw != 3) return fail(ctx, SWK_ERR_ARG, "only the (3,3) opening window is implemented");
-    if (bilateral_radius(p->bil_d, p->bil_sigma_space) > 4) return fail(ctx, SWK_ERR_ARG, "bilateral diameter > 9 is not supported");
+    // the batch path's rules for its filter, before any buffer or launch
+    if (const char *msg = params_refusal(p, false)) return fail(ctx, SWK_ERR_ARG, msg);
     std::vector<FrameGeom> hg;
     int Hmax = 0, Wmax = 0;
     if (planes) {

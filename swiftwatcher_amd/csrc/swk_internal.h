@@ -5,11 +5,12 @@
 #include <atomic>
 #include "swk.h"
 #include "swk_debug.h"
+#include "batch_plan.h"
 
 namespace swk {
 
 constexpr int kMaxN = 64;          // frames per window supported by the matrix-core IALM kernels
-constexpr int kMaxNWide = 128;     // ... and by the plain f64 kernels that take over above that (k_ialm_pass_lds<4>, k_ialm_small_wide)
+// kMaxNWide = 128 (batch_plan.h, where the batch plan refuses more): ... and by the plain f64 kernels that take over above kMaxN
 
 // Kernels that take more than 64 KB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize, and the attribute
 // belongs to the (kernel, device) pair: `mask` (one static per kernel instantiation) keeps a bit per device it has been
@@ -82,8 +83,6 @@ struct IalmWin {
                                    // 4 wanted but not done (a window without an integer start that is too large for one workgroup's
                                    // double-double Gram matrix)
 };
-
-struct PnWin;
 
 struct IalmBuffers {
     const uint8_t *X;              // [nwin][n][P]
@@ -271,24 +270,11 @@ void launch_stabilize_subpel(hipStream_t s, const uint8_t *frames, int64_t fs, i
                              swk_shift *shifts, void *sub_table, swk_subshift *recs, uint8_t *out);
 
 // ---- several groups of windows in one call ---------------------------------------------------------------
-// swk_batch_run and swk_batch_run_groups share one driver (run_batch, swk_api.hip).  A call of one group takes the uniform
-// launchers above; a call of several takes these: a group's windows keep their own geometry, the image stages address every
-// frame through a descriptor, and the IALM runs over planes zero-padded to the call's largest ROI (groups.hip, DESIGN
-// section "Several videos in one call").
-// Gather source of one window: queue position j is the frame at src + j * fs, its ROI pixel (r, c) at
-// + (y0 + r) * rs + (x0 + c) * channels; frame j's X plane starts at off + j * pitch, pixels p >= H * W of it are zero.
-struct GroupWin {
-    const uint8_t *src;
-    int64_t fs, rs, off;
-    int x0, y0, H, W, channels, pitch;
-};
-// Geometry of one frame's u8 stage planes: H x W dense pixels starting at element `off` (H = 0: the kernel skips the frame)
-struct FrameGeom { int H, W; int64_t off; };
-// Classifier-input cut of one frame: its device BGR frame, row stride, frame size, ROI origin, and its region-record cap
-struct SegFrame { const uint8_t *frame; int64_t rs; int frame_h, frame_w, x0, y0, cap, pad_; };
-// (pixels, frames) scatter of one window: P pixels written to dst (null: not wanted)
-struct PnWin { double *dst; int P, pad_; };
-
+// swk_batch_run and swk_batch_run_groups share one driver (run_batch, swk_api.hip) and one host-only plan (batch_plan.h, which
+// also holds the descriptor records GroupWin, FrameGeom, SegFrame and PnWin).  A call of one group takes the uniform launchers
+// above; a call of several takes these: a group's windows keep their own geometry, the image stages address every frame through
+// a descriptor, and the IALM runs over planes zero-padded to the call's largest ROI (groups.hip, DESIGN section "Several videos
+// in one call").
 void launch_gray_groups(hipStream_t s, const GroupWin *wins, int F, int n, int Pmax, int gray_mode, uint8_t *X);
 void launch_planes_to_pn_groups(hipStream_t s, const double *planes, const PnWin *wins, int nwin, int n, int Pmax, int64_t pstride,
                                 int fpad);
