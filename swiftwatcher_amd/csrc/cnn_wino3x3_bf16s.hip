@@ -26,8 +26,15 @@
 // the Winograd total of a forward 3.17 against 3.89 ms.  16 -> 64 measured slower (77 / 101 against 73 / 93 us) and stays on the float32
 // kernel in the classifier.  The matrix pipe is no longer the wall: the six products put 64 -> 256 near 0.33 ms of MFMA time, a third of
 // what it takes.  What remains is the filter stream (0.75 of the float32 kernel's bytes per tile, from L2 by LDS-DMA, one phase ahead),
-// the per-position V staging (eight patch loads, transform and split per thread, then a workgroup barrier) and LDS bank conflicts
+// the per-position V staging (patch loads, transform and split per thread, then a workgroup barrier) and LDS bank conflicts
 // (0.6-1.1 conflict cycles per LDS instruction, profiles/wino_bf16s_pmc_counters.txt); the counters do not separate these further.
+// The staging loads every patch pixel once per ROW of positions: the four positions (xi, 0..3) combine the column pairs (0,2) (1,2)
+// (2,1) (1,3) of the same two patch rows, so (xi, 0) loads four pixels, (xi, 1) and (xi, 3) two and (xi, 2) none -- 32 pixel loads
+// per item and task where 64 were issued, the same values into the same expressions (bit-identical outputs).  nu is unrolled for it,
+// so that the registers and their roles are fixed in the code.  The 16-wave 64 -> 256 layout cannot hold pixels through a position's
+// products at 128 registers: it loads the four pixels of (xi, 1), stores V(xi, 1) and, after the barrier, V(xi, 2) from the same
+// registers into the buffer that barrier has freed (the compiler further keeps column 1 for (xi, 3): 40 loads, no scratch).
+// Measured: DESIGN section 6, "Patch pixels once per row of positions".
 // Twice the tiles per filter byte would need 128 x 256 outputs in one CU's registers (Y alone fills the register file) or V formed
 // twice; see DESIGN section 10.
 // Two kernels: k_wino3x3_bf16s_relu_place as described above (32 -> 128, and every shape under swk_set_cnn_tuning(2, 1)), and
@@ -74,37 +81,47 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
     int slim;                // largest byte offset a patch load of the item may add (the last 32 bytes of src)
     const char *const srcb = (const char *)src;
     auto stage_setup = [&](int64_t task) {
-        int64_t m = task * SLOTS + sslot;
+        int ti = tid;
+        asm volatile("" : "+v"(ti));          // opaque: the next task's origin is formed at its last position, not held through all sixteen
+        const int item = ti;
+        int64_t m = task * SLOTS + item / KG;
         if (m >= ntiles) m = ntiles - 1;
         const unsigned bu = fTT.div((unsigned)m), rem = (unsigned)m - bu * (unsigned)TT, ty = fT.div(rem), tx = rem - ty * (unsigned)T;
         const int64_t b = bu;
-        const int64_t base = (((b * t + 2 * ty) * t + 2 * tx) * (int64_t)CIN + 8 * sg) * 4;
+        const int64_t base = (((b * t + 2 * ty) * t + 2 * tx) * (int64_t)CIN + 8 * (item % KG)) * 4;
         const int64_t lim = src_floats * 4 - 32 - base;          // a patch may reach one row / column past an odd-sized tile
         sbase = (unsigned)base;
         slim = (int)(lim < (1 << 30) ? lim : (1 << 30));
     };
     float4 st[4][2];
-    // patch rows (columns) position xi (nu) combines, as in cnn_wino3x3.hip: first row {0,1,2,1}, second {2,2,1,3}, sign {-,+,-,-}
-    auto stage_issue = [&](int p) {
-        const int xi = p >> 2, nu = p & 3;
-        const int ra0 = (0x1210 >> (4 * xi)) & 15, ra1 = (0x3122 >> (4 * xi)) & 15;
-        const int rb0 = (0x1210 >> (4 * nu)) & 15, rb1 = (0x3122 >> (4 * nu)) & 15;
-        const int os[4] = {(ra0 * t + rb0) * (CIN * 4), (ra0 * t + rb1) * (CIN * 4), (ra1 * t + rb0) * (CIN * 4), (ra1 * t + rb1) * (CIN * 4)};
+    // patch rows (columns) position xi (nu) combines, as in cnn_wino3x3.hip: first row {0,1,2,1}, second {2,2,1,3}, sign {-,+,-,-}.
+    // Along a row of positions the column pairs are (0,2) (1,2) (2,1) (1,3): st[0], st[2] hold the pixels of column 0, then 1, and
+    // st[1], st[3] those of column 2, then 3 -- nu = 0 loads all four, nu = 1 and 3 one column each, nu = 2 none (nu is a constant
+    // of the unrolled code: the slots and their roles cost nothing at run time).  Nothing is kept from one xi to the next.
+    auto stage_issue = [&](int xi, int nu) {
+        const int ra[2] = {(0x1210 >> (4 * xi)) & 15, (0x3122 >> (4 * xi)) & 15};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const char *q = srcb + (sbase + (unsigned)(os[i] < slim ? os[i] : slim));
-            st[i][0] = *(const float4 *)q;
-            st[i][1] = *(const float4 *)(q + 16);
+            const int col = (i & 1) ? (nu == 3 ? 3 : 2) : (nu == 0 ? 0 : 1);
+            if ((i & 1) ? (nu == 0 || nu == 3) : nu < 2) {
+                const int os = (ra[i >> 1] * t + col) * (CIN * 4);
+                const char *q = srcb + (sbase + (unsigned)(os < slim ? os : slim));
+                st[i][0] = *(const float4 *)q;
+                st[i][1] = *(const float4 *)(q + 16);
+            }
         }
     };
-    // V = (d00 + sn d01) + sx (d10 + sn d11), split three ways, stored as the parts' B operands
-    auto stage_store = [&](int p, uint4 *Vn) {
-        const float sx = (p >> 2) == 1 ? 1.0f : -1.0f, sn = (p & 3) == 1 ? 1.0f : -1.0f;
+    // V = (d00 + sn d01) + sx (d10 + sn d11), split three ways, stored as the parts' B operands; nu = 2 takes the columns (2,1) from
+    // the slots of (1,2)
+    auto stage_store = [&](int xi, int nu, uint4 *Vn) {
+        const float sx = xi == 1 ? 1.0f : -1.0f, sn = nu == 1 ? 1.0f : -1.0f;
+        const int ia = nu == 2 ? 1 : 0, ib = 1 - ia;
         bf16x8 v1, v2, v3;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const float a[4] = {st[0][h].x, st[0][h].y, st[0][h].z, st[0][h].w}, b[4] = {st[1][h].x, st[1][h].y, st[1][h].z, st[1][h].w},
-                        c[4] = {st[2][h].x, st[2][h].y, st[2][h].z, st[2][h].w}, d[4] = {st[3][h].x, st[3][h].y, st[3][h].z, st[3][h].w};
+            const float a[4] = {st[ia][h].x, st[ia][h].y, st[ia][h].z, st[ia][h].w}, b[4] = {st[ib][h].x, st[ib][h].y, st[ib][h].z, st[ib][h].w},
+                        c[4] = {st[2 + ia][h].x, st[2 + ia][h].y, st[2 + ia][h].z, st[2 + ia][h].w},
+                        d[4] = {st[2 + ib][h].x, st[2 + ib][h].y, st[2 + ib][h].z, st[2 + ib][h].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float v = __builtin_fmaf(__builtin_fmaf(d[e], sn, c[e]), sx, __builtin_fmaf(b[e], sn, a[e]));
@@ -128,33 +145,19 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
 #pragma unroll
         for (int sub = 0; sub < SPP; ++sub) lds_dma_copy<3>(l + sub * 3072u, gp + sub * 3072, wvoff);
     };
-    // the copies of a phase are issued BEFORE the patch loads: lds_dma_wait<8>() retires them and leaves the eight patch loads in flight
+    // the copies of a phase are issued BEFORE the patch loads: where a position has two phases, lds_dma_wait<N>() retires them and leaves
+    // the N patch loads of the next position (eight, four or none) in flight
 
     int64_t task = blockIdx.x;
     if (task < ntasks) {
         stage_setup(task);
-        stage_issue(0);
-        stage_store(0, V0);
+        stage_issue(0, 0);
+        stage_store(0, 0, V0);
         w_issue(0, 0);
     }
     lds_dma_wait<0>();
     __syncthreads();
     for (; task < ntasks; task += gridDim.x) {
-        // ---- this lane's two tiles as the matrix cores see them: destinations of their 2 x 2 outputs ----
-        int64_t ro[2];
-        bool valid[2], vy1[2], vx1[2];
-#pragma unroll
-        for (int tg = 0; tg < 2; ++tg) {
-            const int64_t m = task * SLOTS + tg * 32 + r;
-            valid[tg] = m < ntiles;
-            const int64_t mm = valid[tg] ? m : ntiles - 1;
-            const unsigned bu = fTT.div((unsigned)mm), rem = (unsigned)mm - bu * (unsigned)TT;
-            const int ty = (int)fT.div(rem), tx = (int)(rem - (unsigned)ty * (unsigned)T);
-            const int64_t b = bu;
-            ro[tg] = ((b * dH + off_y + 2 * ty) * dW + off_x + 2 * tx) * (int64_t)dC + c_off + 32 * wave + 4 * hh;
-            vy1[tg] = 2 * ty + 1 < o;
-            vx1[tg] = 2 * tx + 1 < o;
-        }
         const bool more = task + gridDim.x < ntasks;
         f16v Y[2][2][2];
 #pragma unroll
@@ -187,13 +190,17 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
                 }
             }
         };
-        for (int p = 0; p < 16; ++p) {
-            const uint4 *Vc = (p & 1) ? V1 : V0;
-            uint4 *Vn = (p & 1) ? V0 : V1;
-            const int pn = (p + 1) & 15;
-            if (p == 15 && more) stage_setup(task + gridDim.x);
+        // positions p = 4 xi + nu in their natural order, the four of a row unrolled (and no more than those)
+#pragma unroll 1
+        for (int xi = 0; xi < 4; ++xi)
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) {
+            const int p = 4 * xi + nu;
+            const uint4 *Vc = (nu & 1) ? V1 : V0;
+            uint4 *Vn = (nu & 1) ? V0 : V1;
+            const int xin = nu == 3 ? (xi + 1) & 3 : xi, nun = (nu + 1) & 3;          // the next position
+            if (nu == 3 && xi == 3 && more) stage_setup(task + gridDim.x);
             // Y_ij += A^T[i][xi] A^T[j][nu] M_p,   A^T = [1 1 1 0; 0 1 -1 -1]
-            const int xi = p >> 2, nu = p & 3;
             const float ax[2] = {xi < 3 ? 1.0f : 0.0f, xi == 0 ? 0.0f : xi == 1 ? 1.0f : -1.0f};
             const float an[2] = {nu < 3 ? 1.0f : 0.0f, nu == 0 ? 0.0f : nu == 1 ? 1.0f : -1.0f};
             f16v M[2];
@@ -203,14 +210,19 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
                 for (int e = 0; e < 16; ++e) M[tg][e] = 0.0f;
 #pragma unroll
             for (int h = 0; h < PHS; ++h) {
-                // the next phase's filter slice travels while this one multiplies; the next position's patch pixels during the whole position
-                // (after a workgroup's last position they fetch position 0 of the same tiles again, unused: see cnn_wino3x3.hip)
+                // the next phase's filter slice travels while this one multiplies; the next position's new patch pixels during the whole
+                // position (after a workgroup's last position they fetch position 0 of the same tiles again, unused: see cnn_wino3x3.hip)
                 const int g = p * PHS + h, gn = g + 1 == 16 * PHS ? 0 : g + 1;
+                // No barrier lies between the phases of a position, so nothing but this wait keeps the copy below from overwriting the
+                // buffer the phase before read while its last operand reads are still on their way: where the next position has no patch
+                // pixels to fetch, the compiler puts the reads of the last parts (u2, u3 of the second k-step) right in front of the copy,
+                // and in a few tasks of a hundred they returned the next phase's bytes
+                if (h > 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 w_issue(gn, (g + 1) & 1);
-                if (h == 0) stage_issue(pn);
+                if (h == 0) stage_issue(xin, nun);
                 phase(Wl + ((g & 1) * NW + wave) * WPB, Vc, h * SPP, M);
                 if (h == PHS - 1) {
-                    stage_store(pn, Vn);
+                    stage_store(xin, nun, Vn);
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -225,11 +237,31 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
                         }
                 }
                 // this wave's slice of the next phase has landed (patch loads issued in a first phase of several stay in flight)
-                if (h == 0 && PHS > 1) lds_dma_wait<8>();
+                if (h == 0 && PHS > 1 && nun == 0) lds_dma_wait<8>();
+                else if (h == 0 && PHS > 1 && nun != 2) lds_dma_wait<4>();
                 else lds_dma_wait<0>();
                 // the next position's V is complete, this one's buffer is free
                 if (h == PHS - 1) __syncthreads();
             }
+        }
+        // ---- this lane's two tiles as the matrix cores see them: destinations of their 2 x 2 outputs (formed here, not before the
+        //      positions: nothing of it occupies a register meanwhile) ----
+        int te = tid;
+        asm volatile("" : "+v"(te));          // opaque: what follows from it is formed here every task and not kept through the positions
+        const int re = te & 31, he = (te >> 5) & 1, we = te >> 6;
+        int64_t ro[2];
+        bool valid[2], vy1[2], vx1[2];
+#pragma unroll
+        for (int tg = 0; tg < 2; ++tg) {
+            const int64_t m = task * SLOTS + tg * 32 + re;
+            valid[tg] = m < ntiles;
+            const int64_t mm = valid[tg] ? m : ntiles - 1;
+            const unsigned bu = fTT.div((unsigned)mm), rem = (unsigned)mm - bu * (unsigned)TT;
+            const int ty = (int)fT.div(rem), tx = (int)(rem - (unsigned)ty * (unsigned)T);
+            const int64_t b = bu;
+            ro[tg] = ((b * dH + off_y + 2 * ty) * dW + off_x + 2 * tx) * (int64_t)dC + c_off + 32 * we + 4 * he;
+            vy1[tg] = 2 * ty + 1 < o;
+            vx1[tg] = 2 * tx + 1 < o;
         }
         // ---- bias + ReLU + placement: register quads = four consecutive output channels of the lane's tile ----
 #pragma unroll
@@ -243,7 +275,7 @@ __global__ __launch_bounds__(64 * NBLK, 2) void k_wino3x3_bf16s_relu_place(const
                     float *q = dst + ro[tg] + ((int64_t)i * dW + j) * dC;
 #pragma unroll
                     for (int gq = 0; gq < 4; ++gq) {
-                        const int c = 32 * wave + 8 * gq + 4 * hh;
+                        const int c = 32 * we + 8 * gq + 4 * he;
                         if (c < cout) store_bias_relu(q + 8 * gq, Y[i][j][tg], gq, *(const float4 *)(lbias + c));
                     }
                 }
@@ -324,36 +356,46 @@ __global__ __launch_bounds__(64 * NBLK * WCB, WPS) void k_wino3x3_bf16s_shared_r
     int slim;                // largest byte offset a patch load of the thread may add (the last 16 NH bytes of src)
     const char *const srcb = (const char *)src;
     auto stage_setup = [&](int64_t task) {
-        int64_t m = task * SLOTS + sslot;
+        int ti = tid;
+        asm volatile("" : "+v"(ti));          // opaque: the next task's origin is formed at its last position, not held through all sixteen
+        const int item = NH == 2 ? ti : ti >> 1;
+        int64_t m = task * SLOTS + item / KG;
         if (m >= ntiles) m = ntiles - 1;
         const unsigned bu = fTT.div((unsigned)m), rem = (unsigned)m - bu * (unsigned)TT, ty = fT.div(rem), tx = rem - ty * (unsigned)T;
         const int64_t b = bu;
-        const int64_t base = (((b * t + 2 * ty) * t + 2 * tx) * (int64_t)CIN + 8 * sg + 4 * shalf) * 4;
+        const int64_t base = (((b * t + 2 * ty) * t + 2 * tx) * (int64_t)CIN + 8 * (item % KG) + 4 * (NH == 2 ? 0 : ti & 1)) * 4;
         const int64_t lim = src_floats * 4 - 16 * NH - base;          // a patch may reach one row / column past an odd-sized tile
         sbase = (unsigned)base;
         slim = (int)(lim < (1 << 30) ? lim : (1 << 30));
     };
     float4 st[4][NH];
-    auto stage_issue = [&](int p) {
-        const int xi = p >> 2, nu = p & 3;
-        const int ra0 = (0x1210 >> (4 * xi)) & 15, ra1 = (0x3122 >> (4 * xi)) & 15;
-        const int rb0 = (0x1210 >> (4 * nu)) & 15, rb1 = (0x3122 >> (4 * nu)) & 15;
-        const int os[4] = {(ra0 * t + rb0) * (CIN * 4), (ra0 * t + rb1) * (CIN * 4), (ra1 * t + rb0) * (CIN * 4), (ra1 * t + rb1) * (CIN * 4)};
+    // the slots as in k_wino3x3_bf16s_relu_place: st[0], st[2] hold column 0, then 1, st[1], st[3] column 2, then 3.  Where st lives
+    // through a position (!LATE) a position loads only the columns its row of positions has not loaded yet: all four pixels for nu = 0,
+    // one column for nu = 1 and 3, nothing for nu = 2.  LATE keeps nothing through the products: `both` loads the position's two columns.
+    auto stage_issue = [&](int xi, int nu, bool both) {
+        const int ra[2] = {(0x1210 >> (4 * xi)) & 15, (0x3122 >> (4 * xi)) & 15};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const char *q = srcb + (sbase + (unsigned)(os[i] < slim ? os[i] : slim));
+            const int col = (i & 1) ? (nu == 3 ? 3 : 2) : (nu == 0 ? 0 : 1);
+            if (nu != 2 && (both || ((i & 1) ? (nu == 0 || nu == 3) : nu < 2))) {
+                const int os = (ra[i >> 1] * t + col) * (CIN * 4);
+                const char *q = srcb + (sbase + (unsigned)(os < slim ? os : slim));
 #pragma unroll
-            for (int h = 0; h < NH; ++h) st[i][h] = *(const float4 *)(q + 16 * h);
+                for (int h = 0; h < NH; ++h) st[i][h] = *(const float4 *)(q + 16 * h);
+            }
         }
     };
-    // V = (d00 + sn d01) + sx (d10 + sn d11), split three ways, stored as the parts' B operands
-    auto stage_store = [&](int p, uint4 *Vn) {
-        const float sx = (p >> 2) == 1 ? 1.0f : -1.0f, sn = (p & 3) == 1 ? 1.0f : -1.0f;
+    // V = (d00 + sn d01) + sx (d10 + sn d11), split three ways, stored as the parts' B operands; nu = 2 takes the columns (2,1) from
+    // the slots of (1,2)
+    auto stage_store = [&](int xi, int nu, uint4 *Vn) {
+        const float sx = xi == 1 ? 1.0f : -1.0f, sn = nu == 1 ? 1.0f : -1.0f;
+        const int ia = nu == 2 ? 1 : 0, ib = 1 - ia;
         bf16x4 v1[NH], v2[NH], v3[NH];
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-            const float a[4] = {st[0][h].x, st[0][h].y, st[0][h].z, st[0][h].w}, b[4] = {st[1][h].x, st[1][h].y, st[1][h].z, st[1][h].w},
-                        c[4] = {st[2][h].x, st[2][h].y, st[2][h].z, st[2][h].w}, d[4] = {st[3][h].x, st[3][h].y, st[3][h].z, st[3][h].w};
+            const float a[4] = {st[ia][h].x, st[ia][h].y, st[ia][h].z, st[ia][h].w}, b[4] = {st[ib][h].x, st[ib][h].y, st[ib][h].z, st[ib][h].w},
+                        c[4] = {st[2 + ia][h].x, st[2 + ia][h].y, st[2 + ia][h].z, st[2 + ia][h].w},
+                        d[4] = {st[2 + ib][h].x, st[2 + ib][h].y, st[2 + ib][h].z, st[2 + ib][h].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float v = __builtin_fmaf(__builtin_fmaf(d[e], sn, c[e]), sx, __builtin_fmaf(b[e], sn, a[e]));
@@ -390,13 +432,14 @@ __global__ __launch_bounds__(64 * NBLK * WCB, WPS) void k_wino3x3_bf16s_shared_r
         if (WCB == 1 || wj == 0) w_pieces(std::integral_constant<int, 0>(), std::integral_constant<int, PC0>(), l, gp);
         else w_pieces(std::integral_constant<int, PC0>(), std::integral_constant<int, PC - PC0>(), l, gp);
     };
-    // the copies of a phase are issued BEFORE the patch loads: lds_dma_wait<4 NH>() retires them and leaves the patch loads in flight
+    // the copies of a phase are issued BEFORE the patch loads: lds_dma_wait<N>() retires them and leaves the N patch loads of the next
+    // position (4 NH, 2 NH or none) in flight
 
     int64_t task = blockIdx.x;
     if (task < ntasks) {
         stage_setup(task);
-        stage_issue(0);
-        stage_store(0, V0);
+        stage_issue(0, 0, true);
+        stage_store(0, 0, V0);
         w_issue(0, 0);
     }
     lds_dma_wait<0>();
@@ -436,13 +479,16 @@ __global__ __launch_bounds__(64 * NBLK * WCB, WPS) void k_wino3x3_bf16s_shared_r
                 if constexpr (WPS == 4) __builtin_amdgcn_sched_barrier(0);
             }
         };
-        for (int p = 0; p < 16; ++p) {
-            const uint4 *Vc = (p & 1) ? V1 : V0;
-            uint4 *Vn = (p & 1) ? V0 : V1;
-            const int pn = (p + 1) & 15;
-            if (p == 15 && more) stage_setup(task + gridDim.x);
+        // positions p = 4 xi + nu in their natural order, the four of a row unrolled (and no more than those)
+#pragma unroll 1
+        for (int xi = 0; xi < 4; ++xi)
+#pragma unroll
+        for (int nu = 0; nu < 4; ++nu) {
+            const int p = 4 * xi + nu;
+            uint4 *const Vc = (nu & 1) ? V1 : V0, *const Vn = (nu & 1) ? V0 : V1;
+            const int xin = nu == 3 ? (xi + 1) & 3 : xi, nun = (nu + 1) & 3;          // the next position
+            if (nu == 3 && xi == 3 && more) stage_setup(task + gridDim.x);
             // Y_ij += A^T[i][xi] A^T[j][nu] M_p,   A^T = [1 1 1 0; 0 1 -1 -1]
-            const int xi = p >> 2, nu = p & 3;
             const float ax[2] = {xi < 3 ? 1.0f : 0.0f, xi == 0 ? 0.0f : xi == 1 ? 1.0f : -1.0f};
             const float an[2] = {nu < 3 ? 1.0f : 0.0f, nu == 0 ? 0.0f : nu == 1 ? 1.0f : -1.0f};
             f16v M[TGW];
@@ -453,14 +499,17 @@ __global__ __launch_bounds__(64 * NBLK * WCB, WPS) void k_wino3x3_bf16s_shared_r
 #pragma unroll
             for (int h = 0; h < PHS; ++h) {
                 // the next phase's filter slice travels while this one multiplies (into the buffer the phase before this one read: a barrier
-                // lies between), the next position's patch pixels during the whole position
+                // lies between), the next position's new patch pixels during the whole position
                 const int g = p * PHS + h, gn = g + 1 == 16 * PHS ? 0 : g + 1;
+                // where no barrier ends a phase, the wave's own operand reads of the buffer the copy overwrites (k_wino3x3_bf16s_relu_place)
+                if (h > 0 && WCB == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 w_issue(gn, (g + 1) & 1);
-                if (h == 0 && !LATE) stage_issue(pn);
+                if (h == 0 && !LATE) stage_issue(xin, nun, false);
                 phase(Wl + ((g & 1) * NBLK + cb) * WPB, Vc, h * SPP, M);
                 if (h == PHS - 1) {
-                    if (LATE) stage_issue(pn);
-                    stage_store(pn, Vn);
+                    // LATE: V(xi, 2) was stored at the start of (xi, 1), below: nothing to fetch or to store at its end
+                    if (LATE) stage_issue(xin, nun, true);
+                    if (!LATE || nun != 2) stage_store(xin, nun, Vn);
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -475,15 +524,22 @@ __global__ __launch_bounds__(64 * NBLK * WCB, WPS) void k_wino3x3_bf16s_shared_r
                         }
                 }
                 // this wave's pieces of the next phase have landed (patch loads issued in a first phase of several stay in flight) ...
-                if (h == 0 && PHS > 1) lds_dma_wait<LATE ? 0 : 4 * NH>();
+                if (h == 0 && PHS > 1 && !LATE && nun == 0) lds_dma_wait<4 * NH>();
+                else if (h == 0 && PHS > 1 && !LATE && nun != 2) lds_dma_wait<2 * NH>();
                 else lds_dma_wait<0>();
                 // ... and the barrier shows them to its partner; after the last phase the next position's V is complete, this one's buffer free
                 if (h == PHS - 1 || WCB > 1) __syncthreads();
             }
+            // LATE: the pixels of (xi, 1) are those of (xi, 2).  Its V goes into the buffer the barrier has just freed, before the products
+            // of (xi, 1) need the registers, and is read two barriers later
+            if (LATE && nu == 0) {
+                stage_store(xi, 2, Vc);
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
         // ---- this lane's tiles as the matrix cores see them: destinations of their 2 x 2 outputs (formed here, not
         //      before the positions: nothing of it occupies a register meanwhile) ----
-        int le = lane;
+        int le = tid & 63;
         asm volatile("" : "+v"(le));          // opaque: what follows from it is formed here every task and not kept through the positions
         const int re = le & 31, he = le >> 5;
         int64_t ro[TGW];
