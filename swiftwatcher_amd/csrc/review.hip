@@ -36,30 +36,8 @@ namespace {
 constexpr int kChunk = 128;
 constexpr int kLabelChunk = kChunk * 6 / 16;          // 48 labels of 16 words: the LDS words of a chunk of boxes
 
-// The font: 5 x 7 glyphs, one byte per row, bit 4 the leftmost column, row 7 = 1 for a byte of the character set; bytes
-// kReviewFontFirst (space) .. 'Z'.  Drawn by hand for this library.
-#define G(a, b, c, d, e, f, g) {0x##a, 0x##b, 0x##c, 0x##d, 0x##e, 0x##f, 0x##g, 1}
-#define NONE {0, 0, 0, 0, 0, 0, 0, 0}
-#define SWK_REVIEW_FONT_ROWS {                                                                                                  \
-    /* space ! " # */ G(00, 00, 00, 00, 00, 00, 00), NONE, NONE, G(0A, 0A, 1F, 0A, 1F, 0A, 0A),                                 \
-    /* $ % & ' */     NONE, G(19, 19, 02, 04, 08, 13, 13), NONE, NONE,                                                          \
-    /* ( ) * + */     NONE, NONE, NONE, G(00, 04, 04, 1F, 04, 04, 00),                                                          \
-    /* , - . / */     NONE, G(00, 00, 00, 1F, 00, 00, 00), G(00, 00, 00, 00, 00, 0C, 0C), G(01, 01, 02, 04, 08, 10, 10),        \
-    /* 0 1 2 */       G(0E, 11, 13, 15, 19, 11, 0E), G(04, 0C, 04, 04, 04, 04, 0E), G(0E, 11, 01, 02, 04, 08, 1F),              \
-    /* 3 4 5 */       G(1F, 02, 04, 02, 01, 11, 0E), G(02, 06, 0A, 12, 1F, 02, 02), G(1F, 10, 1E, 01, 01, 11, 0E),              \
-    /* 6 7 8 */       G(06, 08, 10, 1E, 11, 11, 0E), G(1F, 01, 02, 04, 08, 08, 08), G(0E, 11, 11, 0E, 11, 11, 0E),              \
-    /* 9 : ; */       G(0E, 11, 11, 0F, 01, 02, 0C), G(00, 0C, 0C, 00, 0C, 0C, 00), NONE,                                       \
-    /* < = > ? @ */   NONE, G(00, 00, 1F, 00, 1F, 00, 00), NONE, NONE, NONE,                                                    \
-    /* A B C */       G(0E, 11, 11, 1F, 11, 11, 11), G(1E, 11, 11, 1E, 11, 11, 1E), G(0E, 11, 10, 10, 10, 11, 0E),              \
-    /* D E F */       G(1C, 12, 11, 11, 11, 12, 1C), G(1F, 10, 10, 1E, 10, 10, 1F), G(1F, 10, 10, 1E, 10, 10, 10),              \
-    /* G H I */       G(0E, 11, 10, 17, 11, 11, 0F), G(11, 11, 11, 1F, 11, 11, 11), G(0E, 04, 04, 04, 04, 04, 0E),              \
-    /* J K L */       G(07, 02, 02, 02, 02, 12, 0C), G(11, 12, 14, 18, 14, 12, 11), G(10, 10, 10, 10, 10, 10, 1F),              \
-    /* M N O */       G(11, 1B, 15, 15, 11, 11, 11), G(11, 11, 19, 15, 13, 11, 11), G(0E, 11, 11, 11, 11, 11, 0E),              \
-    /* P Q R */       G(1E, 11, 11, 1E, 10, 10, 10), G(0E, 11, 11, 11, 15, 12, 0D), G(1E, 11, 11, 1E, 14, 12, 11),              \
-    /* S T U */       G(0F, 10, 10, 0E, 01, 01, 1E), G(1F, 04, 04, 04, 04, 04, 04), G(11, 11, 11, 11, 11, 11, 0E),              \
-    /* V W X */       G(11, 11, 11, 11, 11, 0A, 04), G(11, 11, 11, 15, 15, 15, 0A), G(11, 11, 0A, 04, 0A, 11, 11),              \
-    /* Y Z */         G(11, 11, 11, 0A, 04, 04, 04), G(1F, 01, 02, 04, 08, 10, 1F)}
-const uint8_t h_font[kReviewFontCount][8] = SWK_REVIEW_FONT_ROWS;
+// the font's rows for draw_labels (review_font.h; the host's copy is review_font, review_plan.cpp)
+#include "review_font.h"
 __constant__ uint8_t d_font[kReviewFontCount][8] = SWK_REVIEW_FONT_ROWS;
 #undef SWK_REVIEW_FONT_ROWS
 #undef NONE
@@ -567,24 +545,6 @@ __global__ __launch_bounds__(256) void k_review_panels(ReviewArgs a, int f0, Rev
     const int cbytes = a.layout == SWK_YUV_I420 ? 1 : 2;
     const int64_t coff = (int64_t)f * a.c_fs + (int64_t)(oy >> 1) * a.c_rs + (ox >> 1) * cbytes;
     store_strip(px, y, a.u, a.v, coff, a.y_rs, a.c_rs, a.layout, sr, sc, 2, ncol);
-}
-
-void review_font(uint8_t out[128][8])
-{
-    memset(out, 0, 128 * 8);
-    memcpy(out[kReviewFontFirst], h_font, sizeof(h_font));
-}
-
-void review_label_palette(uint8_t out[256][3])
-{
-    // twelve hues drawn by hand, each at three strengths: label v >= 1 takes hue (v - 1) % 12 at strength ((v - 1) / 12) % 3, so
-    // neighbouring label values never share a colour and none is black
-    static const uint8_t hue[12][3] = {{0, 0, 255},   {0, 255, 0},   {255, 0, 0},   {0, 255, 255}, {255, 0, 255}, {255, 255, 0},
-                                       {0, 128, 255}, {128, 255, 0}, {255, 0, 128}, {255, 128, 0}, {128, 0, 255}, {0, 255, 128}};
-    static const int strength[3] = {256, 176, 112};
-    out[0][0] = out[0][1] = out[0][2] = 0;
-    for (int v = 1; v < 256; ++v)
-        for (int c = 0; c < 3; ++c) out[v][c] = (uint8_t)((hue[(v - 1) % 12][c] * strength[((v - 1) / 12) % 3]) >> 8);
 }
 
 void launch_review_panels(hipStream_t s, const ReviewArgs &a, int F, const ReviewPanels &q)

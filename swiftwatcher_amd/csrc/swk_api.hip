@@ -1299,84 +1299,30 @@ int32_t swk_bgr2gray(swk_ctx *ctx, const uint8_t *bgr, int32_t count, int32_t H,
     return sync(ctx);
 }
 
-// rows x width bytes of each of `count` host frames (first byte src, rows rs apart, frames fs apart) densely to the device
-static int upload_rects(swk_ctx *ctx, uint8_t *dst, const uint8_t *src, int64_t rs, int64_t fs, size_t width, size_t rows, int count)
+// rows x width bytes of each of `count` frames between a host plane (first byte host, rows rs apart, frames fs apart) and its dense
+// copy on the device (dev), up = host to device.  ((size_t)rs == width implies rs > 0: width >= 1.)
+static int copy_rects(swk_ctx *ctx, uint8_t *dev, const uint8_t *host, int64_t rs, int64_t fs, size_t width, size_t rows, int count, bool up)
 {
     const size_t per = width * rows;
-    if ((size_t)rs == width && rs > 0 && (count == 1 || fs == (int64_t)per)) {
-        HIPCHK(ctx, hipMemcpyAsync(dst, src, per * count, hipMemcpyHostToDevice, ctx->stream));
-        return SWK_OK;
-    }
-    for (int f = 0; f < count; ++f) {
-        const uint8_t *s = src + (int64_t)f * fs;
-        if ((size_t)rs == width) HIPCHK(ctx, hipMemcpyAsync(dst + (size_t)f * per, s, per, hipMemcpyHostToDevice, ctx->stream));
-        else HIPCHK(ctx, hipMemcpy2DAsync(dst + (size_t)f * per, width, s, (size_t)rs, width, rows, hipMemcpyHostToDevice, ctx->stream));
+    const hipMemcpyKind kind = up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    uint8_t *h = const_cast<uint8_t *>(host);                         // (written only on the way down)
+    const bool rows_dense = (size_t)rs == width;
+    const bool one = rows_dense && (count == 1 || fs == (int64_t)per);                // the frames are dense too: one copy for all
+    const int copies = one ? 1 : count;
+    const size_t bytes = one ? per * count : per;
+    for (int f = 0; f < copies; ++f) {
+        uint8_t *d = dev + (size_t)f * per, *s = h + (int64_t)f * fs;
+        if (rows_dense) HIPCHK(ctx, hipMemcpyAsync(up ? d : s, up ? s : d, bytes, kind, ctx->stream));
+        else HIPCHK(ctx, hipMemcpy2DAsync(up ? d : s, up ? width : (size_t)rs, up ? s : d, up ? (size_t)rs : width, width, rows, kind, ctx->stream));
     }
     return SWK_OK;
 }
 
-int32_t swk_yuv420_to_bgr(swk_ctx *ctx, const swk_yuv420 *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
-                          uint8_t *bgr, int32_t bgr_mem)
+// swk_yuv_to_bgr after its null and layout checks; yuv420: swk_yuv420_to_bgr's view of its argument (sx = sy = 1, bits = 8, where
+// the checks of bits, shifts and 2-byte samples cannot fire), which takes its own launcher
+static int yuv_call(swk_ctx *ctx, const swk_yuv *src, bool yuv420, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr, uint8_t *bgr,
+                    int32_t bgr_mem)
 {
-    if (!ctx) return SWK_ERR_ARG;
-    if (!src || !bgr) return fail(ctx, SWK_ERR_ARG, "null argument");
-    if (src->layout != SWK_YUV_I420 && src->layout != SWK_YUV_NV12) return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_I420 or SWK_YUV_NV12)");
-    const bool nv12 = src->layout == SWK_YUV_NV12;
-    if (!src->y || !src->u || (!nv12 && !src->v)) return fail(ctx, SWK_ERR_ARG, "null YUV plane");
-    if (count < 1 || count > (1 << 24)) return fail(ctx, SWK_ERR_ARG, "count must be in 1..2^24");
-    if ((src->mem != SWK_MEM_HOST && src->mem != SWK_MEM_DEVICE) || (bgr_mem != SWK_MEM_HOST && bgr_mem != SWK_MEM_DEVICE))
-        return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
-    const int H = src->H, W = src->W;
-    if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(ctx, SWK_ERR_ARG, "frame size must be 1..32768 on each side");
-    if (x0 < 0 || y0 < 0 || Hr < 1 || Wr < 1 || (int64_t)x0 + Wr > W || (int64_t)y0 + Hr > H)
-        return fail(ctx, SWK_ERR_ARG, "rectangle outside the frame");
-    const int cbytes = nv12 ? 2 : 1;                                  // bytes per chroma sample position in a chroma row
-    if (src->y_row_stride < W || src->c_row_stride < (int64_t)((W + 1) / 2) * cbytes)
-        return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    const size_t out_b = (size_t)count * Hr * Wr * 3;
-    const uint8_t *dy = src->y, *du = src->u, *dv = src->v;
-    int64_t y_rs = src->y_row_stride, y_fs = src->y_frame_stride, c_rs = src->c_row_stride, c_fs = src->c_frame_stride;
-    int kx0 = x0, ky0 = y0;
-    if (src->mem == SWK_MEM_HOST) {
-        // only the chroma cells that cover the rectangle, and the luma pixels of those cells (the rectangle grown to even
-        // origins: at most one more row and column), go to the device, densely; the kernel then sees a frame whose origin is
-        // the rectangle's first chroma cell, and the rectangle starts at its origin's parity
-        const int cy0 = y0 >> 1, ch = ((y0 + Hr - 1) >> 1) - cy0 + 1, cx0 = x0 >> 1, cw = ((x0 + Wr - 1) >> 1) - cx0 + 1;
-        const int lh = y0 + Hr - 2 * cy0, lw = x0 + Wr - 2 * cx0;
-        const size_t yb = ((size_t)count * lh * lw + 15) & ~(size_t)15, cb = ((size_t)count * ch * cw * cbytes + 15) & ~(size_t)15;
-        uint8_t *din;
-        NEED(ctx, SL_TMP_IN, yb + cb * (nv12 ? 1 : 2), din);
-        int rc = upload_rects(ctx, din, src->y + (int64_t)2 * cy0 * y_rs + 2 * cx0, y_rs, y_fs, (size_t)lw, (size_t)lh, count);
-        if (rc) return rc;
-        const int64_t coff = (int64_t)cy0 * c_rs + (int64_t)cx0 * cbytes;
-        rc = upload_rects(ctx, din + yb, src->u + coff, c_rs, c_fs, (size_t)cw * cbytes, (size_t)ch, count);
-        if (rc) return rc;
-        if (!nv12) {
-            rc = upload_rects(ctx, din + yb + cb, src->v + coff, c_rs, c_fs, (size_t)cw, (size_t)ch, count);
-            if (rc) return rc;
-        }
-        dy = din; du = din + yb; dv = nv12 ? nullptr : din + yb + cb;
-        y_rs = lw; y_fs = (int64_t)lh * lw; c_rs = (int64_t)cw * cbytes; c_fs = (int64_t)ch * c_rs;
-        kx0 = x0 & 1; ky0 = y0 & 1;
-    }
-    uint8_t *dout = bgr;
-    if (bgr_mem == SWK_MEM_HOST) NEED(ctx, SL_TMP_OUT, out_b, dout);
-    {
-        Timed t(ctx, SWK_K_GRAY);
-        launch_yuv420_to_bgr(ctx->stream, src->layout, dy, du, dv, y_fs, y_rs, c_fs, c_rs, kx0, ky0, count, Hr, Wr, dout);
-    }
-    if (bgr_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(bgr, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
-    return sync(ctx);
-}
-
-int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr, uint8_t *bgr,
-                       int32_t bgr_mem)
-{
-    if (!ctx) return SWK_ERR_ARG;
-    if (!src || !bgr) return fail(ctx, SWK_ERR_ARG, "null argument");
-    if (src->layout != SWK_YUV_PLANAR && src->layout != SWK_YUV_SEMIPLANAR && src->layout != SWK_YUV_MONO)
-        return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_PLANAR, SWK_YUV_SEMIPLANAR or SWK_YUV_MONO)");
     const bool semi = src->layout == SWK_YUV_SEMIPLANAR, mono = src->layout == SWK_YUV_MONO;
     if (src->bits < 8 || src->bits > 16) return fail(ctx, SWK_ERR_ARG, "bits must be in 8..16");
     const int sx = mono ? 0 : src->sx, sy = mono ? 0 : src->sy;
@@ -1409,22 +1355,22 @@ int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t 
     int kx0 = x0, ky0 = y0;
     if (src->mem == SWK_MEM_HOST) {
         // only the chroma cells that cover the rectangle, and the luma samples of those cells (the rectangle grown to origins that
-        // are multiples of 2^sx and 2^sy), go to the device, densely; the kernel then sees a frame whose origin is the rectangle's
-        // first chroma cell
+        // are multiples of 2^sx and 2^sy: at 4:2:0 at most one more row and column), go to the device, densely; the kernel then
+        // sees a frame whose origin is the rectangle's first chroma cell, and the rectangle starts at its origin's remainder
         const int cy0 = y0 >> sy, ch = ((y0 + Hr - 1) >> sy) - cy0 + 1, cx0 = x0 >> sx, cw = ((x0 + Wr - 1) >> sx) - cx0 + 1;
         const int ly0 = cy0 << sy, lx0 = cx0 << sx, lh = y0 + Hr - ly0, lw = x0 + Wr - lx0;
         const size_t yb = ((size_t)count * lh * lw * B + 15) & ~(size_t)15;
         const size_t cb = mono ? 0 : ((size_t)count * ch * cw * cbytes + 15) & ~(size_t)15;
         uint8_t *din;
         NEED(ctx, SL_TMP_IN, yb + cb * (semi ? 1 : 2), din);
-        int rc = upload_rects(ctx, din, src->y + (int64_t)ly0 * y_rs + (int64_t)lx0 * B, y_rs, y_fs, (size_t)lw * B, (size_t)lh, count);
+        int rc = copy_rects(ctx, din, src->y + (int64_t)ly0 * y_rs + (int64_t)lx0 * B, y_rs, y_fs, (size_t)lw * B, (size_t)lh, count, true);
         if (rc) return rc;
         if (!mono) {
             const int64_t coff = (int64_t)cy0 * c_rs + (int64_t)cx0 * cbytes;
-            rc = upload_rects(ctx, din + yb, src->u + coff, c_rs, c_fs, (size_t)cw * cbytes, (size_t)ch, count);
+            rc = copy_rects(ctx, din + yb, src->u + coff, c_rs, c_fs, (size_t)cw * cbytes, (size_t)ch, count, true);
             if (rc) return rc;
             if (!semi) {
-                rc = upload_rects(ctx, din + yb + cb, src->v + coff, c_rs, c_fs, (size_t)cw * cbytes, (size_t)ch, count);
+                rc = copy_rects(ctx, din + yb + cb, src->v + coff, c_rs, c_fs, (size_t)cw * cbytes, (size_t)ch, count, true);
                 if (rc) return rc;
             }
             du = din + yb; dv = semi ? nullptr : din + yb + cb;
@@ -1438,273 +1384,120 @@ int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t 
     if (bgr_mem == SWK_MEM_HOST) NEED(ctx, SL_TMP_OUT, out_b, dout);
     {
         Timed t(ctx, SWK_K_GRAY);
-        launch_yuv_to_bgr(ctx->stream, src->layout, sx, sy, src->bits, src->msb_aligned, src->full_range, dy, du, dv, y_fs, y_rs, c_fs, c_rs,
-                          kx0, ky0, count, Hr, Wr, dout);
+        // (launch_yuv420_to_bgr hands its NV12 kernel a null v whatever it is given)
+        if (yuv420) launch_yuv420_to_bgr(ctx->stream, src->layout, dy, du, dv, y_fs, y_rs, c_fs, c_rs, kx0, ky0, count, Hr, Wr, dout);
+        else launch_yuv_to_bgr(ctx->stream, src->layout, sx, sy, src->bits, src->msb_aligned, src->full_range, dy, du, dv, y_fs, y_rs, c_fs, c_rs,
+                               kx0, ky0, count, Hr, Wr, dout);
     }
     if (bgr_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(bgr, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
     return sync(ctx);
 }
 
+int32_t swk_yuv420_to_bgr(swk_ctx *ctx, const swk_yuv420 *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
+                          uint8_t *bgr, int32_t bgr_mem)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!src || !bgr) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (src->layout != SWK_YUV_I420 && src->layout != SWK_YUV_NV12) return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_I420 or SWK_YUV_NV12)");
+    static_assert(SWK_YUV_I420 == SWK_YUV_PLANAR && SWK_YUV_NV12 == SWK_YUV_SEMIPLANAR, "swk_yuv420's layouts are swk_yuv's at 4:2:0");
+    swk_yuv view{};
+    view.y = src->y; view.u = src->u; view.v = src->v; view.mem = src->mem; view.layout = src->layout; view.H = src->H; view.W = src->W;
+    view.y_row_stride = src->y_row_stride; view.y_frame_stride = src->y_frame_stride;
+    view.c_row_stride = src->c_row_stride; view.c_frame_stride = src->c_frame_stride;
+    view.sx = view.sy = 1; view.bits = 8;
+    return yuv_call(ctx, &view, true, count, x0, y0, Hr, Wr, bgr, bgr_mem);
+}
+
+int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr, uint8_t *bgr,
+                       int32_t bgr_mem)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!src || !bgr) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (src->layout != SWK_YUV_PLANAR && src->layout != SWK_YUV_SEMIPLANAR && src->layout != SWK_YUV_MONO)
+        return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_PLANAR, SWK_YUV_SEMIPLANAR or SWK_YUV_MONO)");
+    return yuv_call(ctx, src, false, count, x0, y0, Hr, Wr, bgr, bgr_mem);
+}
+
 // ---- review video (review.hip): the ROI of a call's frames, composed with the overlay, as 8-bit 4:2:0 -----------------------------
 namespace {
 
-// plane rows of `count` device frames (dense: rows x width bytes each) to a host plane with its own strides
-int download_rects(swk_ctx *ctx, uint8_t *dst, int64_t rs, int64_t fs, const uint8_t *src, size_t width, size_t rows, int count)
-{
-    const size_t per = width * rows;
-    if ((size_t)rs == width && (count == 1 || fs == (int64_t)per)) {
-        HIPCHK(ctx, hipMemcpyAsync(dst, src, per * count, hipMemcpyDeviceToHost, ctx->stream));
-        return SWK_OK;
-    }
-    for (int f = 0; f < count; ++f) {
-        uint8_t *d = dst + (int64_t)f * fs;
-        if ((size_t)rs == width) HIPCHK(ctx, hipMemcpyAsync(d, src + (size_t)f * per, per, hipMemcpyDeviceToHost, ctx->stream));
-        else HIPCHK(ctx, hipMemcpy2DAsync(d, (size_t)rs, src + (size_t)f * per, width, width, rows, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    return SWK_OK;
-}
-
-// a label's own fields, as swk_render_review_labels and a panel's caption are held to them; null = fine
-const char *label_fault(const swk_review_label &l, int nstyles, const uint8_t (*font)[8])
-{
-    if (l.scale < 1 || l.scale > 8) return "a label's scale outside 1..8";
-    if (l.len < 0 || l.len > 32) return "a label's len outside 0..32";
-    if (l.style < 0 || l.style > nstyles || l.plate < 0 || l.plate > nstyles) return "a label's style or plate outside 0..nstyles";
-    for (int j = 0; j < l.len; ++j)
-        if (l.text[j] > 127 || !font[l.text[j]][7]) return "a label's text holds a byte outside the character set";
-    return nullptr;
-}
-
-// cols == 0: the ROI's frames alone (dst holds Hc x Wc frames); cols >= 1: swk_render_review_panels' mosaic
+// plan_review (review_plan.h) refuses the call or derives its geometry, staging sizes and the kernels' table on the host; what is
+// left here reserves, copies and launches.  cols == 0: the ROI's frames alone (dst holds Hc x Wc frames); cols >= 1:
+// swk_render_review_panels' mosaic
 int review_call(swk_ctx *ctx, const swk_input *in, const swk_review *rv, const swk_review_label *labels, int nlabels, swk_yuv420_dst *dst,
                 const swk_review_panel *panels = nullptr, int npanels = 0, int cols = 0)
 {
-    if (!in || !dst) return fail(ctx, SWK_ERR_ARG, "null argument");
     // ---- every refusal comes before anything is copied or launched
-    if (!in->frames) return fail(ctx, SWK_ERR_ARG, "null frames");
-    if (in->nwin < 1 || in->n < 1 || in->Hc < 1 || in->Wc < 1) return fail(ctx, SWK_ERR_ARG, "empty batch");
-    if (in->channels != 1 && in->channels != 3) return fail(ctx, SWK_ERR_ARG, "channels must be 1 or 3");
-    if ((in->mem != SWK_MEM_HOST && in->mem != SWK_MEM_DEVICE) || (dst->mem != SWK_MEM_HOST && dst->mem != SWK_MEM_DEVICE))
-        return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
-    if (in->x0 < 0 || in->y0 < 0) return fail(ctx, SWK_ERR_ARG, "negative ROI origin");
-    if ((int64_t)in->nwin * in->n > (1 << 24)) return fail(ctx, SWK_ERR_CAPACITY, "too many frames in one call (2^24 at most)");
-    if (in->Hc > 32768 || in->Wc > 32768) return fail(ctx, SWK_ERR_CAPACITY, "ROI side above 32768");
-    const int F = in->nwin * in->n, Hc = in->Hc, Wc = in->Wc;
-    // the destination's frames: the ROI, or the mosaic of rows x cols cells of Hp x Wp
-    const bool mosaic = cols != 0;
-    if (mosaic && (npanels < 0 || npanels > kReviewMaxPanels || cols < 1 || cols > 16))
-        return fail(ctx, SWK_ERR_ARG, "npanels outside 0..15 or cols outside 1..16");
-    if (mosaic && npanels > 0 && !panels) return fail(ctx, SWK_ERR_ARG, "null panels with a non-zero count");
-    const int Hp = Hc + (Hc & 1), Wp = Wc + (Wc & 1), rows = mosaic ? (1 + npanels + cols - 1) / cols : 1;
-    if (mosaic && ((int64_t)rows * Hp > 32768 || (int64_t)cols * Wp > 32768)) return fail(ctx, SWK_ERR_CAPACITY, "mosaic side above 32768");
-    const int Hd = mosaic ? rows * Hp : Hc, Wd = mosaic ? cols * Wp : Wc, ch = (Hd + 1) / 2, cw = (Wd + 1) / 2;
-    if (in->row_stride < ((int64_t)in->x0 + Wc) * in->channels) return fail(ctx, SWK_ERR_ARG, "source row stride smaller than the ROI's row");
-    if (dst->layout != SWK_YUV_I420 && dst->layout != SWK_YUV_NV12) return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_I420 or SWK_YUV_NV12)");
-    const bool nv12 = dst->layout == SWK_YUV_NV12;
-    const int cbytes = nv12 ? 2 : 1;
-    if (!dst->y || !dst->u || (!nv12 && !dst->v)) return fail(ctx, SWK_ERR_ARG, "null YUV plane");
-    if (dst->y_row_stride < Wd || dst->c_row_stride < (int64_t)cw * cbytes) return fail(ctx, SWK_ERR_ARG, "row stride smaller than a row");
-    for (int k = 0; k < npanels; ++k) {
-        const swk_review_panel &p = panels[k];
-        if (!p.plane) return fail(ctx, SWK_ERR_ARG, "a panel's plane is null");
-        if (p.mem != SWK_MEM_HOST && p.mem != SWK_MEM_DEVICE) return fail(ctx, SWK_ERR_ARG, "a panel's mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
-        if (p.kind != SWK_PANEL_GRAY && p.kind != SWK_PANEL_LABELS) return fail(ctx, SWK_ERR_ARG, "a panel's kind is SWK_PANEL_GRAY or SWK_PANEL_LABELS");
-        if (p.kind == SWK_PANEL_GRAY && (p.gain < 1 || p.gain > 255)) return fail(ctx, SWK_ERR_ARG, "a gray panel's gain outside 1..255");
-        if (p.row_stride < Wc) return fail(ctx, SWK_ERR_ARG, "a panel's row stride smaller than the ROI's row");
-        if (p.layers < 0 || p.layers > 15) return fail(ctx, SWK_ERR_ARG, "a panel's layers outside 0..15");
-    }
-    std::vector<int32_t> meta;
-    size_t o_boxes = 0, o_bstart = 0, o_marks = 0, o_mstart = 0, o_border = 0, o_mask = 0, o_labels = 0, o_lstart = 0, o_captions = 0, o_palette = 0;
-    uint32_t mask_colour = 0; int mask_alpha = 0;
-    if (rv) {
-        if (rv->nstyles < 0 || (rv->nstyles > 0 && !rv->styles)) return fail(ctx, SWK_ERR_ARG, "styles");
-        if (rv->nboxes < 0 || rv->nmarks < 0 || (rv->nboxes > 0 && !rv->boxes) || (rv->nmarks > 0 && !rv->marks))
-            return fail(ctx, SWK_ERR_ARG, "a null array with a non-zero count, or a negative count");
-        if (rv->mark_arm < 0 || rv->border < 0) return fail(ctx, SWK_ERR_ARG, "negative mark_arm or border");
-        for (int k = 0; k < rv->nstyles; ++k)
-            if (rv->styles[k].fill_alpha < 0 || rv->styles[k].fill_alpha > 256 || rv->styles[k].line_alpha < 0 || rv->styles[k].line_alpha > 256)
-                return fail(ctx, SWK_ERR_ARG, "an alpha outside 0..256");
-        auto bad_style = [&](int st) { return st < 0 || st > rv->nstyles; };
-        auto colour = [&](int st) { const swk_review_style &y = rv->styles[st - 1]; return (uint32_t)y.b | ((uint32_t)y.g << 8) | ((uint32_t)y.r << 16); };
-        if (bad_style(rv->mask_style)) return fail(ctx, SWK_ERR_ARG, "mask style outside 0..nstyles");
-        int prev = 0;
-        for (int k = 0; k < rv->nboxes; ++k) {
-            const swk_review_box &b = rv->boxes[k];
-            if (b.frame < 0 || b.frame >= F) return fail(ctx, SWK_ERR_ARG, "a box's frame outside the call's frames");
-            if (b.frame < prev) return fail(ctx, SWK_ERR_ARG, "boxes not in ascending frame order");
-            if (bad_style(b.style)) return fail(ctx, SWK_ERR_ARG, "a box's style outside 0..nstyles");
-            prev = b.frame;
-        }
-        prev = 0;
-        for (int k = 0; k < rv->nmarks; ++k) {
-            const swk_review_mark &m = rv->marks[k];
-            if (m.frame < 0 || m.frame >= F) return fail(ctx, SWK_ERR_ARG, "a mark's frame outside the call's frames");
-            if (m.frame < prev) return fail(ctx, SWK_ERR_ARG, "marks not in ascending frame order");
-            if (bad_style(m.style)) return fail(ctx, SWK_ERR_ARG, "a mark's style outside 0..nstyles");
-            prev = m.frame;
-        }
-        if (rv->frame_style)
-            for (int f = 0; f < F; ++f)
-                if (bad_style(rv->frame_style[f])) return fail(ctx, SWK_ERR_ARG, "a frame's border style outside 0..nstyles");
-        if (nlabels < 0 || (nlabels > 0 && !labels)) return fail(ctx, SWK_ERR_ARG, "a null label array with a non-zero count, or a negative count");
-        uint8_t font[128][8];
-        review_font(font);
-        prev = 0;
-        for (int k = 0; k < nlabels; ++k) {
-            const swk_review_label &l = labels[k];
-            if (l.frame < 0 || l.frame >= F) return fail(ctx, SWK_ERR_ARG, "a label's frame outside the call's frames");
-            if (l.frame < prev) return fail(ctx, SWK_ERR_ARG, "labels not in ascending frame order");
-            if (const char *why = label_fault(l, rv->nstyles, font)) return fail(ctx, SWK_ERR_ARG, why);
-            prev = l.frame;
-        }
-        for (int k = 0; k < npanels; ++k)
-            if (const char *why = label_fault(panels[k].caption, rv->nstyles, font)) return fail(ctx, SWK_ERR_ARG, why);
-        // ---- the kernel's tables, styles resolved, in one block of int32 (launch_review, swk_internal.h)
-        o_boxes = 0;
-        meta.resize((size_t)rv->nboxes * 6);
-        for (int k = 0; k < rv->nboxes; ++k) {
-            const swk_review_box &b = rv->boxes[k];
-            int32_t *e = &meta[(size_t)k * 6];
-            e[0] = b.r0; e[1] = b.c0; e[2] = b.r1; e[3] = b.c1; e[4] = 0; e[5] = 0;
-            if (b.style == 0) { e[2] = b.r0; continue; }                  // style 0 draws nothing: an empty box
-            e[4] = (int32_t)colour(b.style);
-            e[5] = rv->styles[b.style - 1].fill_alpha | (rv->styles[b.style - 1].line_alpha << 16);
-        }
-        o_bstart = meta.size();
-        meta.resize(o_bstart + F + 1, 0);
-        for (int k = 0; k < rv->nboxes; ++k) meta[o_bstart + rv->boxes[k].frame + 1] += 1;
-        for (int f = 0; f < F; ++f) meta[o_bstart + f + 1] += meta[o_bstart + f];
-        o_marks = meta.size();
-        meta.resize(o_marks + (size_t)rv->nmarks * 4);
-        for (int k = 0; k < rv->nmarks; ++k) {
-            const swk_review_mark &m = rv->marks[k];
-            int32_t *e = &meta[o_marks + (size_t)k * 4];
-            e[0] = m.r; e[1] = m.c;
-            e[2] = m.style ? (int32_t)colour(m.style) : 0;
-            e[3] = m.style ? rv->styles[m.style - 1].line_alpha : 0;   // (alpha 0 is the identity)
-        }
-        o_mstart = meta.size();
-        meta.resize(o_mstart + F + 1, 0);
-        for (int k = 0; k < rv->nmarks; ++k) meta[o_mstart + rv->marks[k].frame + 1] += 1;
-        for (int f = 0; f < F; ++f) meta[o_mstart + f + 1] += meta[o_mstart + f];
-        o_border = meta.size();
-        if (rv->frame_style) {
-            meta.resize(o_border + (size_t)F * 2);
-            for (int f = 0; f < F; ++f) {
-                const int st = rv->frame_style[f];
-                meta[o_border + 2 * (size_t)f] = st ? (int32_t)colour(st) : 0;
-                meta[o_border + 2 * (size_t)f + 1] = st ? rv->styles[st - 1].line_alpha : -1;
-            }
-        }
-        o_mask = meta.size();
-        if (rv->mask && rv->mask_style) {
-            meta.resize(o_mask + ((size_t)Hc * Wc + 3) / 4);
-            memcpy(&meta[o_mask], rv->mask, (size_t)Hc * Wc);
-            mask_colour = colour(rv->mask_style);
-            mask_alpha = rv->styles[rv->mask_style - 1].fill_alpha;
-        }
-        auto label_record = [&](const swk_review_label &l, int32_t *e) {
-            e[0] = l.r; e[1] = l.c; e[2] = l.scale; e[3] = l.len;
-            e[4] = l.style ? (int32_t)colour(l.style) : 0;
-            e[5] = l.style ? rv->styles[l.style - 1].line_alpha : 0;          // (alpha 0 is the identity)
-            e[6] = l.plate ? (int32_t)colour(l.plate) : 0;
-            e[7] = l.plate ? rv->styles[l.plate - 1].fill_alpha : 0;
-            for (int j = 0; j < l.len; ++j) e[8 + (j >> 2)] |= (int32_t)((uint32_t)(l.text[j] - kReviewFontFirst) << (8 * (j & 3)));
-        };
-        if (npanels > 0) {
-            // the panels' captions, then the palette as b | g << 8 | r << 16
-            o_captions = meta.size();
-            meta.resize(o_captions + (size_t)npanels * 16, 0);
-            for (int k = 0; k < npanels; ++k) label_record(panels[k].caption, &meta[o_captions + (size_t)k * 16]);
-            o_palette = meta.size();
-            meta.resize(o_palette + 256);
-            uint8_t pal[256][3];
-            review_label_palette(pal);
-            for (int v = 0; v < 256; ++v) meta[o_palette + v] = (int32_t)((uint32_t)pal[v][0] | ((uint32_t)pal[v][1] << 8) | ((uint32_t)pal[v][2] << 16));
-        }
-        if (nlabels > 0) {
-            o_labels = meta.size();
-            meta.resize(o_labels + (size_t)nlabels * 16, 0);
-            for (int k = 0; k < nlabels; ++k) label_record(labels[k], &meta[o_labels + (size_t)k * 16]);
-            o_lstart = meta.size();
-            meta.resize(o_lstart + F + 1, 0);
-            for (int k = 0; k < nlabels; ++k) meta[o_lstart + labels[k].frame + 1] += 1;
-            for (int f = 0; f < F; ++f) meta[o_lstart + f + 1] += meta[o_lstart + f];
-        }
-    }
+    ReviewPlan pl;
+    const char *why = nullptr;
+    if (const int rc = plan_review(in, rv, labels, nlabels, dst, panels, npanels, cols, &pl, &why)) return fail(ctx, rc, why);
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int F = pl.F, Hc = pl.Hc, Wc = pl.Wc;
     ReviewArgs a{};
     ReviewLabels text{};
     a.src = in->frames; a.fs = in->frame_stride; a.rs = in->row_stride; a.x0 = in->x0; a.y0 = in->y0;
     a.Hc = Hc; a.Wc = Wc; a.channels = in->channels; a.layout = dst->layout;
     if (in->mem == SWK_MEM_HOST) {
         // the ROI alone, densely
-        const size_t rowb = (size_t)Wc * in->channels;
         uint8_t *din;
-        NEED(ctx, SL_TMP_IN, (size_t)F * Hc * rowb, din);
-        const int rc = upload_rects(ctx, din, in->frames + (int64_t)in->y0 * in->row_stride + (int64_t)in->x0 * in->channels, in->row_stride,
-                                    in->frame_stride, rowb, (size_t)Hc, F);
+        NEED(ctx, SL_TMP_IN, pl.src_bytes, din);
+        const int rc = copy_rects(ctx, din, in->frames + (int64_t)in->y0 * in->row_stride + (int64_t)in->x0 * in->channels, in->row_stride,
+                                  in->frame_stride, pl.rowb, (size_t)Hc, F, true);
         if (rc) return rc;
-        a.src = din; a.fs = (int64_t)Hc * rowb; a.rs = (int64_t)rowb; a.x0 = a.y0 = 0;
+        a.src = din; a.fs = (int64_t)Hc * pl.rowb; a.rs = (int64_t)pl.rowb; a.x0 = a.y0 = 0;
     }
     ReviewPanels q{};
-    q.npanels = npanels; q.ncells = rows * (mosaic ? cols : 1); q.cols = mosaic ? cols : 1;
-    {
-        // device planes are read where they lie; host planes go up densely, one after the other
-        const size_t per = ((size_t)F * Hc * Wc + 15) & ~(size_t)15;
-        size_t host_planes = 0;
-        for (int k = 0; k < npanels; ++k) host_planes += panels[k].mem == SWK_MEM_HOST;
-        uint8_t *dpl = nullptr;
-        if (host_planes) NEED(ctx, SL_TMP_AUX, host_planes * per, dpl);
-        for (int k = 0; k < npanels; ++k) {
-            const swk_review_panel &p = panels[k];
-            q.panel[k] = ReviewPanel{p.plane, p.frame_stride, p.row_stride, p.kind, p.gain, p.layers, 0};
-            if (p.mem == SWK_MEM_HOST) {
-                const int rc = upload_rects(ctx, dpl, p.plane, p.row_stride, p.frame_stride, (size_t)Wc, (size_t)Hc, F);
-                if (rc) return rc;
-                q.panel[k].plane = dpl; q.panel[k].fs = (int64_t)Hc * Wc; q.panel[k].rs = Wc;
-                dpl += per;
-            }
+    q.npanels = npanels; q.ncells = pl.rows * pl.cols; q.cols = pl.cols;
+    // device planes are read where they lie; host planes go up densely, one after the other
+    uint8_t *dpl = nullptr;
+    if (pl.host_panels) NEED(ctx, SL_TMP_AUX, pl.host_panels * pl.per, dpl);
+    for (int k = 0; k < npanels; ++k) {
+        const swk_review_panel &p = panels[k];
+        q.panel[k] = ReviewPanel{p.plane, p.frame_stride, p.row_stride, p.kind, p.gain, p.layers, 0};
+        if (p.mem == SWK_MEM_HOST) {
+            const int rc = copy_rects(ctx, dpl, p.plane, p.row_stride, p.frame_stride, (size_t)Wc, (size_t)Hc, F, true);
+            if (rc) return rc;
+            q.panel[k].plane = dpl; q.panel[k].fs = (int64_t)Hc * Wc; q.panel[k].rs = Wc;
+            dpl += pl.per;
         }
     }
-    const size_t yb = ((size_t)F * Hd * Wd + 15) & ~(size_t)15, cb = ((size_t)F * ch * cw * cbytes + 15) & ~(size_t)15;
     if (dst->mem == SWK_MEM_HOST) {
         uint8_t *dout;
-        NEED(ctx, SL_TMP_OUT, yb + cb * (nv12 ? 1 : 2), dout);
-        a.y = dout; a.u = dout + yb; a.v = nv12 ? nullptr : dout + yb + cb;
-        a.y_rs = Wd; a.y_fs = (int64_t)Hd * Wd; a.c_rs = (int64_t)cw * cbytes; a.c_fs = (int64_t)ch * a.c_rs;
+        NEED(ctx, SL_TMP_OUT, pl.yb + pl.cb * (pl.nv12 ? 1 : 2), dout);
+        a.y = dout; a.u = dout + pl.yb; a.v = pl.nv12 ? nullptr : dout + pl.yb + pl.cb;
+        a.y_rs = pl.Wd; a.y_fs = (int64_t)pl.Hd * pl.Wd; a.c_rs = (int64_t)pl.cw * pl.cbytes; a.c_fs = (int64_t)pl.ch * a.c_rs;
     } else {
-        a.y = dst->y; a.u = dst->u; a.v = nv12 ? nullptr : dst->v;
+        a.y = dst->y; a.u = dst->u; a.v = pl.nv12 ? nullptr : dst->v;
         a.y_rs = dst->y_row_stride; a.y_fs = dst->y_frame_stride; a.c_rs = dst->c_row_stride; a.c_fs = dst->c_frame_stride;
     }
     if (rv) {
         int32_t *dmeta;
-        NEED(ctx, SL_REVIEW, meta.size() * 4, dmeta);
-        if (!meta.empty()) HIPCHK(ctx, hipMemcpyAsync(dmeta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        a.boxes = dmeta + o_boxes; a.box_start = dmeta + o_bstart; a.marks = dmeta + o_marks; a.mark_start = dmeta + o_mstart;
-        a.frame_border = rv->frame_style ? dmeta + o_border : nullptr;
-        a.mask = mask_alpha ? (const uint8_t *)(dmeta + o_mask) : nullptr;
-        a.mask_colour = mask_colour; a.mask_alpha = mask_alpha;
+        NEED(ctx, SL_REVIEW, pl.meta.size() * 4, dmeta);
+        if (!pl.meta.empty()) HIPCHK(ctx, hipMemcpyAsync(dmeta, pl.meta.data(), pl.meta.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        a.boxes = dmeta + pl.o_boxes; a.box_start = dmeta + pl.o_bstart; a.marks = dmeta + pl.o_marks; a.mark_start = dmeta + pl.o_mstart;
+        a.frame_border = pl.has_border ? dmeta + pl.o_border : nullptr;
+        a.mask = pl.mask_alpha ? (const uint8_t *)(dmeta + pl.o_mask) : nullptr;
+        a.mask_colour = pl.mask_colour; a.mask_alpha = pl.mask_alpha;
         a.mark_arm = rv->mark_arm; a.border = rv->border;
-        if (nlabels > 0) { text.labels = dmeta + o_labels; text.label_start = dmeta + o_lstart; }
-        if (npanels > 0) { q.captions = dmeta + o_captions; q.palette = (const uint32_t *)(dmeta + o_palette); }
+        if (nlabels > 0) { text.labels = dmeta + pl.o_labels; text.label_start = dmeta + pl.o_lstart; }
+        if (npanels > 0) { q.captions = dmeta + pl.o_captions; q.palette = (const uint32_t *)(dmeta + pl.o_palette); }
     }
     {
         Timed t(ctx, SWK_K_GRAY);
         launch_review(ctx->stream, a, F, rv != nullptr, rv != nullptr && nlabels > 0 ? &text : nullptr);
-        if (mosaic) launch_review_panels(ctx->stream, a, F, q);
+        if (pl.mosaic) launch_review_panels(ctx->stream, a, F, q);
     }
     if (dst->mem == SWK_MEM_HOST) {
-        int rc = download_rects(ctx, dst->y, dst->y_row_stride, dst->y_frame_stride, a.y, (size_t)Wd, (size_t)Hd, F);
+        int rc = copy_rects(ctx, a.y, dst->y, dst->y_row_stride, dst->y_frame_stride, (size_t)pl.Wd, (size_t)pl.Hd, F, false);
         if (rc) return rc;
-        rc = download_rects(ctx, dst->u, dst->c_row_stride, dst->c_frame_stride, a.u, (size_t)cw * cbytes, (size_t)ch, F);
+        rc = copy_rects(ctx, a.u, dst->u, dst->c_row_stride, dst->c_frame_stride, (size_t)pl.cw * pl.cbytes, (size_t)pl.ch, F, false);
         if (rc) return rc;
-        if (!nv12) {
-            rc = download_rects(ctx, dst->v, dst->c_row_stride, dst->c_frame_stride, a.v, (size_t)cw, (size_t)ch, F);
+        if (!pl.nv12) {
+            rc = copy_rects(ctx, a.v, dst->v, dst->c_row_stride, dst->c_frame_stride, (size_t)pl.cw, (size_t)pl.ch, F, false);
             if (rc) return rc;
         }
     }
-    return sync(ctx);            // (meta lives on this stack frame)
+    return sync(ctx);            // (the table lives in pl, on this stack frame)
 }
 
 }  // namespace
@@ -2050,7 +1843,7 @@ int32_t swk_segment_shapes_u8(swk_ctx *ctx, const uint8_t *labels, int32_t mem, 
     if (mem == SWK_MEM_HOST) {
         uint8_t *din;
         NEED(ctx, SL_TMP_IN, (size_t)count * H * W, din);
-        const int rc = upload_rects(ctx, din, labels, row_stride, frame_stride, (size_t)W, (size_t)H, count);
+        const int rc = copy_rects(ctx, din, labels, row_stride, frame_stride, (size_t)W, (size_t)H, count, true);
         if (rc) return rc;
         planes = din; fs = (int64_t)H * W; rs = W;
     }
@@ -2101,7 +1894,7 @@ int32_t swk_stabilize_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem, int32
     if (mem == SWK_MEM_HOST) {
         uint8_t *din;
         NEED(ctx, SL_TMP_IN, (size_t)count * Hs * Ws * 3, din);
-        const int rc = upload_rects(ctx, din, frames, row_stride, frame_stride, (size_t)Ws * 3, (size_t)Hs, count);
+        const int rc = copy_rects(ctx, din, frames, row_stride, frame_stride, (size_t)Ws * 3, (size_t)Hs, count, true);
         if (rc) return rc;
         src = din; rs = (int64_t)Ws * 3; fs = (int64_t)Hs * rs;
     }
@@ -2141,7 +1934,7 @@ int32_t swk_stabilize_subpel_u8(swk_ctx *ctx, const uint8_t *frames, int32_t mem
     if (mem == SWK_MEM_HOST) {
         uint8_t *din;
         NEED(ctx, SL_TMP_IN, (size_t)count * Hs * Ws * 3, din);
-        const int rc = upload_rects(ctx, din, frames, row_stride, frame_stride, (size_t)Ws * 3, (size_t)Hs, count);
+        const int rc = copy_rects(ctx, din, frames, row_stride, frame_stride, (size_t)Ws * 3, (size_t)Hs, count, true);
         if (rc) return rc;
         src = din; rs = (int64_t)Ws * 3; fs = (int64_t)Hs * rs;
     }

@@ -6,6 +6,7 @@
 #include "swk.h"
 #include "swk_debug.h"
 #include "batch_plan.h"
+#include "review_plan.h"
 
 namespace swk {
 
@@ -175,8 +176,8 @@ void launch_yuv_to_bgr(hipStream_t s, int layout, int sx, int sy, int bits, int 
 // frame_border [F][2] = (colour, line alpha or -1 for none) or null.  draw = false: the conversion alone (nothing but the source, the
 // geometry and the destination is read).  text (with draw; null = no labels): labels [nlabels][16] = (r, c, scale, len, ink colour,
 // ink alpha, plate colour, plate alpha, 8 words of text as font indices = byte - kReviewFontFirst) with label_start [F + 1]; an alpha
-// of 0 stands for style 0 / plate 0 (the blend is then the identity).
-constexpr int kReviewFontFirst = 32, kReviewFontCount = 59;          // the font table covers bytes 32 (space) .. 90 ('Z')
+// of 0 stands for style 0 / plate 0 (the blend is then the identity).  The host builds all of these in one block (plan_review,
+// review_plan.h, where kReviewFontFirst, kReviewFontCount and the host's copy of the font, review_font, live).
 struct ReviewArgs {
     const uint8_t *src;
     int64_t fs, rs;
@@ -191,15 +192,13 @@ struct ReviewArgs {
 // the labels go to the kernel as an argument of their own, which only the instantiation with text has: the others keep their arguments
 struct ReviewLabels { const int32_t *labels, *label_start; };
 void launch_review(hipStream_t s, const ReviewArgs &a, int F, bool draw, const ReviewLabels *text = nullptr);
-// the font's rows of byte ch (0..127): rows[0..6], rows[7] = 1 where ch is in the character set (host)
-void review_font(uint8_t out[128][8]);
 // The stage panels of a mosaic (swk_render_review_panels): a's destination describes the mosaic, ncells = rows * cols cells of
 // Hp x Wp luma pixels (Hc, Wc made even), cell k at ((k / cols) * Hp, (k % cols) * Wp).  launch_review draws cell 0 (it writes the
 // ROI's pixels at the mosaic's strides); launch_review_panels writes the rest in one launch per 32768 frames: cell k = 1..npanels from
 // panel[k - 1] (device memory; frame f, pixel (r, c) at plane + f * fs + r * rs + c) with the layers of a whose bit is set and label
 // record captions[k - 1] (16 words as in ReviewLabels; len 0 = none), Y = 16 and U = V = 128 in the cells after them and in every
-// cell's pad row / column.  palette [256] = b | g << 8 | r << 16 (device; read only where a panel is SWK_PANEL_LABELS).
-constexpr int kReviewMaxPanels = 15;
+// cell's pad row / column.  palette [256] = b | g << 8 | r << 16 (device; read only where a panel is SWK_PANEL_LABELS; the host's
+// review_label_palette and kReviewMaxPanels = 15 are in review_plan.h).
 struct ReviewPanel { const uint8_t *plane; int64_t fs, rs; int kind, gain, layers, pad_; };
 struct ReviewPanels {
     ReviewPanel panel[kReviewMaxPanels];
@@ -208,7 +207,6 @@ struct ReviewPanels {
     int npanels, ncells, cols;
 };
 void launch_review_panels(hipStream_t s, const ReviewArgs &a, int F, const ReviewPanels &q);
-void review_label_palette(uint8_t out[256][3]);
 
 // classify_input.hip
 void launch_classifier_input(hipStream_t s, const uint8_t *crops, const int64_t *offsets, const int32_t *hw, int nseg,
