@@ -277,6 +277,61 @@ typedef struct swk_yuv {
 int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
                        uint8_t *bgr, int32_t bgr_mem);
 
+/* ---- interlaced video: every field as a whole picture (motion-adaptive, edge-directed, exact integers) ----------
+ * Camcorder footage (1080i) stores two fields, taken 1/50 or 1/59.94 s apart, in the even and odd rows of one frame.
+ * cv2.VideoCapture hands the reference the woven frame, in which a moving bird is two combed half-birds; doubling each
+ * field's rows moves every still edge up and down at field rate.  This is this project's own definition (no other
+ * deinterlacer is claimed to be equalled): where nothing moves it reproduces the stored picture exactly, and it
+ * interpolates only where something moves.
+ *
+ * A plane is the H x W sample array of one component (Y, U or V) of stored frame t: P_t, with d-bit unsigned sample values
+ * (for MSB-aligned sources the value is word >> (16 - d)).  Every plane is processed on its own, by the same rule.
+ * Row y of a plane belongs to the top field if (y + parity0) is even, otherwise to the bottom field; parity0 is the parity,
+ * in the picture, of the described plane's row 0: 0 for whole pictures, and luma and chroma have their own (y_parity0,
+ * c_parity0).  With sy = 1 chroma row j belongs to field j & 1, the convention of interlaced 4:2:0.
+ * tff = 1: a frame's top field is earlier in time (It); tff = 0: the bottom field is (Ib).  Stored frame t gives output
+ * picture 2t (its first field in time) and output picture 2t + 1 (its second field).
+ *
+ * The output picture for (frame t, kept parity p) keeps the rows of P_t that have parity p.  Every other row y is computed
+ * per column x, all in int32:
+ *   up = y - 1 if that row exists, else y + 1;  dn = y + 1 if it exists, else y - 1;  a one-row plane: out = P_t[y][x].
+ *   c = P_t[up][x],  e = P_t[dn][x],  xl = max(x - 1, 0),  xr = min(x + 1, W - 1)
+ *   score = |P_t[up][xl] - P_t[dn][xl]| + |c - e| + |P_t[up][xr] - P_t[dn][xr]| - 1;   pred = (c + e) >> 1
+ *   direction j in {-2, -1, 1, 2} is admissible iff x - 1 - |j| >= 0 and x + 1 + |j| <= W - 1, and then
+ *     score_j = sum over k = -1..1 of |P_t[up][x + k + j] - P_t[dn][x + k - j]|,  pred_j = (P_t[up][x + j] + P_t[dn][x - j]) >> 1
+ *   search: j = -1 is taken (score, pred = score_j, pred_j) if admissible and score_j < score, strictly; only if it was
+ *   taken j = -2 is tried the same way; then j = +1 against the current score; only if it was taken, j = +2.
+ *   temporal = 0: out = pred.  temporal = 1: Pv = P_(t-1), Nx = P_(t+1), a frame that does not exist replaced by P_t;
+ *     for the frame's first field in time Bf = Pv, Af = P_t, otherwise Bf = P_t, Af = Nx;
+ *     b = Bf[y][x],  a = Af[y][x],  dm = (b + a) >> 1,  td0 = |b - a|
+ *     td1 = (|Pv[up][x] - c| + |Pv[dn][x] - e|) >> 1,  td2 = (|Nx[up][x] - c| + |Nx[dn][x] - e|) >> 1
+ *     diff = max(td0 >> 1, td1, td2);   out = min(max(pred, dm - diff), dm + diff)
+ * Consequences: the result lies in 0 .. 2^d - 1 (pred and dm are means of two samples, and the clamp only moves pred towards dm); a sample
+ * depends only on frames t - 1, t, t + 1 at rows y - 1 .. y + 1 and columns x - 3 .. x + 3; where those three frames agree
+ * on that footprint, out = P_t[y][x] (diff = 0 and dm = P_t[y][x]): a still scene comes out as it was stored; at d = 16 every
+ * sum fits int32 (the largest is 3 * 65535).
+ * Limits: no inverse telecine, no streams of mixed field order, no per-frame field flags; the chroma of 4:2:0 is
+ * deinterlaced per plane and not re-sited. */
+typedef struct swk_deinterlace {
+    int32_t tff, rate /* 1: first field of each frame only, 2: both */, temporal;
+    int32_t has_prev, has_next;    /* the first / last described frame is context only: it gives no output */
+    int32_t y_parity0, c_parity0, reserved_;
+} swk_deinterlace;
+
+/* src is read exactly as swk_yuv_to_bgr reads it (host or device memory; planar, semiplanar and mono; 8..16 bits; every
+ * (sx, sy)).  nout = rate * (count - has_prev - has_next) pictures come out, in temporal order.  bgr, if not null, receives
+ * dense [nout][Hr][Wr][3]: swk_yuv_to_bgr's formula applied to the deinterlaced samples, so a source whose three neighbouring
+ * frames are equal gives swk_yuv_to_bgr's bytes.  planes, if not null, receives the deinterlaced samples themselves:
+ * Y [nout][Hr][Wr], then U and V [nout][ch][cw] over chroma rows (y0 >> sy) .. ((y0 + Hr - 1) >> sy) and the matching
+ * columns; bytes at 8 bits, otherwise LSB-aligned little-endian 16-bit words.  The rectangle is a crop of the picture-wide
+ * definition: the footprint outside it is read from the described planes, and the planes' borders are the picture's
+ * borders.  Of a host source only the samples the footprint needs go to the device.  SWK_ERR_ARG: everything
+ * swk_yuv_to_bgr refuses, rate outside {1, 2}, count - has_prev - has_next < 1, both outputs null, an odd device address
+ * of planes with 2-byte samples. */
+int32_t swk_yuv_deinterlace(swk_ctx *ctx, const swk_yuv *src, const swk_deinterlace *d, int32_t count,
+                            int32_t x0, int32_t y0, int32_t Hr, int32_t Wr,
+                            uint8_t *bgr, int32_t bgr_mem, void *planes, int32_t planes_mem);
+
 /* ---- review video: BGR -> 8-bit 4:2:0 YUV, with the overlay of a count drawn in ---------------------------------
  * The reference shows what it counted with `--export`: one overlay PNG per segment (data_structures.py:65-113).  Here the
  * ROI frames of a call leave as 4:2:0 video frames (what Y4MWriter stores and ffmpeg / mpv open) with the segments, the

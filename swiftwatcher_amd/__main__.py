@@ -22,7 +22,12 @@ DIR/stabilization.csv, one row per frame (frame_number, dy, dx, sad, sad_unshift
 "stabilize": {"search": S, "moved_frames": k, "max_shift": m}.
 --stabilize-subpel (with --stabilize) adds the quarter-pixel stage: every frame is resampled at the best of the 25 quarter-pixel
 shifts around the integer one.  stabilization.csv then has three more columns -- shift_y, shift_x: the total shift in pixels with
-two decimal places (-1.25), and sad_subpel -- and the "stabilize" object gains "subpel": true and "fractional_frames": k."""
+two decimal places (-1.25), and sad_subpel -- and the "stabilize" object gains "subpel": true and "fractional_frames": k.
+--deinterlace {bob,frame,weave} counts an interlaced source (header tags It / Ib; without the option it is refused by name, and a
+progressive source with it is) on the pictures of its fields (deinterlace.DeinterlacingReader): bob = every field, at twice the frame
+rate ("frames" is then twice the stored count), frame = each frame's first field, weave = the stored frames as they are;
+--deinterlace-spatial interpolates without the temporal clamp.  The JSON line gains "deinterlace": {"mode": m, "field_order": "t" or
+"b", "stored_frames": n, "frames": k}."""
 import argparse
 import json
 import os
@@ -95,6 +100,10 @@ def build_parser():
                         "stabilization.csv")
     p.add_argument("--stabilize-subpel", action="store_true",
                    help="with --stabilize: refine every frame's shift to a quarter pixel and resample it there")
+    p.add_argument("--deinterlace", choices=("bob", "frame", "weave"), default=None,
+                   help="count an interlaced source on the pictures of its fields: bob = every field at twice the frame rate, frame = "
+                        "each frame's first field, weave = the stored frames as they are")
+    p.add_argument("--deinterlace-spatial", action="store_true", help="with --deinterlace: spatial interpolation only, no temporal clamp")
     p.add_argument("--windows-per-call", type=int, default=1, metavar="K", help="queue-fuls segmented per GPU call")
     p.add_argument("--device", type=int, default=0, metavar="D", help="GPU index")
     return p
@@ -114,6 +123,8 @@ def plan(argv):
         parser.error("--review-stages needs --review PATH")
     if args.stabilize_subpel and not args.stabilize:
         parser.error("--stabilize-subpel needs --stabilize")
+    if args.deinterlace_spatial and not args.deinterlace:
+        parser.error("--deinterlace-spatial needs --deinterlace")
     shared = None
     try:
         if args.corners is not None:
@@ -174,9 +185,15 @@ def main(argv=None):
         from .segment_classification import SegmentClassifier
         classifier = SegmentClassifier(args.classify, device="cuda:%d" % args.device)
     for source, corners in jobs:
+        opened = None
         try:
-            reader = open_y4m(source, args.start, args.end)
+            reader = opened = open_y4m(source, args.start, args.end, **({"interlaced": True} if args.deinterlace else {}))
+            if args.deinterlace:
+                from .deinterlace import DeinterlacingReader
+                reader = DeinterlacingReader(reader, None, args.deinterlace, not args.deinterlace_spatial, device=args.device)
         except (OSError, ValueError) as exc:
+            if hasattr(opened, "close"):             # (the source was opened and then refused: a progressive header with --deinterlace)
+                opened.close()
             print("swiftwatcher_amd: cannot read %s: %s" % (source, exc), file=sys.stderr)
             return 1
         stem = "stdin" if source == "-" else os.path.splitext(os.path.basename(source))[0]
@@ -221,6 +238,8 @@ def main(argv=None):
                 os.makedirs(out_dir, exist_ok=True)
                 write_csv(os.path.join(out_dir, "stabilization.csv"), counted.shifts, *sub)
             line["stabilize"] = summary(counted.shifts, args.stabilize, *sub)
+        if args.deinterlace:
+            line["deinterlace"] = reader.fields
         print(json.dumps(line), flush=True)
     return 0
 

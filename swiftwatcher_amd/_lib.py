@@ -97,6 +97,10 @@ class Yuv(ctypes.Structure):
                                   ("msb_aligned", ctypes.c_int32), ("full_range", ctypes.c_int32), ("reserved_", ctypes.c_int32)]
 
 
+class Deinterlace(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("tff", "rate", "temporal", "has_prev", "has_next", "y_parity0", "c_parity0", "reserved_")]
+
+
 class Yuv420Dst(ctypes.Structure):
     _fields_ = [("y", ctypes.c_void_p), ("u", ctypes.c_void_p), ("v", ctypes.c_void_p), ("mem", ctypes.c_int32),
                 ("layout", ctypes.c_int32), ("y_row_stride", ctypes.c_int64), ("y_frame_stride", ctypes.c_int64),
@@ -198,6 +202,8 @@ _SIGS = {
     "swk_batch_run_groups": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.c_int32, ctypes.POINTER(Params), ctypes.POINTER(Output)]),
     "swk_yuv420_to_bgr": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv420)] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int32]),
     "swk_yuv_to_bgr": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv)] + [ctypes.c_int32] * 5 + [ctypes.c_void_p, ctypes.c_int32]),
+    "swk_yuv_deinterlace": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Yuv), ctypes.POINTER(Deinterlace)] + [ctypes.c_int32] * 5 +
+                            [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32]),
     "swk_bgr_to_yuv420": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Yuv420Dst)]),
     "swk_render_review": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Review), ctypes.POINTER(Yuv420Dst)]),
     "swk_render_review_labels": (ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(Input), ctypes.POINTER(Review), ctypes.c_void_p, ctypes.c_int32,
@@ -752,15 +758,8 @@ class Context:
         self._check(self._lib.swk_yuv420_to_bgr(self._h, ctypes.byref(src), count, int(x0), int(y0), int(Hr), int(Wr), optr, omem))
         return out[0] if single else out
 
-    def yuv_to_bgr(self, y, u=None, v=None, *, subsampling=(1, 1), bits=8, msb_aligned=False, full_range=False, rect=None, device_out=False):
-        """swk_yuv_to_bgr: planar, semiplanar or mono YUV frames of 8..16 bits, limited or full range -> BGR (the definition in
-        include/swk.h).  y: (count, H, W) or (H, W), uint8 at bits = 8 and uint16 above.  subsampling = (sx, sy), the chroma shifts:
-        (0, 0) 4:4:4, (1, 0) 4:2:2, (1, 1) 4:2:0, (2, 0) 4:1:1; a chroma plane is (count, ceil(H / 2^sy), ceil(W / 2^sx)).  Planar: u
-        and v.  Semiplanar (NV12, NV16, NV24, P010, P016, P210): v=None and u the interleaved plane, (count, ch, cw, 2) or
-        (count, ch, 2 cw).  Mono: u=None.  msb_aligned: 16-bit words that hold the sample in their upper bits (P010).  All numpy
-        arrays, or all torch tensors on this context's GPU (read in place); contiguous along a row, any row pitch and frame stride.
-        rect: (x0, y0, Wr, Hr) inside the frame, None = the whole frame.  Returns BGR (count, Hr, Wr, 3) (no count axis for a 2-D y):
-        a numpy array, or with device_out=True a torch uint8 tensor on the GPU -- what batch_run / batch_run_groups take as frames."""
+    def _yuv_source(self, y, u, v, subsampling, bits, msb_aligned, full_range):
+        """(Yuv struct, count, H, W, single, the arrays the struct points into) of yuv_to_bgr's plane arguments"""
         bits, (sx, sy) = int(bits), (int(subsampling[0]), int(subsampling[1]))
         B = 2 if bits > 8 else 1
         np_dtype = np.uint16 if B == 2 else np.uint8
@@ -807,10 +806,22 @@ class Context:
                 if ch >= 0 and not ok:
                     raise ValueError("the interleaved chroma plane must be (count, %d, %d, 2) or (count, %d, %d)" % (ch, cw, ch, 2 * cw))
                 layout = YUV_SEMIPLANAR
-        x0, y0, Wr, Hr = rect if rect is not None else (0, 0, W, H)
         src = Yuv(y=yptr, u=uptr, v=vptr, mem=MEM_DEVICE if on_device else MEM_HOST, layout=layout, H=H, W=W,
                   y_row_stride=ystr[1], y_frame_stride=ystr[0], c_row_stride=cstr[1], c_frame_stride=cstr[0],
                   sx=sx, sy=sy, bits=bits, msb_aligned=int(bool(msb_aligned)), full_range=int(bool(full_range)))
+        return src, count, H, W, single, planes
+
+    def yuv_to_bgr(self, y, u=None, v=None, *, subsampling=(1, 1), bits=8, msb_aligned=False, full_range=False, rect=None, device_out=False):
+        """swk_yuv_to_bgr: planar, semiplanar or mono YUV frames of 8..16 bits, limited or full range -> BGR (the definition in
+        include/swk.h).  y: (count, H, W) or (H, W), uint8 at bits = 8 and uint16 above.  subsampling = (sx, sy), the chroma shifts:
+        (0, 0) 4:4:4, (1, 0) 4:2:2, (1, 1) 4:2:0, (2, 0) 4:1:1; a chroma plane is (count, ceil(H / 2^sy), ceil(W / 2^sx)).  Planar: u
+        and v.  Semiplanar (NV12, NV16, NV24, P010, P016, P210): v=None and u the interleaved plane, (count, ch, cw, 2) or
+        (count, ch, 2 cw).  Mono: u=None.  msb_aligned: 16-bit words that hold the sample in their upper bits (P010).  All numpy
+        arrays, or all torch tensors on this context's GPU (read in place); contiguous along a row, any row pitch and frame stride.
+        rect: (x0, y0, Wr, Hr) inside the frame, None = the whole frame.  Returns BGR (count, Hr, Wr, 3) (no count axis for a 2-D y):
+        a numpy array, or with device_out=True a torch uint8 tensor on the GPU -- what batch_run / batch_run_groups take as frames."""
+        src, count, H, W, single, _keep = self._yuv_source(y, u, v, subsampling, bits, msb_aligned, full_range)
+        x0, y0, Wr, Hr = rect if rect is not None else (0, 0, W, H)
         shape = (count, int(Hr), int(Wr), 3) if Hr > 0 and Wr > 0 and count > 0 else (1, 1, 1, 3)          # (the library refuses those)
         if device_out:
             import torch
@@ -821,6 +832,62 @@ class Context:
             optr, omem = _ptr(out), MEM_HOST
         self._check(self._lib.swk_yuv_to_bgr(self._h, ctypes.byref(src), count, int(x0), int(y0), int(Hr), int(Wr), optr, omem))
         return out[0] if single else out
+
+    def yuv_deinterlace(self, frames_or_planes, rect, tff, rate=2, temporal=True, has_prev=False, has_next=False, parity0=(0, 0),
+                        want_planes=False, *, subsampling=(1, 1), bits=8, msb_aligned=False, full_range=False, device_out=False,
+                        want_bgr=True):
+        """swk_yuv_deinterlace: the fields of interlaced frames as whole pictures (the definition in include/swk.h).
+        frames_or_planes: the planes (y, u, v), (y, uv) or (y,) as yuv_to_bgr takes them, with its format keywords -- or a list of
+        io_y4m frames of one format (Yuv420Frame, YuvFrame, or the frames of a pipe's reader that hold one rectangle), of which the
+        rectangle grown by the definition's footprint is gathered; the format and parity0 then come from the frames.
+        rect: (x0, y0, Wr, Hr) in the picture, None = the whole picture.  tff: the top field is the earlier one.  rate: 2 = both
+        fields of every frame, 1 = the first one.  has_prev / has_next: the first / last frame is context only.
+        Returns BGR (nout, Hr, Wr, 3), nout = rate * (count - has_prev - has_next): a numpy array, or with device_out=True a torch
+        tensor on the GPU.  want_planes: (BGR, (Y, U, V)) with the deinterlaced samples (U = V = None for mono); want_bgr=False: BGR
+        is None."""
+        if not isinstance(frames_or_planes, tuple) and hasattr(frames_or_planes[0], "y"):
+            planes, fmt, rect, parity0 = _gather_fields(frames_or_planes, rect)
+            subsampling, bits, full_range, msb_aligned = fmt[0], fmt[1], fmt[2], False
+        else:
+            planes = tuple(frames_or_planes)
+        y, u, v = (tuple(planes) + (None, None))[:3]
+        src, count, H, W, _single, _keep = self._yuv_source(y, u, v, subsampling, bits, msb_aligned, full_range)
+        if _single:
+            raise ValueError("deinterlacing takes frame stacks (count, H, W)")
+        x0, y0, Wr, Hr = (int(c) for c in (rect if rect is not None else (0, 0, W, H)))
+        d = Deinterlace(tff=int(bool(tff)), rate=int(rate), temporal=int(bool(temporal)), has_prev=int(bool(has_prev)),
+                        has_next=int(bool(has_next)), y_parity0=int(parity0[0]), c_parity0=int(parity0[1]))
+        nout = int(rate) * (count - d.has_prev - d.has_next)
+        ok = Hr > 0 and Wr > 0 and nout > 0 and x0 >= 0 and y0 >= 0 and 0 <= src.sx <= 2 and 0 <= src.sy <= 1          # (else the library refuses)
+        sx, sy = (0, 0) if u is None else (src.sx, src.sy)
+        ch, cw = (((y0 + Hr - 1) >> sy) - (y0 >> sy) + 1, ((x0 + Wr - 1) >> sx) - (x0 >> sx) + 1) if ok else (1, 1)
+        luma, chroma = (nout * Hr * Wr, 0 if u is None else nout * ch * cw) if ok else (1, 0)
+        dt = np.uint16 if src.bits > 8 else np.uint8
+        bgr = pl = None
+        bptr = pptr = None
+        mem = MEM_DEVICE if device_out else MEM_HOST
+        if device_out:
+            import torch
+            if want_bgr:
+                bgr = torch.empty((nout, Hr, Wr, 3) if ok else (1, 1, 1, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
+                bptr = ctypes.c_void_p(bgr.data_ptr())
+            if want_planes:
+                pl = torch.empty(luma + 2 * chroma, dtype=torch.uint16 if src.bits > 8 else torch.uint8, device="cuda:%d" % self.device)
+                pptr = ctypes.c_void_p(pl.data_ptr())
+        else:
+            if want_bgr:
+                bgr = np.empty((nout, Hr, Wr, 3) if ok else (1, 1, 1, 3), np.uint8)
+                bptr = _ptr(bgr)
+            if want_planes:
+                pl = np.empty(luma + 2 * chroma, dt)
+                pptr = _ptr(pl)
+        self._check(self._lib.swk_yuv_deinterlace(self._h, ctypes.byref(src), ctypes.byref(d), count, x0, y0, Hr, Wr, bptr, mem, pptr, mem))
+        if not want_planes:
+            return bgr
+        Y = pl[:luma].reshape(nout, Hr, Wr)
+        if u is None:
+            return bgr, (Y, None, None)
+        return bgr, (Y, pl[luma:luma + chroma].reshape(nout, ch, cw), pl[luma + chroma:].reshape(nout, ch, cw))
 
     # ---- review video ----
     def _review_io(self, frames, rect, layout, device_out, dst, out_hw=None):
@@ -1312,6 +1379,40 @@ class Context:
             optr, omem = out.ctypes.data, MEM_HOST
         return dict(source=(fptr, fmem, count, Hs, Ws, fs, rs), rect=(y0, x0, Ho, Wo), search=search, anchor=(aptr, amem, abytes),
                     out=out, out_ptr=(optr, omem), count=count, side=2 * search + 1 if 0 <= search <= 16 else 1, keep=keep)
+
+
+def _gather_fields(frames, rect):
+    """((Y, U, V) stacks, ((sx, sy), bits, full_range), the rectangle inside them, parity0) for Context.yuv_deinterlace over io_y4m
+    frames of one format.  The stacks hold the chroma cells of the rectangle grown by one chroma row and three chroma columns on every
+    side, clipped to the picture, and those cells' luma samples: every row and column of the definition's footprint that the picture
+    has, so the stacks' borders act as borders only where they are the picture's."""
+    first = frames[0]
+    H, W = first.shape[:2]
+    sx, sy = getattr(first, "sx", 1), getattr(first, "sy", 1)
+    bits, full = getattr(first, "bits", 8), getattr(first, "full_range", False)
+    mono = first.u is None
+    oy, ox = getattr(first, "origin", (0, 0))
+    fmt = lambda f: (f.shape, getattr(f, "sx", 1), getattr(f, "sy", 1), getattr(f, "bits", 8), getattr(f, "full_range", False),          # noqa: E731
+                     f.u is None, getattr(f, "origin", (0, 0)), f.y.shape)
+    if any(fmt(f) != fmt(first) for f in frames):
+        raise ValueError("the frames of one deinterlacing call have one format and hold one rectangle")
+    x0, y0, Wr, Hr = (int(c) for c in (rect if rect is not None else (0, 0, W, H)))
+    if x0 < 0 or y0 < 0 or Wr < 1 or Hr < 1 or x0 + Wr > W or y0 + Hr > H:
+        raise ValueError("rectangle outside the frame")
+    CH, CW = ((H - 1) >> sy) + 1, ((W - 1) >> sx) + 1
+    ca, cb = max((y0 >> sy) - 1, 0), min(((y0 + Hr - 1) >> sy) + 2, CH)
+    cl, cr = max((x0 >> sx) - 3, 0), min(((x0 + Wr - 1) >> sx) + 4, CW)
+    la, lb, ll, lr = ca << sy, min(cb << sy, H), cl << sx, min(cr << sx, W)
+    hh, hw = first.y.shape
+    if la < oy or ll < ox or lb > oy + hh or lr > ox + hw:
+        raise ValueError("the frames do not hold the rectangle plus the deinterlacer's footprint (one row, three columns)")
+    Y = np.stack([f.y[la - oy:lb - oy, ll - ox:lr - ox] for f in frames])
+    U = V = None
+    if not mono:
+        coy, cox = oy >> sy, ox >> sx
+        U = np.stack([f.u[ca - coy:cb - coy, cl - cox:cr - cox] for f in frames])
+        V = np.stack([f.v[ca - coy:cb - coy, cl - cox:cr - cox] for f in frames])
+    return (Y, U, V), ((sx, sy), bits, full), (x0 - ll, y0 - la, Wr, Hr), (la & 1, ca & 1)
 
 
 def stage_frames(frames, y0, y1, x0, x1, dst, threads=4):

@@ -1318,10 +1318,8 @@ static int copy_rects(swk_ctx *ctx, uint8_t *dev, const uint8_t *host, int64_t r
     return SWK_OK;
 }
 
-// swk_yuv_to_bgr after its null and layout checks; yuv420: swk_yuv420_to_bgr's view of its argument (sx = sy = 1, bits = 8, where
-// the checks of bits, shifts and 2-byte samples cannot fire), which takes its own launcher
-static int yuv_call(swk_ctx *ctx, const swk_yuv *src, bool yuv420, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr, uint8_t *bgr,
-                    int32_t bgr_mem)
+// what swk_yuv_to_bgr and swk_yuv_deinterlace refuse alike, after their null and layout checks (bgr_mem: where the BGR result goes)
+static int yuv_refusal(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr, int32_t bgr_mem)
 {
     const bool semi = src->layout == SWK_YUV_SEMIPLANAR, mono = src->layout == SWK_YUV_MONO;
     if (src->bits < 8 || src->bits > 16) return fail(ctx, SWK_ERR_ARG, "bits must be in 8..16");
@@ -1348,6 +1346,20 @@ static int yuv_call(swk_ctx *ctx, const swk_yuv *src, bool yuv420, int32_t count
         if (((uintptr_t)src->y & 1) || (!mono && ((uintptr_t)src->u & 1)) || (!mono && !semi && ((uintptr_t)src->v & 1)))
             return fail(ctx, SWK_ERR_ARG, "odd plane address with 2-byte samples");
     }
+    return SWK_OK;
+}
+
+// swk_yuv_to_bgr after its null and layout checks; yuv420: swk_yuv420_to_bgr's view of its argument (sx = sy = 1, bits = 8, where
+// the checks of bits, shifts and 2-byte samples cannot fire), which takes its own launcher
+static int yuv_call(swk_ctx *ctx, const swk_yuv *src, bool yuv420, int32_t count, int32_t x0, int32_t y0, int32_t Hr, int32_t Wr, uint8_t *bgr,
+                    int32_t bgr_mem)
+{
+    const int refused = yuv_refusal(ctx, src, count, x0, y0, Hr, Wr, bgr_mem);
+    if (refused) return refused;
+    const bool semi = src->layout == SWK_YUV_SEMIPLANAR, mono = src->layout == SWK_YUV_MONO;
+    const int sx = mono ? 0 : src->sx, sy = mono ? 0 : src->sy;
+    const int B = src->bits > 8 ? 2 : 1;                              // bytes per sample
+    const int cbytes = semi ? 2 * B : B;                              // bytes per chroma sample position in a chroma row
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t out_b = (size_t)count * Hr * Wr * 3;
     const uint8_t *dy = src->y, *du = mono ? nullptr : src->u, *dv = mono || semi ? nullptr : src->v;
@@ -1416,6 +1428,94 @@ int32_t swk_yuv_to_bgr(swk_ctx *ctx, const swk_yuv *src, int32_t count, int32_t 
     if (src->layout != SWK_YUV_PLANAR && src->layout != SWK_YUV_SEMIPLANAR && src->layout != SWK_YUV_MONO)
         return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_PLANAR, SWK_YUV_SEMIPLANAR or SWK_YUV_MONO)");
     return yuv_call(ctx, src, false, count, x0, y0, Hr, Wr, bgr, bgr_mem);
+}
+
+// ---- deinterlacing (deinterlace.hip): every field of interlaced frames as a whole picture ----------------------------------------
+int32_t swk_yuv_deinterlace(swk_ctx *ctx, const swk_yuv *src, const swk_deinterlace *d, int32_t count, int32_t x0, int32_t y0, int32_t Hr,
+                            int32_t Wr, uint8_t *bgr, int32_t bgr_mem, void *planes, int32_t planes_mem)
+{
+    if (!ctx) return SWK_ERR_ARG;
+    if (!src || !d) return fail(ctx, SWK_ERR_ARG, "null argument");
+    if (!bgr && !planes) return fail(ctx, SWK_ERR_ARG, "no output asked for: bgr and planes are both null");
+    if (src->layout != SWK_YUV_PLANAR && src->layout != SWK_YUV_SEMIPLANAR && src->layout != SWK_YUV_MONO)
+        return fail(ctx, SWK_ERR_ARG, "unknown YUV layout (SWK_YUV_PLANAR, SWK_YUV_SEMIPLANAR or SWK_YUV_MONO)");
+    const int refused = yuv_refusal(ctx, src, count, x0, y0, Hr, Wr, bgr ? bgr_mem : (int32_t)SWK_MEM_HOST);
+    if (refused) return refused;
+    if (planes && planes_mem != SWK_MEM_HOST && planes_mem != SWK_MEM_DEVICE) return fail(ctx, SWK_ERR_ARG, "mem must be SWK_MEM_HOST or SWK_MEM_DEVICE");
+    if (d->rate != 1 && d->rate != 2) return fail(ctx, SWK_ERR_ARG, "rate must be 1 (first fields) or 2 (both fields)");
+    const int hp = d->has_prev != 0, hn = d->has_next != 0;
+    if (count - hp - hn < 1) return fail(ctx, SWK_ERR_ARG, "no frame is left between the context frames");
+    const bool semi = src->layout == SWK_YUV_SEMIPLANAR, mono = src->layout == SWK_YUV_MONO;
+    const int sx = mono ? 0 : src->sx, sy = mono ? 0 : src->sy;
+    const int B = src->bits > 8 ? 2 : 1;
+    if (B == 2 && planes && planes_mem == SWK_MEM_DEVICE && ((uintptr_t)planes & 1))
+        return fail(ctx, SWK_ERR_ARG, "odd plane address with 2-byte samples");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    DeintJob job{count, hp, d->rate * (count - hp - hn), d->rate, d->tff != 0, d->temporal != 0};
+    // the rectangle in each plane, and the plane's own size
+    const int H = src->H, W = src->W, CH = ((H - 1) >> sy) + 1, CW = ((W - 1) >> sx) + 1;
+    const int cy0 = y0 >> sy, ch = ((y0 + Hr - 1) >> sy) - cy0 + 1, cx0 = x0 >> sx, cw = ((x0 + Wr - 1) >> sx) - cx0 + 1;
+    const size_t yb = (size_t)job.nout * Hr * Wr * B, cb = mono ? 0 : (size_t)job.nout * ch * cw * B;
+    const int msb = B == 2 && src->msb_aligned ? 16 - src->bits : 0;
+    DeintPlane pl[3];
+    pl[0] = DeintPlane{src->y, src->y_frame_stride, src->y_row_stride, 1, 0, 0, H, W, y0, x0, Hr, Wr, d->y_parity0 & 1, msb, nullptr};
+    if (!mono) {
+        pl[1] = DeintPlane{src->u, src->c_frame_stride, src->c_row_stride, semi ? 2 : 1, 0, 0, CH, CW, cy0, cx0, ch, cw, d->c_parity0 & 1, msb, nullptr};
+        pl[2] = pl[1];
+        pl[2].src = semi ? src->u + B : src->v;
+    }
+    const int np = mono ? 1 : 3;
+    if (src->mem == SWK_MEM_HOST) {
+        // of each plane only the rectangle grown by the definition's footprint, one row and three columns on every side, clipped to
+        // the plane, goes to the device, densely (interleaved chroma as it lies: one copy serves U and V)
+        size_t at[3] = {0, 0, 0}, total = 0;
+        int ry0[3], rx0[3], rh[3], rw[3];
+        const int ncopy = mono ? 1 : (semi ? 2 : 3);
+        for (int k = 0; k < ncopy; ++k) {
+            const DeintPlane &p = pl[k];
+            ry0[k] = p.py0 > 0 ? p.py0 - 1 : 0; rx0[k] = p.px0 > 3 ? p.px0 - 3 : 0;
+            rh[k] = (p.py0 + p.ph + 1 < p.PH ? p.py0 + p.ph + 1 : p.PH) - ry0[k];
+            rw[k] = (p.px0 + p.pw + 3 < p.PW ? p.px0 + p.pw + 3 : p.PW) - rx0[k];
+            at[k] = total;
+            total += ((size_t)count * rh[k] * rw[k] * p.step * B + 15) & ~(size_t)15;
+        }
+        uint8_t *din;
+        NEED(ctx, SL_TMP_IN, total, din);
+        for (int k = 0; k < ncopy; ++k) {
+            DeintPlane &p = pl[k];
+            const size_t width = (size_t)rw[k] * p.step * B;
+            const int rc = copy_rects(ctx, din + at[k], p.src + (int64_t)ry0[k] * p.rs + (int64_t)rx0[k] * p.step * B, p.rs, p.fs, width,
+                                      (size_t)rh[k], count, true);
+            if (rc) return rc;
+            p.src = din + at[k]; p.rs = (int64_t)width; p.fs = (int64_t)rh[k] * p.rs; p.oy = ry0[k]; p.ox = rx0[k];
+        }
+        if (semi) { pl[2] = pl[1]; pl[2].src = pl[1].src + B; }
+    }
+    // the scratch planar picture stack, laid out as `planes` is: a device `planes` is the stack itself
+    uint8_t *dpl = (uint8_t *)planes;
+    if (!planes || planes_mem == SWK_MEM_HOST) NEED(ctx, SL_TMP_AUX, yb + 2 * cb, dpl);
+    pl[0].dst = dpl;
+    if (!mono) { pl[1].dst = dpl + yb; pl[2].dst = dpl + yb + cb; }
+    const size_t out_b = (size_t)job.nout * Hr * Wr * 3;
+    uint8_t *dout = bgr;
+    if (bgr && bgr_mem == SWK_MEM_HOST) NEED(ctx, SL_TMP_OUT, out_b, dout);
+    {
+        Timed t(ctx, SWK_K_GRAY);
+        for (int k = 0; k < np; ++k) launch_deint_plane(ctx->stream, pl[k], job, B == 2);
+        if (bgr) {
+            // the stack as frames whose origin is the rectangle's first chroma cell: the rectangle starts at its origin's remainder
+            // (ky0, kx0), and the luma base is moved back by that much -- the kernel reads no sample in front of the rectangle
+            const int ky0 = y0 - (cy0 << sy), kx0 = x0 - (cx0 << sx);
+            const int64_t y_rs = (int64_t)Wr * B, c_rs = (int64_t)cw * B;
+            const uintptr_t ybase = (uintptr_t)dpl - (uintptr_t)(ky0 * y_rs + (int64_t)kx0 * B);
+            launch_yuv_to_bgr(ctx->stream, mono ? SWK_YUV_MONO : SWK_YUV_PLANAR, sx, sy, src->bits, 0, src->full_range, (const uint8_t *)ybase,
+                              mono ? nullptr : dpl + yb, mono ? nullptr : dpl + yb + cb, (int64_t)Hr * y_rs, y_rs, (int64_t)ch * c_rs, c_rs, kx0, ky0,
+                              job.nout, Hr, Wr, dout);
+        }
+    }
+    if (bgr && bgr_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(bgr, dout, out_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (planes && planes_mem == SWK_MEM_HOST) HIPCHK(ctx, hipMemcpyAsync(planes, dpl, yb + 2 * cb, hipMemcpyDeviceToHost, ctx->stream));
+    return sync(ctx);
 }
 
 // ---- review video (review.hip): the ROI of a call's frames, composed with the overlay, as 8-bit 4:2:0 -----------------------------

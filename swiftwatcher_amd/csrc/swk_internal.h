@@ -169,6 +169,29 @@ void launch_yuv_to_bgr(hipStream_t s, int layout, int sx, int sy, int bits, int 
                        const uint8_t *u, const uint8_t *v, int64_t y_fs, int64_t y_rs, int64_t c_fs, int64_t c_rs, int x0, int y0, int F,
                        int Hr, int Wr, uint8_t *out);
 
+// deinterlace.hip: one component plane of `count` interlaced frames -> the rectangle [py0, py0 + ph) x [px0, px0 + pw) of that plane
+// in nout deinterlaced pictures, dense [nout][ph][pw] LSB-aligned samples (swk_yuv_deinterlace, include/swk.h).  Device memory.
+// (tests/deinterlace_host.py mirrors both structs in ctypes and checks its copy against swk_deint_layout of the host-check build:
+//  a member added here is added there and in that function.)
+struct DeintPlane {
+    const uint8_t *src;            // the sample at row oy, column ox of the plane in the first described frame
+    int64_t fs, rs;                // frame and row stride in bytes
+    int step;                      // samples from one sample of a row to the next (2: interleaved chroma)
+    int oy, ox;                    // (a staged copy of a host source starts inside the plane; 0, 0 for the plane itself)
+    int PH, PW;                    // the plane's size: its borders are the picture's borders
+    int py0, px0, ph, pw;
+    int parity0;                   // parity, in the picture, of the plane's row 0
+    int msb;                       // 16 - bits for MSB-aligned words, else 0
+    uint8_t *dst;
+};
+struct DeintJob {
+    int count;                     // described frames
+    int first;                     // the first frame that gives output (has_prev)
+    int nout;                      // pictures made: rate x frames that give output
+    int rate, tff, temporal;
+};
+void launch_deint_plane(hipStream_t s, const DeintPlane &p, const DeintJob &j, int wide);
+
 // review.hip: F source frames' ROI (frame f at src + f * fs, ROI pixel (r, c) at + (y0 + r) * rs + (x0 + c) * channels; device memory)
 // composed with the review overlay and converted to 8-bit 4:2:0 in device memory (include/swk.h, swk_render_review).  The host
 // resolves styles: boxes [nboxes][6] = (r0, c0, r1, c1, colour b | g << 8 | r << 16, fill alpha | line alpha << 16) with

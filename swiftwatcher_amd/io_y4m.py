@@ -12,8 +12,9 @@ same pixels.
 
 open_y4m(path) picks the reader.  Y4MReader: 8-bit 4:2:0, progressive; it refuses everything else by name.  YuvReader: C420*,
 C422, C444, C411 and Cmono, with the suffixes p9, p10, p12, p14, p16 (mono9, mono10, mono12, mono16: little-endian 16-bit samples),
-limited range or, with XCOLORRANGE=FULL, full range.  Interlaced files, C444alpha and FRAME lines with parameters are refused by
-name.
+limited range or, with XCOLORRANGE=FULL, full range.  C444alpha, mixed field order (Im) and FRAME lines with parameters are refused by
+name, and so are interlaced files (It, Ib) unless the reader is made with interlaced=: it then hands out the stored, woven frames
+and says which field is the earlier one (field_order), for deinterlace.DeinterlacingReader to make pictures of.
 
 A source that can only be read once, front to back, and whose length nobody knows -- "-" (standard input), a FIFO, a descriptor, a
 binary file object: `ffmpeg -i in.mp4 -f yuv4mpegpipe - | python -m swiftwatcher_amd - --corners ...` -- gets Y4MStreamReader: the
@@ -207,14 +208,16 @@ def _chroma_format(value):
     return None
 
 
-def _parse_header(line, general=False):
+def _parse_header(line, general=False, interlaced=None):
     """(width, height, fps numerator, denominator) of a YUV4MPEG2 stream header line (without its newline).  general: every format
-    of open_y4m is accepted, and the result ends with its (mono, sx, sy, bits, full_range)."""
+    of open_y4m is accepted, and the result ends with its (mono, sx, sy, bits, full_range).  interlaced: None refuses It / Ib by
+    name; any other value accepts them, and the result ends with the field order, "p" (I?, Ip or no I tag), "t" or "b".  Im (mixed)
+    is always refused."""
     tags = line.split(b" ")
     if tags[0] != MAGIC:
         raise ValueError("not a YUV4MPEG2 file")
     width = height = rate = None
-    fmt, full = (False, 1, 1, 8), False
+    fmt, full, order = (False, 1, 1, 8), False, "p"
     for raw in tags[1:]:
         if not raw:
             continue
@@ -229,8 +232,14 @@ def _parse_header(line, general=False):
                 num, den = value.split(":")
                 rate = (int(num), int(den))
             elif kind == "I":
-                if value not in ("?", "p"):
+                if value in ("t", "b") and interlaced is None:
+                    raise ValueError("interlaced YUV4MPEG2 files are not supported (tag %s) unless they are deinterlaced: "
+                                     "deinterlace= / --deinterlace" % tag)
+                if value == "m":
+                    raise ValueError("interlaced YUV4MPEG2 files are not supported (tag %s): mixed field order" % tag)
+                if value not in ("?", "p", "t", "b"):          # (any other value, worded as it always was)
                     raise ValueError("interlaced YUV4MPEG2 files are not supported (tag %s)" % tag)
+                order = "p" if value == "?" else value
             elif kind == "C" and general:
                 fmt = _chroma_format(value)
                 if fmt is None:
@@ -255,9 +264,8 @@ def _parse_header(line, general=False):
             raise ValueError("the YUV4MPEG2 header has no %s tag" % name)
     if width < 1 or height < 1 or rate[0] < 1 or rate[1] < 1:
         raise ValueError("the YUV4MPEG2 header needs positive W, H and F (got W%d H%d F%d:%d)" % (width, height, rate[0], rate[1]))
-    if general:
-        return width, height, rate[0], rate[1], fmt + (full,)
-    return width, height, rate[0], rate[1]
+    out = (width, height, rate[0], rate[1]) + ((fmt + (full,),) if general else ())
+    return out if interlaced is None else out + (order,)
 
 
 class _Frames:
@@ -288,7 +296,7 @@ class Y4MReader(ArrayReader):
     (io_video.py:13-82; the frame one past the end is served once by the last good frame, null frames after that), frames handed
     out as Yuv420Frame views of the mapping -- only the pages the ROI touches are ever read from disk.  fps comes from the header."""
 
-    def __init__(self, path, start=0, end=0):
+    def __init__(self, path, start=0, end=0, interlaced=None):
         with open(path, "rb") as fh:
             head = fh.read(4096)
         if not head.startswith(MAGIC):
@@ -296,7 +304,7 @@ class Y4MReader(ArrayReader):
         eol = head.find(b"\n")
         if eol < 0:
             raise ValueError("the YUV4MPEG2 header line does not end: %s" % path)
-        width, height, num, den = _parse_header(head[:eol])
+        width, height, num, den, self.field_order = (_parse_header(head[:eol], interlaced=interlaced) + ("p",))[:5]
         mapping = np.memmap(path, dtype=np.uint8, mode="r")
         first = eol + 1
         frames = _Frames(mapping, first, width, height, 0)
@@ -356,7 +364,7 @@ class YuvReader(ArrayReader):
     """Y4MReader's bookkeeping over a memory-mapped YUV4MPEG2 file of any format open_y4m accepts, frames handed out as YuvFrame
     views of the mapping.  full_range: None = what the header says (XCOLORRANGE=FULL, else limited), True / False override it."""
 
-    def __init__(self, path, start=0, end=0, full_range=None):
+    def __init__(self, path, start=0, end=0, full_range=None, interlaced=None):
         with open(path, "rb") as fh:
             head = fh.read(4096)
         if not head.startswith(MAGIC):
@@ -364,7 +372,7 @@ class YuvReader(ArrayReader):
         eol = head.find(b"\n")
         if eol < 0:
             raise ValueError("the YUV4MPEG2 header line does not end: %s" % path)
-        width, height, num, den, fmt = _parse_header(head[:eol], general=True)
+        width, height, num, den, fmt, self.field_order = (_parse_header(head[:eol], general=True, interlaced=interlaced) + ("p",))[:6]
         if full_range is not None:
             fmt = fmt[:4] + (bool(full_range),)
         mapping = np.memmap(path, dtype=np.uint8, mode="r")
@@ -553,7 +561,7 @@ class Y4MStreamReader:
     in the caller's thread, and never more than one FRAME marker beyond the last frame handed out.  read_seconds / read_bytes: time
     in, and bytes from, the source's read calls."""
 
-    def __init__(self, source, start=0, end=0, full_range=None, crop_region=None, min_seg_size=(24, 24), ahead=1):
+    def __init__(self, source, start=0, end=0, full_range=None, crop_region=None, min_seg_size=(24, 24), ahead=1, interlaced=None):
         self._src = _ByteSource(source)
         self.filepath = source if isinstance(source, (str, bytes)) or hasattr(source, "__fspath__") else self._src.name
         try:
@@ -567,7 +575,7 @@ class Y4MStreamReader:
                     break
             if one != b"\n":
                 raise ValueError("the YUV4MPEG2 header line does not end: %s" % self._src.name)
-            width, height, num, den, fmt = _parse_header(bytes(head), general=True)
+            width, height, num, den, fmt, self.field_order = (_parse_header(bytes(head), general=True, interlaced=interlaced) + ("p",))[:6]
         except BaseException:
             self._src.close()
             raise
@@ -593,6 +601,7 @@ class Y4MStreamReader:
         self._decoded, self._marked, self._eof, self._fail = 0, False, False, None
         self._scratch = None                       # one whole picture: what is read past (frames before start, pixels outside the rectangle)
         self._first, self._first_wanted = None, True
+        self._second, self._keep_second = None, self.field_order in ("t", "b")          # (an interlaced video's first picture needs two frames)
         # the producer's own counters (it runs ahead of what has been handed out): next number, frames read, read errors, last frame, shape
         self._cur = [self.start_frame, 0, 0, None, self.frame_shape]
         self._cv = threading.Condition()
@@ -713,7 +722,8 @@ class Y4MStreamReader:
         if self._fail is not None:
             raise self._fail
         first = self._decoded == 0 and self._first_wanted
-        if first or (keep and self._rect is None):
+        second = self._decoded == 1 and self._first_wanted and self._keep_second
+        if first or second or (keep and self._rect is None):
             buf = np.empty(self._body_bytes, np.uint8)          # a frame that is held whole owns its buffer
         else:
             if self._scratch is None:
@@ -728,6 +738,8 @@ class Y4MStreamReader:
         planes = self._planes(buf)
         if first:
             self._first = planes
+        if second:
+            self._second = planes
         self._marked = False
         self._decoded += 1
         self._wake()
@@ -746,6 +758,8 @@ class Y4MStreamReader:
         if k < self._decoded:
             if k == 0 and self._first is not None:          # read early by read_frame(0, increment=False)
                 return self._held(self._first)
+            if k == 1 and self._second is not None:
+                return self._held(self._second)
             raise ValueError("a stream cannot go back to frame %d" % k)
         return self._body(True) if self._seek(k) else None
 
@@ -827,15 +841,20 @@ class Y4MStreamReader:
 
     def read_frame(self, frame_number, increment=True):
         """The video's first frame in full, until the first window has been handed out (swift_counting_algorithm reads it for
-        generate_regions); None when the video has no frame.  A stream has no other frame to offer out of turn."""
+        generate_regions); None when the video has no frame.  A stream has no other frame to offer out of turn -- but the second one
+        of an interlaced video (read_frame(1, increment=False)), which its first picture needs."""
+        if frame_number == 1 and self._keep_second and not (increment or self._handed or self._thread is not None):
+            if self.read_frame(0, increment=False) is not None and self._second is None and self._decoded == 1 and self._seek(1):
+                self._body(False)
+            return None if self._second is None else self._whole(self._second)
         if frame_number != 0 or increment or self._handed or self._thread is not None:
             raise ValueError("a stream reader only offers read_frame(0, increment=False), before its first window")
         if self._first is None and self._decoded == 0 and self._seek(0):
             self._body(False)
-        return None if self._first is None else self._whole_first()
+        return None if self._first is None else self._whole(self._first)
 
-    def _whole_first(self):
-        y, u, v = self._first
+    def _whole(self, planes):
+        y, u, v = planes
         if self._plain420:
             return Yuv420Frame(y, u, v)
         return YuvFrame(y, u, v, self.subsampling, self.bits, self.full_range)
@@ -869,6 +888,8 @@ class Y4MStreamReader:
             frames.append(f); numbers.append(k); stamps.append(t)
         self._handed = True
         self._first, self._first_wanted = None, False
+        if self.next_frame_number > 1:               # (a second frame read early stays until it has been handed out)
+            self._second = None
         return frames, numbers, stamps
 
     @property
@@ -893,7 +914,7 @@ class Y4MStreamReader:
         if self._thread is None or not self._thread.is_alive():          # (a thread still waiting in read keeps its descriptor)
             self._src.close()
         self._items.clear()
-        self._first = self._scratch = None
+        self._first = self._second = self._scratch = None
 
     def __enter__(self):
         return self
@@ -915,13 +936,15 @@ def _is_stream(source):
     return hasattr(source, "readinto") or hasattr(source, "read")
 
 
-def open_y4m(source, start=0, end=0, full_range=None, crop_region=None, min_seg_size=(24, 24), ahead=1):
+def open_y4m(source, start=0, end=0, full_range=None, crop_region=None, min_seg_size=(24, 24), ahead=1, interlaced=None):
     """The reader of a YUV4MPEG2 video.  The path of a regular file: Y4MReader for an 8-bit 4:2:0 limited-range progressive file,
     YuvReader for every other supported format (crop_region, min_seg_size and ahead do not apply to them).  A source that can only
     be read once, front to back -- the path of a FIFO, "-" (standard input), a file descriptor, a binary file object --:
-    Y4MStreamReader.  full_range: None = what the header says, True / False override it."""
+    Y4MStreamReader.  full_range: None = what the header says, True / False override it.  interlaced: None refuses interlaced files
+    (It / Ib) by name; any other value accepts them -- the reader's field_order is then "p", "t" or "b", and its frames are the stored,
+    woven frames (deinterlace.DeinterlacingReader makes pictures of them)."""
     if _is_stream(source):
-        return Y4MStreamReader(source, start, end, full_range, crop_region, min_seg_size, ahead)
+        return Y4MStreamReader(source, start, end, full_range, crop_region, min_seg_size, ahead, interlaced)
     path = source
     with open(path, "rb") as fh:
         head = fh.read(4096)
@@ -930,21 +953,24 @@ def open_y4m(source, start=0, end=0, full_range=None, crop_region=None, min_seg_
     eol = head.find(b"\n")
     if eol < 0:
         raise ValueError("the YUV4MPEG2 header line does not end: %s" % path)
-    fmt = _parse_header(head[:eol], general=True)[4]
+    fmt = _parse_header(head[:eol], general=True, interlaced=interlaced)[4]
     full = fmt[4] if full_range is None else bool(full_range)
     if fmt[:4] == (False, 1, 1, 8) and not full:
-        return Y4MReader(path, start, end)
-    return YuvReader(path, start, end, full)
+        return Y4MReader(path, start, end, interlaced)
+    return YuvReader(path, start, end, full, interlaced)
 
 
 class Y4MWriter:
-    """Writes a YUV4MPEG2 file of progressive frames: append(y, u, v) per frame (append(y) for mono), close() (or use it as a context
+    """Writes a YUV4MPEG2 file of progressive frames (interlaced="t" / "b": of woven frames whose top / bottom field is the earlier one,
+    tagged It / Ib): append(y, u, v) per frame (append(y) for mono), close() (or use it as a context
     manager).  fps: a number (30, 29.97...: stored as the nearest fraction) or a (numerator, denominator) pair.  chroma: "420",
     "422", "444", "411" or "mono"; bits: 8, 9, 10, 12, 14 or 16 (uint16 planes, LSB-aligned, written little-endian); full_range adds
     XCOLORRANGE=FULL.  The defaults write 8-bit 4:2:0."""
 
-    def __init__(self, path, width, height, fps, chroma="420", bits=8, full_range=False):
+    def __init__(self, path, width, height, fps, chroma="420", bits=8, full_range=False, interlaced="p"):
         from fractions import Fraction
+        if interlaced not in ("p", "t", "b"):
+            raise ValueError('interlaced is "p" (progressive), "t" (top field first) or "b" (bottom field first)')
         if isinstance(fps, (tuple, list)):
             num, den = int(fps[0]), int(fps[1])
         else:
@@ -963,8 +989,8 @@ class Y4MWriter:
         self.mono, self.bits = chroma == "mono", int(bits)
         self.sx, self.sy = (0, 0) if self.mono else _SUBSAMPLING[chroma]
         self._fh = open(path, "wb")
-        self._fh.write(b"%s W%d H%d F%d:%d Ip A0:0 C%s%s\n" % (MAGIC, self.width, self.height, num, den, tag.encode("ascii"),
-                                                              b" XCOLORRANGE=FULL" if full_range else b""))
+        self._fh.write(b"%s W%d H%d F%d:%d I%s A0:0 C%s%s\n" % (MAGIC, self.width, self.height, num, den, interlaced.encode("ascii"),
+                                                               tag.encode("ascii"), b" XCOLORRANGE=FULL" if full_range else b""))
 
     def append(self, y, u=None, v=None):
         ch, cw = ((self.height - 1) >> self.sy) + 1, ((self.width - 1) >> self.sx) + 1

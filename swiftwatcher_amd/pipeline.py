@@ -14,7 +14,7 @@ from . import image_filtering as img
 def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size=21, classifier=None, min_seg_size=(24, 24),
                              device=0, keep_stages=False, windows_per_call=1, corners=None, export_dir=None, params=None,
                              track_by_window=True, review=None, review_text=False, review_stages=(), shape_props=False, stabilize=0,
-                             stabilize_subpel=False):
+                             stabilize_subpel=False, deinterlace=None, deinterlace_temporal=True):
     """Same call order as __main__.py:62-100.  corners = ((x1, y1), (x2, y2)) of the chimney's top edge: crop region
     and ROI mask are then generated from the video's first frame (:62-63) instead of being passed in.  Returns the tracker's detected events (lists of Segment objects,
     the structure the reference hands to event classification).  windows_per_call > 1 reads that many queue-fuls
@@ -37,7 +37,16 @@ def swift_counting_algorithm(reader, crop_region=None, roi_mask=None, queue_size
     sees a stabilized video.  A reader that is a StabilizingReader already is taken as it is.  0 (the default): nothing is different.
     stabilize_subpel=True (with stabilize; ValueError without): the quarter-pixel stage after the integer search
     (swk_stabilize_subpel_u8 in swk_stabilize_u8's place): every frame is resampled at the best of the 25 quarter-pixel shifts
-    around the integer one.  False (the default): nothing is different."""
+    around the integer one.  False (the default): nothing is different.  deinterlace: "bob", "frame" or "weave" for an interlaced
+    source (a reader of io_y4m opened with interlaced=...: YUV4MPEG2 tags It / Ib): the reader is wrapped in a
+    deinterlace.DeinterlacingReader, which hands out the fields as whole pictures -- "bob": every field, at twice the frame rate;
+    "frame": each frame's first field; "weave": the stored frames as they are (one more GPU call per window, swk_yuv_deinterlace;
+    none for "weave"); the regions are then made from its first picture, and stabilize works on its pictures.  deinterlace_temporal
+    =False: spatial interpolation only.  A source whose header says progressive is a ValueError.  None (the default): nothing is
+    different."""
+    if deinterlace:
+        from .deinterlace import wrap
+        reader = wrap(reader, deinterlace, None, deinterlace_temporal, min_seg_size, device)
     if corners is not None:
         first_frame = reader.read_frame(0, increment=False)                        # :62
         crop_region, roi_mask, _ = img.generate_regions(first_frame, corners)      # :63
@@ -189,11 +198,13 @@ def count_swifts(frames, crop_region=None, roi_mask=None, fps=30.0, params=None,
     review.ReviewWriter: the review video of the count), review_text (text in a review made from a path) and review_stages (stage
     images as panels in it) as in swift_counting_algorithm; so is shape_props=True (among **kw): the events' segments then carry the
     shape properties; and stabilize=S (among **kw; True = 8): shaken footage is brought back onto its first frame before it is
-    segmented, with stabilize_subpel=True to a quarter pixel."""
+    segmented, with stabilize_subpel=True to a quarter pixel; and deinterlace="bob" | "frame" | "weave" (among **kw, with
+    deinterlace_temporal): an interlaced source is counted on the pictures of its fields -- without it an interlaced file is refused
+    by name, and with it a progressive one is."""
     opened = None
     if _is_video_source(frames):
         from .io_y4m import open_y4m
-        frames = opened = open_y4m(frames)
+        frames = opened = open_y4m(frames, **({"interlaced": True} if kw.get("deinterlace") else {}))
     reader = frames if hasattr(frames, "get_n_frames") else ArrayReader(frames, fps=fps)
     try:
         events = swift_counting_algorithm(reader, crop_region, roi_mask, params=params, review=review, review_text=review_text,
@@ -276,7 +287,8 @@ def schedule_videos(readers, sizes, segment, consume, in_flight=4, windows_per_c
 
 def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows_per_call=1, classifier=None, queue_size=21,
                         min_seg_size=(24, 24), device=0, fps=30.0, pad_factor=2.0, params=None, track_by_window=True, reviews=None,
-                        review_text=False, review_stages=(), shape_props=False, stabilize=0, stabilize_subpel=False):
+                        review_text=False, review_stages=(), shape_props=False, stabilize=0, stabilize_subpel=False, deinterlace=None,
+                        deinterlace_temporal=True):
     """count_swifts over a list of videos (the reference's loop over its video list, __main__.py:21), several videos at a time on one
     GPU: `in_flight` videos are open, each with its own SegmentTracker, and every GPU call (swk_batch_run_groups) segments the next
     windows_per_call queue-fuls of each of them at once, every video at its own crop region.  Each tracker still sees its video's
@@ -289,11 +301,26 @@ def count_swifts_videos(videos, regions=None, corners=None, in_flight=4, windows
     review_text: the writers made here from paths also write text (its review_text=); review_stages: and show these stage images as
     panels (its review_stages=).  shape_props: as swift_counting_algorithm's; one shape call per group of a GPU call, since the
     groups' geometries differ.  stabilize and stabilize_subpel: as swift_counting_algorithm's, one StabilizingReader per video.
+    deinterlace: as swift_counting_algorithm's for every video, or one value per video (None for a progressive one), with
+    deinterlace_temporal; one DeinterlacingReader per interlaced video.
     Returns [(count, events), ...] in input order."""
     from .io_y4m import open_y4m
-    readers = [open_y4m(v) if _is_video_source(v) else v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps) for v in videos]
-    opened = [r for r, v in zip(readers, videos) if r is not v and hasattr(r, "close")]          # (closed again when the count is done)
+    modes = list(deinterlace) if isinstance(deinterlace, (list, tuple)) else [deinterlace] * len(videos)
+    if len(modes) != len(videos):
+        raise ValueError("one deinterlace mode (or None) per video")
+    readers, opened = [], []                         # (what is opened here is closed again when the count is done)
     try:
+        for v, mode in zip(videos, modes):
+            if _is_video_source(v):
+                r = open_y4m(v, **({"interlaced": True} if mode else {}))
+                if hasattr(r, "close"):
+                    opened.append(r)
+            else:
+                r = v if hasattr(v, "get_n_frames") else ArrayReader(v, fps=fps)
+            if mode:
+                from .deinterlace import wrap
+                r = wrap(r, mode, None, deinterlace_temporal, min_seg_size, device)
+            readers.append(r)
         return _count_videos(readers, regions, corners, in_flight, windows_per_call, classifier, queue_size, min_seg_size, device,
                              pad_factor, params, track_by_window, reviews, review_text, review_stages, shape_props, stabilize,
                              stabilize_subpel)
@@ -323,7 +350,8 @@ def _count_videos(readers, regions, corners, in_flight, windows_per_call, classi
     for r, (crop_region, _) in zip(readers, regions):
         if hasattr(r, "set_region"):                 # a reader of a pipe (io_y4m.Y4MStreamReader): it keeps only what this loop reads
             r.set_region(crop_region, min_seg_size)
-            r.ahead = max(r.ahead, windows_per_call)
+            if hasattr(r, "ahead"):                  # (a deinterlacing reader offers set_region over files too, which do not read ahead)
+                r.ahead = max(r.ahead, windows_per_call)
     trackers = [SegmentTracker(mask) for _, mask in regions]
     sizes = [(cr[1][0] - cr[0][0]) * (cr[1][1] - cr[0][1]) for cr, _ in regions]
     reviews = list(reviews) if reviews is not None else [None] * len(readers)
